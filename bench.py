@@ -1,9 +1,15 @@
 #!/usr/bin/env python3
 """Headline benchmark: condensed-MPC QP solves per second, pendulum Nc=5, batch 1e6 (f64).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run is lean: set-up, W warm-up steps, the K timed steps, the outputs of the last timed step (with
+--dump-outputs DIR: DIR/x.npy and DIR/exitflag.npy, see dump_outputs()) and ONE JSON line on stdout with the
+headline fields (metric, value, unit, ms_per_step, higher_is_better, dtype, ...).  Everything else below -- the
+oracle check of what the timed region wrote, the roofline and single-launch sections, the CPU baseline, the other
+configurations, the exchange measurement of N > 1 -- runs only with --full.
 
 One "step" = one pass of the hot path (lmpc_solve_batch_device: constraint shift, dual
 active-set solve, primal recovery) over one batch of 1e6 synthetic parameter points per GPU,
@@ -21,7 +27,7 @@ sends on its own link) -- is timed behind the timed region and reported as confi
 By default three batches are kept in flight on three HIP streams (each with its own solver
 handle): the streaming pass of one batch overlaps the latency-bound iterating pass of another.
 
-Rank 0 prints a COMPACT JSON line (< 4 KB; compact_line(); the driver keeps only a tail of stdout) -- once as soon as
+With --full, rank 0 prints a COMPACT JSON line (< 4 KB; compact_line(); the driver keeps only a tail of stdout) -- once as soon as
 the headline is measured, and again, with the per-config summaries, as the LAST line of stdout; the full report
 (every histogram, verification block and note) goes to bench_full.json and to stderr:
   value / ms_per_step   whole-job throughput of the timed region (cold HBM, batches in flight)
@@ -453,6 +459,33 @@ def describe(w):
     else:
         body = f"{w.name} (n={qp.n}, m={qp.m}, nth={qp.nth})"
     return f"{w.workload}: {body}, {w.n_local} parameter points per GPU, cold start, first move u0 returned"
+
+
+def metric_name(workload):
+    return ("condensed-MPC QP solves/sec (batch 1e6 params), pendulum Nc=5"
+            if workload == "pendulum" else f"condensed-MPC QP solves/sec ({workload})")
+
+
+DUMP_LIMIT = 64 * 2**20      # bytes --dump-outputs may write in all
+
+
+def dump_outputs(d, x, exitflag, seed=2024):
+    """--dump-outputs: what one step hands its caller -- the solutions x (batch x nout, in the run's real type) and the
+    exit flags (small integers, written as float32: exact) -- as d/x.npy and d/exitflag.npy.  A batch whose arrays
+    outgrow DUMP_LIMIT is cut to a fixed, seeded sample of rows (the same rows in every run with the same arguments),
+    whose row numbers go to d/rows.npy (float64).  Returns the names of the files written."""
+    os.makedirs(d, exist_ok=True)
+    xh = x.cpu().numpy()
+    fh = exitflag.cpu().numpy().astype(np.float32)
+    per_row = xh.itemsize * (xh.size // max(len(xh), 1)) + fh.itemsize
+    arrays = {"x": xh, "exitflag": fh}
+    if len(xh) * per_row > DUMP_LIMIT - 4096:
+        keep = (DUMP_LIMIT - 4096) // (per_row + 8)
+        rows = np.sort(np.random.default_rng(seed).choice(len(xh), keep, replace=False))
+        arrays = {"x": xh[rows], "exitflag": fh[rows], "rows": rows.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a))
+    return [name + ".npy" for name in arrays]
 
 
 def multi_abi_check(torch, lmpc, g, nout, n_per_dev, seed):
@@ -1251,7 +1284,7 @@ def main():
                     help="skip the other BASELINE configurations (profiling runs: keeps the kernel trace to one workload)")
     ap.add_argument("--gather", default="after", choices=["after", "final", "step", "none"],
                     help="N > 1: the shards are independent, the timed region holds no collective; 'after' (default) "
-                         "times ONE RCCL gather of a batch's x and exit flags to rank 0 behind the timed region and "
+                         "times (with --full) ONE RCCL gather of a batch's x and exit flags to rank 0 behind the timed region and "
                          "reports it next to the headline (config.exchange); 'final' puts that gather inside the timed "
                          "region, 'step' all-gathers after every step (overlapped with the next solve), 'none' skips it")
     ap.add_argument("--no-single-launch", action="store_true",
@@ -1273,7 +1306,16 @@ def main():
                     help="lmpc_set_option(NAME, VALUE) on every handle of the headline workload (recorded in config.options)")
     ap.add_argument("--streams", type=int, default=3,
                     help="independent batches kept in flight per GPU (each has its own handle and HIP stream)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed region, write what its last step computed (rank 0's shard) to DIR/x.npy and "
+                         "DIR/exitflag.npy (see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: oracle check of the timed region, roofline and single-launch "
+                         "sections, CPU baseline, the other configurations, the N > 1 exchange; full report in "
+                         "bench_full.json")
     args = ap.parse_args()
+    if args.dump_outputs is not None and args.steps < 1:
+        ap.error("--dump-outputs needs --steps >= 1 (it writes what the last timed step computed)")
 
     import torch
     import torch.distributed as dist
@@ -1339,7 +1381,7 @@ def main():
 
     do_gather = world > 1 and args.gather == "step"
     final_gather = world > 1 and args.gather == "final"
-    after_gather = world > 1 and args.gather == "after"
+    after_gather = world > 1 and args.gather == "after" and args.full     # (a measurement of its own: --full only)
     if final_gather or after_gather:
         # gather to rank 0: every rank sends its shard straight to the root over its own xGMI link
         # (ncclSend/ncclRecv pairs), N-1 links in parallel -- a ring all-gather would move N-1 shards
@@ -1428,6 +1470,10 @@ def main():
         gather_to_root(xbuf[last_b[0]], fbuf[last_b[0]])
     fence()
     elapsed = time.perf_counter() - t0
+    # what the last timed step computed, before anything below launches on the same buffers again
+    dumped = None
+    if args.dump_outputs is not None and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, xbuf[last_b[0]], fbuf[last_b[0]])
     exchange_ms = None
     if after_gather and args.steps:
         # the exchange a single consumer of all shards would add: one batch's solutions and flags to rank 0
@@ -1440,24 +1486,26 @@ def main():
     # ---- what the timed region wrote, checked against the oracle (untimed; behind the exchange measurement so that
     # rank 0's check does not sit inside the other ranks' gather time): the last steps of every stream
     verification = None
-    if rank == 0 and args.steps and not do_gather:
-        verification = W.verify_steps(list(range(max(0, args.steps - max(nstreams, 2)), args.steps)))
-    # average device time of one launch on its stream = event span of the stream / its launches (diagnostic,
-    # untimed repeat of the same steps, at most 200 of them)
-    nrep = min(args.steps, 200)
-    ev0 = [torch.cuda.Event(enable_timing=True) for _ in streams]
-    ev1 = [torch.cuda.Event(enable_timing=True) for _ in streams]
-    for e_, s_ in zip(ev0, streams):
-        e_.record(s_)
-    for k in range(nrep):
-        step(k)
-    for e_, s_ in zip(ev1, streams):
-        e_.record(s_)
-    drain()
-    fence()
-    calls_on = [len(range(i_, nrep, nstreams)) for i_ in range(nstreams)]
-    span_ms = [ev0[i_].elapsed_time(ev1[i_]) if calls_on[i_] else 0.0 for i_ in range(nstreams)]
-    stream_call_ms = sum(span_ms) / max(sum(calls_on), 1)
+    stream_call_ms = None
+    if args.full:
+        if rank == 0 and args.steps and not do_gather:
+            verification = W.verify_steps(list(range(max(0, args.steps - max(nstreams, 2)), args.steps)))
+        # average device time of one launch on its stream = event span of the stream / its launches (diagnostic,
+        # untimed repeat of the same steps, at most 200 of them)
+        nrep = min(args.steps, 200)
+        ev0 = [torch.cuda.Event(enable_timing=True) for _ in streams]
+        ev1 = [torch.cuda.Event(enable_timing=True) for _ in streams]
+        for e_, s_ in zip(ev0, streams):
+            e_.record(s_)
+        for k in range(nrep):
+            step(k)
+        for e_, s_ in zip(ev1, streams):
+            e_.record(s_)
+        drain()
+        fence()
+        calls_on = [len(range(i_, nrep, nstreams)) for i_ in range(nstreams)]
+        span_ms = [ev0[i_].elapsed_time(ev1[i_]) if calls_on[i_] else 0.0 for i_ in range(nstreams)]
+        stream_call_ms = sum(span_ms) / max(sum(calls_on), 1)
 
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     if world > 1:
@@ -1465,11 +1513,23 @@ def main():
     elapsed = float(t.item())
     # world > 1: BASELINE configs 3 and 4 sharded over the ranks (every rank takes part; reported by rank 0 below)
     rank_cfgs = None
-    if world > 1 and args.workload == "pendulum" and not args.no_configs and not args.f32 and not args.wave:
+    if args.full and world > 1 and args.workload == "pendulum" and not args.no_configs and not args.f32 and not args.wave:
         _phase("multi-rank configs: mass_spring_3in and region discovery, one shard per rank")
         rank_cfgs = multi_rank_configs(torch, lmpc, dist, dev, local_rank, rank, world, n_local)
 
-    if rank == 0:
+    if rank == 0 and not args.full:
+        # the plain run's one line: the headline of the timed region and what it ran on, nothing measured beside it
+        value = world * n_local * args.steps / elapsed if elapsed > 0 else 0.0
+        line = {"metric": metric_name(args.workload), "value": value, "unit": "solves/s", "n_gpus": world,
+                "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / max(args.steps, 1),
+                "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32" if args.f32 else "f64",
+                "data": "synthetic",
+                "config": {"workload": describe(W), "batch_per_gpu": n_local, "kernel": W.kernel,
+                           "batches_in_flight": nstreams, "rotating_batches": W.nrot, "options": dict(W.options)}}
+        if dumped is not None:
+            line["outputs"] = dumped
+        print(json.dumps(line), flush=True)
+    if rank == 0 and args.full:
         total = world * n_local * args.steps
         value = total / elapsed if elapsed > 0 else 0.0
         step_ms = 1e3 * elapsed / max(args.steps, 1)
@@ -1529,8 +1589,7 @@ def main():
                          "frac": ach / VALU_PEAK_TFLOPS[dtype]})
         roof["traffic"], roof["traffic_info"] = traffic_stamp(args.workload)
         out = {
-            "metric": "condensed-MPC QP solves/sec (batch 1e6 params), pendulum Nc=5"
-                      if args.workload == "pendulum" else f"condensed-MPC QP solves/sec ({args.workload})",
+            "metric": metric_name(args.workload),
             "value": value, "unit": "solves/s", "n_gpus": world, "steps": args.steps,
             # `value` = the timed region: `batches_in_flight` independent batches kept in flight (a pipeline figure);
             # next to it the same workload ONE call at a time on one stream (cold HBM), which is what

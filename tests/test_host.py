@@ -425,6 +425,33 @@ def test_bench_helpers_cover_every_workload():
     assert bench.rotation_depth(100, per) == 64           # tiny batches: the cap (everything is cache-resident anyway)
 
 
+def test_bench_dump_outputs_is_exact_and_bounded(tmp_path, monkeypatch):
+    """bench.py --dump-outputs (no GPU: host tensors stand in for the step's buffers): x in its own real type and the
+    exit flags as float32, exactly; a batch over the size limit becomes the same seeded sample of rows every time,
+    with its row numbers, under the limit."""
+    import torch
+    import bench
+    rng = np.random.default_rng(3)
+    x = torch.from_numpy(rng.normal(size=(5000, 2)))
+    ef = torch.from_numpy(rng.integers(-6, 3, 5000).astype(np.int32))
+    assert bench.dump_outputs(str(tmp_path / "a"), x, ef) == ["x.npy", "exitflag.npy"]
+    xa, fa = np.load(tmp_path / "a" / "x.npy"), np.load(tmp_path / "a" / "exitflag.npy")
+    assert xa.dtype == np.float64 and fa.dtype == np.float32
+    assert np.array_equal(xa, x.numpy()) and np.array_equal(fa, ef.numpy())
+    bench.dump_outputs(str(tmp_path / "f"), x.float(), ef)
+    assert np.load(tmp_path / "f" / "x.npy").dtype == np.float32
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 40_000)
+    for d in ("b", "c"):
+        assert bench.dump_outputs(str(tmp_path / d), x, ef) == ["x.npy", "exitflag.npy", "rows.npy"]
+        assert sum(f.stat().st_size for f in (tmp_path / d).iterdir()) <= 40_000
+    rows = np.load(tmp_path / "b" / "rows.npy")
+    assert rows.dtype == np.float64 and np.array_equal(rows, np.load(tmp_path / "c" / "rows.npy"))
+    r = rows.astype(np.int64)
+    assert len(r) > 100 and np.all(np.diff(r) > 0)
+    assert np.array_equal(np.load(tmp_path / "b" / "x.npy"), x.numpy()[r])
+    assert np.array_equal(np.load(tmp_path / "b" / "exitflag.npy"), ef.numpy()[r])
+
+
 def test_bench_line_is_compact_and_strict_json():
     """The driver keeps only a tail of stdout: the bench line must stay a few KB whatever the full report holds
     (round 3's line grew to 37 KB and was not parsed).  Built here from a full report of every configuration with
