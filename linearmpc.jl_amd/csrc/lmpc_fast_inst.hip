@@ -31,15 +31,17 @@ static int launch_fast_t(lmpc_handle *h, int64_t nprob, const double *theta, dou
     // times over, few enough that the grid is a couple of workgroups per CU (one resident round)
     const int nstr = h->fastNstr >= 1 && h->fastNstr <= 4 ? h->fastNstr : 3;
     const long long ntiles = (nprob + 63) / 64;
-    // ONE resident round with the same number of workgroups on every CU (LMPC_FAST_WAVES per CU: four
-    // wavefronts each): with 652 workgroups on 768 slots the CUs that got three were still streaming 5 us
-    // after those that got two had finished (tools/fast_trace.py)
-    long long slots = (long long)h->numCU * LMPC_FAST_WAVES;
+    // ONE resident round with the same number of workgroups on every CU: with 652 workgroups on 768 slots the CUs
+    // that got three were still streaming 5 us after those that got two had finished (tools/fast_trace.py).  The grid
+    // is sized for kFastGridWaves workgroups per CU, not for the LMPC_FAST_WAVES the registers and LDS allow: a call
+    // issued alone on a grid of four per CU took 23.7 us instead of 22.2 on three (same box); four pay off only with
+    // several batches in flight (the in_flight shape sets its tiles itself)
+    long long slots = (long long)h->numCU * kFastGridWaves;
     long long Rl = (ntiles + slots - 1) / slots;
     if (Rl < 8) Rl = 8;
     if (h->fastTiles > 0) Rl = h->fastTiles;
-    // The workgroup's queue holds one index per problem of its R tiles (256 R bytes of LDS next to ~23 KB of fixed
-    // data): R is capped so that three workgroups keep fitting one CU (kFastMaxTiles = 96: 47 KB per workgroup);
+    // The workgroup's queue holds one index per problem of its R tiles (256 R bytes of LDS next to ~13 KB of fixed
+    // data): R is capped so that four workgroups keep fitting one CU (kFastMaxTiles = 96: 38 KB per workgroup);
     // beyond ~6e6 points per call the grid grows past one resident round instead (tests: N = 3e7)
     if (Rl > kFastMaxTiles) Rl = kFastMaxTiles;
     if (Rl > ntiles) Rl = ntiles > 0 ? ntiles : 1;
@@ -56,7 +58,8 @@ static int launch_fast_t(lmpc_handle *h, int64_t nprob, const double *theta, dou
     // streaming wavefronts take their records by LDS-DMA into a ring of dk tile slots each ("fast_dma": 0 = through
     // registers, 2 / 3 = ring depth; default LMPC_FAST_DMA_DEPTH); the generated controller's gather stays on registers
     // (default: a ring of two tiles with three streaming wavefronts; with four of them -- the shape for several batches
-    // in flight -- the rings would cost the third workgroup per CU its LDS: registers there)
+    // in flight -- the rings would cost the fourth and third workgroup per CU their LDS: registers there, measured
+    // 14.7 us/step for three 1e6 batches in flight against 15.3 with three streamers on rings of two)
     int dk = GATHER ? 0 : (h->fastDma >= 0 ? h->fastDma : (nstr <= 3 ? LMPC_FAST_DMA_DEPTH : 0));
     if (dk == 1 || dk > 3) dk = dk == 1 ? 0 : 3;
     if (nprob * (int64_t)NT * 8 < 16) dk = 0;
@@ -115,7 +118,7 @@ static int launch_fast_multi_t(lmpc_handle *h, int nb, int64_t nprob, const doub
                                int32_t *const *flag, hipStream_t st) {
     const int nstr = h->fastNstr >= 1 && h->fastNstr <= 4 ? h->fastNstr : 3;
     const long long ntiles = (nprob + 63) / 64;
-    long long slots = (long long)h->numCU * LMPC_FAST_WAVES;
+    long long slots = (long long)h->numCU * kFastGridWaves;
     long long Rl = (ntiles + slots - 1) / slots;
     if (Rl < 8) Rl = 8;
     if (h->fastTiles > 0) Rl = h->fastTiles;

@@ -12,7 +12,7 @@
 //     indices of the others into the workgroup's queue in LDS (reserve with one LDS atomic per tile, write);
 //   * the remaining wavefronts -- and every streaming wavefront once its tiles are done -- claim 64 queued
 //     problems at a time (compare-and-swap on the read index) and solve them one per lane: the straight-line
-//     tiers of lmpc_tiers.hpp first, the generic loop of lane_kernel (lane_loop, same LDS layout) for the lanes
+//     tiers of lmpc_tiers.hpp first, the generic loop of lane_kernel (lane_loop, out of line: fast_fallback) for the lanes
 //     the tiers do not finish, so the kernel is complete by itself and no second launch follows.
 //
 // Synchronisation is workgroup-local and one-directional: producers never wait (the queue holds every problem
@@ -36,8 +36,9 @@
 namespace lmpc {
 
 #ifndef LMPC_FAST_WAVES
-#define LMPC_FAST_WAVES 3      // wavefronts per SIMD the kernel is register-budgeted for (lane_loop sets the need)
+#define LMPC_FAST_WAVES 4      // wavefronts per SIMD the kernel is register-budgeted for (128 VGPRs; see fast_fallback)
 #endif
+constexpr int kFastGridWaves = 3;         // workgroups per CU the default grid is sized for (launch_fast_t)
 constexpr int kFastSpinLimit = 1 << 22;
 constexpr int kFastCtrs = 16;              // ticket counters of the dynamic tail (a power of two)
 constexpr int kFastMaxTiles = 96;          // tiles of 64 problems per workgroup at most (LDS queue: 256 bytes per tile)
@@ -83,13 +84,57 @@ __host__ __device__ constexpr int fast_scr_doubles(int N, int NTHMAX) { return (
 #endif
 constexpr int kFastPay = LMPC_FAST_PAY;
 __host__ __device__ constexpr size_t fast_lds_bytes(int N, int R, int NTHMAX) {
-    return sizeof(double) * (size_t)(((N * N + N * (N + 1) / 2 + 2 * N + 1) & ~1) + 4 * N * 64 + fast_scr_doubles(N, NTHMAX) +
+    return sizeof(double) * (size_t)(((N * N + N * (N + 1) / 2 + 2 * N + 1) & ~1) + fast_scr_doubles(N, NTHMAX) +
                                      (size_t)kFastPay * (N + 1)) +
            sizeof(int32_t) * ((size_t)R * 64 + 4);
 }
 // ... plus the streaming wavefronts' LDS-DMA rings behind it (dk slots of one tile per streaming wavefront)
 __host__ __device__ constexpr size_t fast_lds_bytes_dma(int N, int R, int NTHMAX, int NT, int nstr, int dk) {
     return fast_lds_bytes(N, R, NTHMAX) + (size_t)dk * nstr * fast_tile_bytes(NT);
+}
+
+// The generic loop of lane_kernel (lane_loop) for a lane the straight-line tiers did not finish -- about one problem
+// in 10^6 of an iterating batch -- as a function of its own.  Inlined, its working set (LaneState<N, N>: ~60 registers
+// for N = 5) set the register budget of the whole kernel and its b[j][lane] columns took 4 N 64 doubles of every
+// workgroup's LDS; out of line the kernel is budgeted for the stream, the screen and the tiers, and the call's
+// registers are saved around it on the (rare) lanes that take it.  b goes to lane_loop through this frame's private
+// copy (stride 1); the constants are the workgroup's LDS copies, as in lane_kernel.  Same loop, same values: the
+// results do not change by a bit.
+template <int N> struct FastShifts { double b[N]; };
+template <int N> struct FastFallback { double u[N]; unsigned long long act, low; int flag, iter; };
+// (the pack fields lane_loop reads, by value: a reference to the kernel's PackLayout argument would make the kernel
+// copy all of it to its stack at entry)
+struct FastLoopArgs {
+    unsigned long long imm_mask, eq_mask;
+    double primal_tol, dual_tol, zero_tol, progress_tol, fval_bound;
+    int n, m, words, oM, odu, odl, cycle_tol, iter_limit;
+};
+__device__ __forceinline__ FastLoopArgs fast_loop_args(const PackLayout &P) {
+    return FastLoopArgs{P.imm_mask, P.eq_mask, P.primal_tol, P.dual_tol, P.zero_tol, P.progress_tol, P.fval_bound,
+                        P.n, P.m, P.words, P.oM, P.odu, P.odl, P.cycle_tol, P.iter_limit};
+}
+template <int N>
+__device__ __attribute__((noinline)) FastFallback<N> fast_fallback(const FastLoopArgs A, const double *__restrict__ C,
+                                                                    const FastShifts<N> sh, const long long pid) {
+    PackLayout P{};
+    P.imm_mask = A.imm_mask; P.eq_mask = A.eq_mask;
+    P.primal_tol = A.primal_tol; P.dual_tol = A.dual_tol; P.zero_tol = A.zero_tol; P.progress_tol = A.progress_tol;
+    P.fval_bound = A.fval_bound;
+    P.n = A.n; P.m = A.m; P.words = A.words; P.oM = A.oM; P.odu = A.odu; P.odl = A.odl;
+    P.cycle_tol = A.cycle_tol; P.iter_limit = A.iter_limit;
+    extern __shared__ __align__(16) double lds[];             // (fast_body's layout: M, G, du0, dl0 first)
+    const double *sM = lds, *sG = sM + N * N, *sdu = sG + N * (N + 1) / 2, *sdl = sdu + N;
+    double sB[N];
+#pragma unroll
+    for (int j = 0; j < N; j++) sB[j] = sh.b[j];
+    LaneState<N, N> s;
+    s.init();
+    lane_loop<N, N, N, false>(P, C, sM, sG, sdu, sdl, sB, 1, 0, pid, nullptr, s);
+    FastFallback<N> r;
+#pragma unroll
+    for (int c = 0; c < N; c++) r.u[c] = s.u[c];
+    r.act = s.act; r.low = s.low; r.flag = s.flag; r.iter = s.iter;
+    return r;
 }
 
 // GATHER: the generated controller's call (lmpc_compute_control*): theta is assembled from the five argument arrays
@@ -109,8 +154,7 @@ __device__ __forceinline__ void fast_body(
     constexpr int nconst = N * N + N * (N + 1) / 2 + 2 * N;
     extern __shared__ __align__(16) double lds[];
     double *sconst = lds;                                      // M, G, du0, dl0 (as in the pack, as lane_kernel keeps them)
-    double *sBall = sconst + ((nconst + 1) & ~1);              // b[j][lane] of the four wavefronts (generic loop)
-    double *sScr = sBall + 4 * N * 64;                          // screening constants (see fast_scr_doubles)
+    double *sScr = sconst + ((nconst + 1) & ~1);               // screening constants (see fast_scr_doubles)
     double *sPay = sScr + fast_scr_doubles(N, NTHMAX);         // (b_0 .. b_{N-1}, x shift) of the first kFastPay queue positions
     int32_t *ring = reinterpret_cast<int32_t *>(sPay + (size_t)kFastPay * (N + 1));
     int *ctrl = reinterpret_cast<int *>(ring + R * 64);        // [0] write index, [1] read index, [2] producers done
@@ -126,7 +170,6 @@ __device__ __forceinline__ void fast_body(
     if (tid < 4) ctrl[tid] = 0;
     __syncthreads();
     const double *sM = sconst, *sG = sM + N * N, *sdu = sG + N * (N + 1) / 2, *sdl = sdu + N;
-    double *sB = sBall + wv * N * 64;
     const double ntol = -P.primal_tol;
     const long long ntiles = (nprob + 63) / 64;
 #ifdef LMPC_FAST_TRACE      // diagnostic build: 100 MHz timestamps per wavefront into errflag[16 + 8 * wave ..]
@@ -197,10 +240,10 @@ __device__ __forceinline__ void fast_body(
         // A streaming wavefront asks for ONE tile, waits, screens it, asks for the next (kFastAhead = 1).  Measured on
         // the headline batch with no point needing iterations (tools/stream_floor.py; one call, cold HBM, event-timed):
         // this form 20.3 us; the next tile requested before the current one is screened (two register sets used
-        // alternately, LMPC_FAST_PP) 21.2 us; two / four / seven tiles requested back to back before the first is
+        // alternately; removed) 21.2 us; two / four / seven tiles requested back to back before the first is
         // consumed (straight-line code, so that the compiler's waits are vmcnt(4 (T - 1 - d)) instead of the vmcnt(0)
         // it puts at the head of every loop with stores behind it: loads and stores share one in-order counter)
-        // 22.6 / 22.6 / 26.3 us; each wavefront on a contiguous run of tiles (LMPC_FAST_CONTIG) the same.  More
+        // 22.6 / 22.6 / 26.3 us; each wavefront on a contiguous run of tiles (removed) the same.  More
         // requests in flight per wavefront make THIS access shape slower, not faster: a record is 56 bytes per lane,
         // the four load instructions of a tile touch the same 28 lines one after the other and rely on the 32 KB L1
         // to merge them -- nine streaming wavefronts with one tile each are 31.5 KB.  (Read in address order through a
@@ -303,42 +346,6 @@ __device__ __forceinline__ void fast_body(
                 if (active) active[pid * P.words] = 0ull;
             }
         };
-#ifdef LMPC_FAST_CONTIG     // each streaming wavefront takes a contiguous run of the workgroup's tiles
-        const long long per = (R + nstr - 1) / nstr;
-        const long long s0 = t0 + role * per, s1 = s0 + per < t1 ? s0 + per : t1;
-        for (long long base = s0; base < s1; base += kFastAhead) {
-#pragma unroll
-            for (int d = 0; d < kFastAhead; d++) {
-                const long long tl = base + d;
-                load_record((tl < s1 ? tl : base) * 64 + lane, buf[d]);
-            }
-#pragma unroll
-            for (int d = 0; d < kFastAhead; d++) {
-                const long long tl = base + d;
-                process(tl < s1 ? tl : base, buf[d], tl < s1);
-            }
-        }
-#elif defined(LMPC_FAST_PP)    // two register sets used alternately, the next tile requested before the current one is consumed
-        {
-            double bufB[NT];
-            long long tile = t0 + role;
-            if (tile < t1) {
-                load_record(tile * 64 + lane, buf[0]);
-                for (;;) {
-                    long long nxt = tile + nstr < t1 ? tile + nstr : tile;
-                    load_record(nxt * 64 + lane, bufB);
-                    process(tile, buf[0], true);
-                    if (tile + nstr >= t1) break;
-                    tile += nstr;
-                    nxt = tile + nstr < t1 ? tile + nstr : tile;
-                    load_record(nxt * 64 + lane, buf[0]);
-                    process(tile, bufB, true);
-                    if (tile + nstr >= t1) break;
-                    tile += nstr;
-                }
-            }
-        }
-#else
         if (!GATHER && dk >= 2) {
             // Records by LDS-DMA (round 3).  The wavefront owns a ring of dk tile slots in LDS; a tile (64 records,
             // 64 NT 8 bytes, contiguous in theta) is moved by ceil(bytes / 1 KiB) wave-instructions of 16 bytes per
@@ -466,7 +473,6 @@ __device__ __forceinline__ void fast_body(
                 process(tl < t1 ? tl : base, buf[d], tl < t1);
             }
         }
-#endif
         if (dyn && !(!GATHER && dk >= 2)) {
             // dynamic tail (register path): one tile per ticket, the next ticket in flight while this tile is screened
             int cc = (int)((blockIdx.x * (unsigned)nstr + (unsigned)role) & (kFastCtrs - 1));
@@ -591,15 +597,14 @@ __device__ __forceinline__ void fast_body(
         }
 #ifndef LMPC_FAST_NO_FALLBACK      // (diagnostic build without it: what the tiers and the stream need on their own)
         if (mine && !solved) {
-            // the generic loop of lane_kernel on the lanes the tiers did not finish (from scratch)
+            // the generic loop of lane_kernel on the lanes the tiers did not finish (from scratch), out of line
+            FastShifts<N> bs;
 #pragma unroll
-            for (int j = 0; j < N; j++) sB[j * 64 + lane] = b[j];
-            LaneState<N, N> s;
-            s.init();
-            lane_loop<N, N, N, false>(P, C, sM, sG, sdu, sdl, sB, 64, lane, pid, nullptr, s);
+            for (int j = 0; j < N; j++) bs.b[j] = b[j];
+            const FastFallback<N> r = fast_fallback<N>(fast_loop_args(P), C, bs, pid);
 #pragma unroll
-            for (int c = 0; c < N; c++) u[c] = s.u[c];
-            flag = s.flag; iter = s.iter; act = s.act; low = s.low;
+            for (int c = 0; c < N; c++) u[c] = r.u[c];
+            flag = r.flag; iter = r.iter; act = r.act; low = r.low;
         }
 #endif
         if (mine) {
