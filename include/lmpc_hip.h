@@ -623,6 +623,97 @@ const char *lmpc_last_error(const lmpc_handle *h);
 /* Library/ABI version, bumped on any signature change. */
 int lmpc_abi_version(void);
 
+/*
+ * Explicit MPC: a piecewise-affine controller built from a solved training sample and evaluated on the GPU -- the
+ * counterpart of the reference's ExplicitMPC + build_tree! + compute_control(empc, x) (src/explicit.jl:23-76,
+ * src/utils.jl:53-60), with the regions taken from the sample instead of an exact enumeration.
+ *
+ * Build (host only, no GPU touched): the distinct optimal active sets of the sample's points with exit flag >= 1 are
+ * the regions, most frequent first.  For each, in the handle's LDP form (the pack lmpc_get_ldp returns), the working
+ * set A gives the multipliers lambda_A(theta) = -(M_A M_A' + rho_soft S_A)^-1 (d_A0 + Dth_A theta) (S_A: 1 on SOFT
+ * rows), u = -M_A' lambda, outputs x = Rout u + x0 + Xth theta.  Stored per region: the output law, the law of the
+ * active SOFT rows' multipliers (their slack rho * sum lambda^2 against primal_tol decides exit flag 2 vs 1), and the
+ * halfspaces a . theta <= b: both finite bounds of every inactive non-IMMUTABLE row, the dual sign of every active
+ * non-IMMUTABLE row (upper >= 0, lower <= 0), optionally the box lb <= theta <= ub.  Rows with a zero theta part that
+ * always hold are dropped; nothing else is (no LP redundancy removal).  A singular reduced system (pivot < zero_tol)
+ * drops the region.  A point-location tree is grown on the labelled sample (splits: halfspace rows of the most frequent
+ * regions at a node, scored by the larger child candidate set); the tree is approximate, the leaf check is exact.
+ * The sample certifies nothing: regions it did not hit, or dropped for capacity, are not in the table, and their
+ * points go to the implicit solve.  Refused with LMPC_ERR_UNSUPPORTED: BINARY rows, is_avi handles, proximal-point
+ * handles, nth > LMPC_EXPLICIT_MAX_NTH.  Binary64 only.
+ *
+ * Evaluation: one point per lane -- tree walk, the leaf's candidates in frequency order, the law with explicit fmas.
+ * A point is UNLOCATED (region -1) when no candidate holds it, or when its soft slack lies within soft_band *
+ * primal_tol of primal_tol.  lmpc_explicit_eval_device then solves the unlocated points with the handle's own
+ * implicit path (lmpc_solve_batch_device) on the same stream and writes their x / exitflag at their indices: it
+ * SYNCHRONISES `stream` once to read how many there are (one 4-byte copy), then enqueues a gather, the solve and a
+ * scatter, and returns without waiting for those.  Infeasible points always end there.  The same answers as
+ * lmpc_solve_batch_device wherever the located region is the solver's final active set (up to rounding), within the
+ * solver's own primal_tol band elsewhere; fallback points are the implicit results bit for bit.
+ */
+#define LMPC_EXPLICIT_MAX_NTH 32
+#define LMPC_EXPLICIT_INFO 12
+typedef struct lmpc_explicit lmpc_explicit;
+typedef struct lmpc_explicit_opts {
+    int32_t max_regions;     /* 4096: regions kept, most frequent first */
+    int32_t leaf_size;       /* 8: a node with this many candidate regions or fewer is a leaf */
+    int32_t max_depth;       /* 24: 0 = one leaf, a frequency-ordered scan of every region */
+    int32_t split_regions;   /* 4: a node tries the halfspace rows of its this many most frequent regions as splits */
+    int32_t split_rows;      /* 96: ... at most this many rows */
+    int32_t score_points;    /* 65536: training points a node scores its candidate splits on (evenly strided subset) */
+    int64_t max_bytes;       /* 256 MiB: cap on the region table (region records, halfspace rows, laws, soft rows; the
+                              * tree's nodes and leaf lists come on top); regions beyond it are dropped like those beyond
+                              * max_regions */
+    double soft_band;        /* 0.1: relative band around primal_tol in which the soft slack leaves a point unlocated */
+    const double *box_lb;    /* NULL, or nth lower bounds of theta: adds lb <= theta <= ub to every region */
+    const double *box_ub;
+} lmpc_explicit_opts;
+void lmpc_explicit_default_opts(lmpc_explicit_opts *o);
+
+/* Host-only build from an LDP pack (row-major, as lmpc_setup_ldp takes it) and its settings (NULL = defaults), no
+ * GPU.  theta: N records of nth doubles (not read when nth == 0); active: N records of (2m + 63) / 64 words (the
+ * solver's masks); exitflag: N int32.  is_avi != 0 states that the pack is a variational problem's (refused).
+ * *out is NULL on failure; lmpc_last_error(NULL) has the text.  Such a controller can be inspected and evaluated
+ * on the host (lmpc_explicit_locate_host), not on a GPU. */
+int lmpc_explicit_build_ldp(lmpc_explicit **out, int n, int m, int ms, int nth, int nout,
+                            const double *M, const double *du, const double *dl, const double *Dth,
+                            const double *Rout, const double *x0, const double *Xth, const int32_t *sense,
+                            const lmpc_settings *s, int is_avi, int64_t N, const double *theta,
+                            const uint64_t *active, const int32_t *exitflag, const lmpc_explicit_opts *opts);
+/* The same build from the handle's own pack and settings (HOST arrays), then one upload of the table to the
+ * handle's GPU.  The controller keeps using `h` for its fallback: free it before the handle. */
+int lmpc_explicit_build(lmpc_explicit **out, lmpc_handle *h, int64_t N, const double *theta, const uint64_t *active,
+                        const int32_t *exitflag, const lmpc_explicit_opts *opts);
+/* out[LMPC_EXPLICIT_INFO]: regions kept, dropped for capacity (max_regions / max_bytes), dropped as singular,
+ * halfspace rows in total, tree nodes, tree depth, leaves, largest leaf, table bytes, training points in kept
+ * regions, distinct optimal active sets in the sample, SOFT multiplier rows in total. */
+int lmpc_explicit_info(const lmpc_explicit *e, int64_t *out);
+/* Region r: output law F[nout*nth] (row-major) and g[nout]; halfspaces A[rows*nth], b[rows]; its mask[words] and
+ * training count.  *nrows = the region's halfspace rows (call with A == NULL first to size A, b); any output may be
+ * NULL. */
+int lmpc_explicit_region(const lmpc_explicit *e, int32_t r, double *F, double *g, double *A, double *b,
+                         int32_t *nrows, uint64_t *mask, int64_t *count);
+/* The serialised table (layout: csrc/lmpc_explicit_kernel.hpp); *bytes = its size, out == NULL: size only. */
+int lmpc_explicit_blob(const lmpc_explicit *e, void *out, int64_t *bytes);
+/* Per training point: its region (-1: failed, or in a dropped region) and the tree leaf (node index) the build
+ * sent it to (-1 if unlabelled).  Either may be NULL. */
+int lmpc_explicit_training(const lmpc_explicit *e, int32_t *label, int32_t *leaf);
+/* The kernel's evaluation on the host, same arithmetic: region[N] (-1 unlocated), and where located x[N*nout] and
+ * exitflag[N] (unlocated points: exitflag 0, x left as it is); rows_checked[N] = tree nodes + halfspace rows
+ * evaluated.  Any output but region may be NULL.  No fallback. */
+int lmpc_explicit_locate_host(const lmpc_explicit *e, int64_t N, const double *theta, double *x, int32_t *exitflag,
+                              int32_t *region, int32_t *rows_checked);
+/* DEVICE pointers on the handle's GPU (see above for the one synchronisation); region may be NULL.  The fallback's
+ * gather / solve / scatter are still enqueued when the call returns and use the controller's own scratch, and the
+ * implicit solve uses the handle's: one controller serves one stream at a time, and a call on another stream (or the
+ * handle's other entry points) must wait until that stream has finished the previous call. */
+int lmpc_explicit_eval_device(lmpc_explicit *e, int64_t N, const double *theta, double *x, int32_t *exitflag,
+                              int32_t *region, void *stream);
+/* HOST pointers; synchronous. */
+int lmpc_explicit_eval(lmpc_explicit *e, int64_t N, const double *theta, double *x, int32_t *exitflag, int32_t *region);
+const char *lmpc_explicit_last_error(const lmpc_explicit *e);
+void lmpc_explicit_free(lmpc_explicit *e);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,9 @@ SYMBOLS = (
     "lmpc_pin_host", "lmpc_unpin_host", "lmpc_release_scratch", "lmpc_check",
     "lmpc_distinct_active_sets_device", "lmpc_distinct_active_sets_overflowed", "lmpc_wave_stats",
     "lmpc_setup_ex", "lmpc_is_avi", "lmpc_get_avi", "lmpc_transform_avi", "lmpc_multi_set_option", "lmpc_discover_regions_device", "lmpc_reserve", "lmpc_get_prox",
+    "lmpc_explicit_default_opts", "lmpc_explicit_build_ldp", "lmpc_explicit_build", "lmpc_explicit_info",
+    "lmpc_explicit_region", "lmpc_explicit_blob", "lmpc_explicit_training", "lmpc_explicit_locate_host",
+    "lmpc_explicit_eval_device", "lmpc_explicit_eval", "lmpc_explicit_last_error", "lmpc_explicit_free",
 )
 
 

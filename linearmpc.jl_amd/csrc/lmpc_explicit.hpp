@@ -1,0 +1,34 @@
+// Explicit MPC controller object (include/lmpc_hip.h, "Explicit MPC"): the host tables written by the builder
+// (lmpc_explicit.cpp) and the device copy and fallback scratch kept by lmpc_explicit.hip.
+#pragma once
+
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/lmpc_hip.h"
+
+struct lmpc_explicit {
+    int n = 0, m = 0, ms = 0, nth = 0, nout = 0, words = 0;
+    double primal_tol = 1e-6, rho_soft = 1e-6, band = 1e-3;
+    std::vector<uint64_t> blob;                 // the serialised table (lmpc_explicit_kernel.hpp), 8-byte words
+    std::vector<uint64_t> masks;                // kept regions' masks, `words` each
+    std::vector<int64_t> counts;                // ... and their training counts
+    std::vector<int32_t> label, leaf;           // per training point: region, tree leaf
+    int64_t info[LMPC_EXPLICIT_INFO] = {};
+    std::string err;
+    // device side: the handle whose GPU holds the table and whose implicit path takes the unlocated points
+    lmpc_handle *h = nullptr;
+    int device = -1;
+    void *dBlob = nullptr;
+    int32_t *dList = nullptr, *dCount = nullptr, *dFlag = nullptr, *hCount = nullptr;
+    double *dTheta = nullptr, *dX = nullptr;
+    int64_t cap = 0;
+};
+
+namespace lmpc {
+int explicit_build_pack(lmpc_explicit *e, int n, int m, int ms, int nth, int nout, const double *M, const double *du,
+                        const double *dl, const double *Dth, const double *Rout, const double *x0, const double *Xth,
+                        const int32_t *sense, const lmpc_settings &s, int is_avi, int64_t N, const double *theta,
+                        const uint64_t *active, const int32_t *exitflag, const lmpc_explicit_opts &o);
+}  // namespace lmpc

@@ -311,3 +311,275 @@ def certify_sampled(solve_fn, theta, group=None):
                 flags[k] = flags.get(k, 0) + v
     return {"max_iterations": max_it, "argmax_theta": arg, "iterations_hist": np.asarray(hist),
             "cells": cells, "n_cells": int(len(cells)), "exitflags": flags}
+
+
+# ---------------------------------------------------------------- explicit controller (include/lmpc_hip.h, "Explicit MPC")
+def _explicit_opts_type():
+    import ctypes
+    c = ctypes
+
+    class ExplicitOpts(c.Structure):
+        """`lmpc_explicit_opts`."""
+        _fields_ = [("max_regions", c.c_int32), ("leaf_size", c.c_int32), ("max_depth", c.c_int32),
+                    ("split_regions", c.c_int32), ("split_rows", c.c_int32), ("score_points", c.c_int32),
+                    ("max_bytes", c.c_int64), ("soft_band", c.c_double), ("box_lb", c.c_void_p), ("box_ub", c.c_void_p)]
+    return ExplicitOpts
+
+
+_OPTS = None
+
+
+def _bind():
+    """argtypes of the explicit-controller entry points (bound once, on first use)."""
+    import ctypes
+    from ._cabi import lib
+    global _OPTS
+    L = lib()
+    if _OPTS is None:
+        _OPTS = _explicit_opts_type()
+        vp, i32, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
+        L.lmpc_explicit_default_opts.argtypes = [vp]
+        L.lmpc_explicit_default_opts.restype = None
+        L.lmpc_explicit_build_ldp.argtypes = [ctypes.POINTER(vp)] + [i32] * 5 + [vp] * 9 + [i32, i64, vp, vp, vp, vp]
+        L.lmpc_explicit_build.argtypes = [ctypes.POINTER(vp), vp, i64, vp, vp, vp, vp]
+        L.lmpc_explicit_info.argtypes = [vp, vp]
+        L.lmpc_explicit_region.argtypes = [vp, ctypes.c_int32] + [vp] * 7
+        L.lmpc_explicit_blob.argtypes = [vp, vp, vp]
+        L.lmpc_explicit_training.argtypes = [vp, vp, vp]
+        L.lmpc_explicit_locate_host.argtypes = [vp, i64] + [vp] * 5
+        L.lmpc_explicit_eval_device.argtypes = [vp, i64] + [vp] * 5
+        L.lmpc_explicit_eval.argtypes = [vp, i64] + [vp] * 4
+        for f in ("build_ldp", "build", "info", "region", "blob", "training", "locate_host", "eval_device", "eval"):
+            getattr(L, "lmpc_explicit_" + f).restype = i32
+        L.lmpc_explicit_last_error.argtypes = [vp]
+        L.lmpc_explicit_last_error.restype = ctypes.c_char_p
+        L.lmpc_explicit_free.argtypes = [vp]
+        L.lmpc_explicit_free.restype = None
+    return L
+
+
+INFO_KEYS = ("regions", "dropped_capacity", "dropped_singular", "rows", "nodes", "depth", "leaves", "largest_leaf",
+             "bytes", "labelled", "distinct_sets", "soft_rows")
+
+
+class ExplicitController:
+    """A piecewise-affine controller built from a solved training sample (the reference's ExplicitMPC + build_tree!,
+    src/explicit.jl:23-76, with the regions taken from the sample): `evaluate_device` locates every point in a region
+    on the GPU and evaluates its affine law, and sends the points no kept region holds to the handle's implicit solve.
+    Options (keyword arguments): max_regions, leaf_size, max_depth, split_regions, split_rows, score_points, max_bytes,
+    soft_band, box=(lb, ub) -- see lmpc_explicit_opts."""
+
+    def __init__(self, ptr, qp=None, words=None):
+        self._e = ptr
+        self.qp = qp
+        head = self.blob()[:128].view(np.int64)
+        self.nth, self.nout, self.nregions = int(head[0]), int(head[1]), int(head[2])
+        self.words = qp.words if qp is not None else int(words)
+
+    @staticmethod
+    def _opts(nth, **kw):
+        import ctypes
+        L = _bind()
+        o = _OPTS()
+        L.lmpc_explicit_default_opts(ctypes.byref(o))
+        keep = []
+        box = kw.pop("box", None)
+        for k, v in kw.items():
+            if not hasattr(o, k):
+                raise KeyError(f"unknown explicit-controller option {k}")
+            setattr(o, k, type(getattr(o, k))(v))
+        if box is not None:
+            lb = np.ascontiguousarray(np.asarray(box[0], float).reshape(nth))
+            ub = np.ascontiguousarray(np.asarray(box[1], float).reshape(nth))
+            keep += [lb, ub]
+            o.box_lb, o.box_ub = lb.ctypes.data, ub.ctypes.data
+        return o, keep
+
+    @staticmethod
+    def _sample(theta, active, exitflag, nth):
+        th = np.ascontiguousarray(np.asarray(theta, np.float64).reshape(-1, nth) if nth else np.zeros((len(exitflag), 0)))
+        act = np.ascontiguousarray(np.asarray(active).view(np.uint64) if np.asarray(active).dtype == np.int64
+                                   else np.asarray(active, np.uint64))
+        ef = np.ascontiguousarray(np.asarray(exitflag, np.int32).reshape(-1))
+        if th.shape[0] != ef.shape[0] or act.shape[0] != ef.shape[0]:
+            raise ValueError("theta, active and exitflag must describe the same N points")
+        return th, act, ef
+
+    @classmethod
+    def build(cls, qp, theta, active, exitflag, **opts):
+        """Host arrays (or CPU-copyable tensors) of a solved sample -> a controller on qp's GPU (lmpc_explicit_build)."""
+        import ctypes
+        from ._cabi import LmpcError
+        L = _bind()
+        theta, active, exitflag = (t.cpu().numpy() if hasattr(t, "cpu") else t for t in (theta, active, exitflag))
+        th, act, ef = cls._sample(theta, active, exitflag, qp.nth)
+        o, keep = cls._opts(qp.nth, **opts)
+        e = ctypes.c_void_p()
+        vp = ctypes.c_void_p
+        rc = L.lmpc_explicit_build(ctypes.byref(e), qp._h, len(ef), vp(th.ctypes.data) if th.size else None,
+                                   vp(act.ctypes.data) if act.size else None, vp(ef.ctypes.data) if ef.size else None,
+                                   ctypes.byref(o))
+        if rc != 1:
+            raise LmpcError(rc, (L.lmpc_explicit_last_error(None) or b"").decode())
+        return cls(e, qp)
+
+    @classmethod
+    def build_ldp(cls, pack, theta, active, exitflag, settings=None, is_avi=False, **opts):
+        """Host-only build (no GPU) from an LDP pack: a dict with row-major M, du, dl, Dth, Rout, x0, Xth, sense (and
+        ms), as BatchedQP.ldp() returns it (lmpc_explicit_build_ldp).  Inspect it and evaluate it with locate_host."""
+        import ctypes
+        from ._cabi import LmpcError
+        L = _bind()
+        M = np.ascontiguousarray(np.asarray(pack["M"], float))
+        m, n = M.shape
+        Rout = np.ascontiguousarray(np.asarray(pack["Rout"], float).reshape(-1, n))
+        nout = Rout.shape[0]
+        Xth = np.ascontiguousarray(np.asarray(pack["Xth"], float).reshape(nout, -1))
+        nth = Xth.shape[1]
+        Dth = np.ascontiguousarray(np.asarray(pack["Dth"], float).reshape(m, nth))
+        du, dl, x0 = (np.ascontiguousarray(np.asarray(pack[k], float).reshape(-1)) for k in ("du", "dl", "x0"))
+        sense = np.ascontiguousarray(np.asarray(pack["sense"], np.int32).reshape(m))
+        th, act, ef = cls._sample(theta, active, exitflag, nth)
+        o, keep = cls._opts(nth, **opts)
+        e = ctypes.c_void_p()
+        p = lambda a: ctypes.c_void_p(a.ctypes.data) if a.size else None
+        rc = L.lmpc_explicit_build_ldp(ctypes.byref(e), n, m, int(pack.get("ms", 0)), nth, nout, p(M), p(du), p(dl),
+                                       p(Dth), p(Rout), p(x0), p(Xth), p(sense),
+                                       ctypes.cast(ctypes.pointer(settings), ctypes.c_void_p) if settings is not None else None,
+                                       int(bool(is_avi)), len(ef), p(th), p(act), p(ef), ctypes.byref(o))
+        if rc != 1:
+            raise LmpcError(rc, (L.lmpc_explicit_last_error(None) or b"").decode())
+        return cls(e, None, words=(2 * m + 63) // 64)
+
+    @classmethod
+    def from_sample(cls, qp, theta, **opts):
+        """Solve the sample (a float64 CUDA tensor, or host array) with qp.solve_device, masks kept, then build."""
+        import torch
+        if not torch.is_tensor(theta):
+            theta = torch.from_numpy(np.ascontiguousarray(np.asarray(theta, np.float64))).to(f"cuda:{qp.device}")
+        N = theta.shape[0]
+        act = torch.zeros((N, qp.words), dtype=torch.int64, device=theta.device)
+        x, ef = qp.solve_device(theta, active=act)
+        torch.cuda.synchronize(theta.device)
+        return cls.build(qp, theta.cpu().numpy(), act.cpu().numpy().view(np.uint64), ef.cpu().numpy(), **opts)
+
+    @classmethod
+    def from_range(cls, qp, lb, ub, nsamples, seed=0, extra_theta=None, **opts):
+        """ExplicitMPC(mpc; range): a uniform sample of the box [lb, ub] drawn on the device (seeded), `extra_theta`
+        rows appended, solved with masks and built into a controller."""
+        import torch
+        dev = torch.device("cuda", qp.device)
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(int(seed))
+        lo = torch.as_tensor(np.asarray(lb, float).reshape(-1), dtype=torch.float64, device=dev)
+        hi = torch.as_tensor(np.asarray(ub, float).reshape(-1), dtype=torch.float64, device=dev)
+        theta = lo + (hi - lo) * torch.rand((int(nsamples), lo.numel()), dtype=torch.float64, device=dev, generator=gen)
+        if extra_theta is not None:
+            ex = torch.as_tensor(np.asarray(extra_theta, float).reshape(-1, lo.numel()), dtype=torch.float64, device=dev)
+            theta = torch.cat([theta, ex]).contiguous()
+        return cls.from_sample(qp, theta, **opts)
+
+    # ---------------------------------------------------------------- inspection
+    def info(self):
+        import ctypes
+        out = np.zeros(len(INFO_KEYS), np.int64)
+        self._check(_bind().lmpc_explicit_info(self._e, ctypes.c_void_p(out.ctypes.data)))
+        return {k: int(v) for k, v in zip(INFO_KEYS, out)}
+
+    def region(self, r):
+        """Region r: dict(F (nout x nth), g, A (rows x nth), b, mask, count): x = F theta + g where A theta <= b."""
+        import ctypes
+        L = _bind()
+        vp = lambda a: ctypes.c_void_p(a.ctypes.data) if a.size else None
+        nr, cnt = ctypes.c_int32(), ctypes.c_int64()
+        self._check(L.lmpc_explicit_region(self._e, int(r), None, None, None, None, ctypes.byref(nr), None, None))
+        F, g = np.zeros((self.nout, self.nth)), np.zeros(self.nout)
+        A, b = np.zeros((nr.value, self.nth)), np.zeros(nr.value)
+        mask = np.zeros(self.words, np.uint64)
+        self._check(L.lmpc_explicit_region(self._e, int(r), vp(F), vp(g), vp(A), vp(b), ctypes.byref(nr), vp(mask),
+                                           ctypes.byref(cnt)))
+        return {"F": F, "g": g, "A": A, "b": b, "mask": mask, "count": int(cnt.value)}
+
+    def blob(self):
+        """The serialised table as bytes (uint8 array; layout in csrc/lmpc_explicit_kernel.hpp)."""
+        import ctypes
+        L = _bind()
+        nb = ctypes.c_int64()
+        self._check(L.lmpc_explicit_blob(self._e, None, ctypes.byref(nb)))
+        out = np.zeros(nb.value, np.uint8)
+        self._check(L.lmpc_explicit_blob(self._e, ctypes.c_void_p(out.ctypes.data), ctypes.byref(nb)))
+        return out
+
+    def training(self, n):
+        """(label, leaf) of the n training points the controller was built from."""
+        import ctypes
+        lab, leaf = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        self._check(_bind().lmpc_explicit_training(self._e, ctypes.c_void_p(lab.ctypes.data), ctypes.c_void_p(leaf.ctypes.data)))
+        return lab, leaf
+
+    # ---------------------------------------------------------------- evaluation
+    def locate_host(self, theta):
+        """The kernel's arithmetic on the host, no fallback: (x, exitflag, region, rows_checked); region -1 =
+        unlocated (its x is NaN, its flag 0)."""
+        import ctypes
+        th = np.ascontiguousarray(np.asarray(theta, np.float64).reshape(-1, self.nth) if self.nth else np.zeros((len(theta), 0)))
+        N = th.shape[0]
+        x = np.full((N, self.nout), np.nan)
+        ef, reg, rc = np.zeros(N, np.int32), np.zeros(N, np.int32), np.zeros(N, np.int32)
+        vp = lambda a: ctypes.c_void_p(a.ctypes.data) if a.size else None
+        self._check(_bind().lmpc_explicit_locate_host(self._e, N, vp(th), vp(x), vp(ef), vp(reg), vp(rc)))
+        return x, ef, reg, rc
+
+    def evaluate(self, theta):
+        """Host arrays in and out, GPU evaluation with the implicit fallback (lmpc_explicit_eval): (x, exitflag, region)."""
+        import ctypes
+        th = np.ascontiguousarray(np.asarray(theta, np.float64).reshape(-1, self.nth) if self.nth else np.zeros((len(theta), 0)))
+        N = th.shape[0]
+        x, ef, reg = np.zeros((N, self.nout)), np.zeros(N, np.int32), np.zeros(N, np.int32)
+        vp = lambda a: ctypes.c_void_p(a.ctypes.data) if a.size else None
+        self._check(_bind().lmpc_explicit_eval(self._e, N, vp(th), vp(x), vp(ef), vp(reg)))
+        return x, ef, reg
+
+    def evaluate_device(self, theta, x=None, exitflag=None, region=None, stream=None):
+        """CUDA tensors in and out on `stream` (default: torch's current stream); synchronises that stream once to
+        read the number of unlocated points, then enqueues their implicit solve.  -> (x, exitflag, region)."""
+        import ctypes
+        import torch
+        from .solver import _dev_arg
+        dev = self.qp.device
+        if not (theta.is_cuda and theta.dtype == torch.float64 and theta.is_contiguous() and theta.dim() == 2
+                and theta.shape[1] == self.nth):
+            raise ValueError(f"theta must be a contiguous float64 CUDA tensor of shape (N, {self.nth})")
+        N = theta.shape[0]
+        if x is None:
+            x = torch.empty((N, self.nout), dtype=torch.float64, device=theta.device)
+        if exitflag is None:
+            exitflag = torch.empty(N, dtype=torch.int32, device=theta.device)
+        if region is None:
+            region = torch.empty(N, dtype=torch.int32, device=theta.device)
+        st = torch.cuda.current_stream(theta.device).cuda_stream if stream is None else stream
+        tp = ctypes.c_void_p(theta.data_ptr()) if theta.numel() else None
+        self._check(_bind().lmpc_explicit_eval_device(
+            self._e, N, tp, _dev_arg(x, "x", torch.float64, N * self.nout, dev, False),
+            _dev_arg(exitflag, "exitflag", torch.int32, N, dev, False), _dev_arg(region, "region", torch.int32, N, dev, False),
+            ctypes.c_void_p(st)))
+        return x, exitflag, region
+
+    def _check(self, rc):
+        if rc != 1:
+            from ._cabi import LmpcError
+            raise LmpcError(rc, (_bind().lmpc_explicit_last_error(self._e) or b"").decode())
+
+    def close(self):
+        if getattr(self, "_e", None):
+            import torch
+            if self.qp is not None and torch.cuda.is_available():
+                torch.cuda.synchronize(self.qp.device)
+            _bind().lmpc_explicit_free(self._e)
+            self._e = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -358,3 +358,44 @@ class GeneratedController:
         controller condenses references.  None stands for the C caller's NULL."""
         return self.model.compute_control(control, state, reference, disturbance, affine_parameter,
                                           warm=self.warm_start)
+
+
+class ExplicitMPC:
+    """`ExplicitMPC(mpc; range)` + `build_tree!` + `compute_control(empc, x)` (reference src/explicit.jl:23-76,
+    src/utils.jl:53-60) on the batched backend: the controller's regions and laws come from a sample of the range
+    solved on the GPU (explicit.ExplicitController), on the handle `control_model()` gives, so the outputs are
+    u - K x as in utils.jl:48-49.  `range` = (lb, ub) of theta = [x; r; d; uprev; p]."""
+
+    def __init__(self, mpc: MPC, range, nsamples=10**6, seed=0, extra_theta=None, build_tree=True, **opts):
+        self.mpc = mpc
+        self.lb, self.ub = (np.asarray(a, float).reshape(-1) for a in range)
+        self.nsamples, self.seed, self.extra_theta, self.opts = int(nsamples), int(seed), extra_theta, opts
+        self.uprev = np.zeros(mpc.nu)
+        self.controller = None
+        self.last_region = None
+        if build_tree:
+            self.build_tree()
+
+    def build_tree(self):
+        """`build_tree!`: sample, solve, build the regions and the point-location tree, upload them."""
+        from .explicit import ExplicitController
+        if self.controller is not None:
+            self.controller.close()
+        self.controller = ExplicitController.from_range(self.mpc.control_model(), self.lb, self.ub, self.nsamples,
+                                                        self.seed, self.extra_theta, **self.opts)
+        return self.controller
+
+    def form_parameter(self, x, r=None, d=None, uprev=None, p=None):
+        """explicit.jl:54-63: as MPC.form_parameter, with this controller's own uprev as the default."""
+        return self.mpc.form_parameter(x, r, d, self.uprev[:self.mpc.nuprev] if uprev is None else uprev, p)
+
+    def compute_control(self, x, r=None, d=None, uprev=None, p=None, check=True):
+        if self.controller is None:
+            raise RuntimeError("Need to build a binary search tree to evaluate control law")
+        theta = self.form_parameter(x, r, d, uprev, p)
+        u, flag, region = self.controller.evaluate(theta[None])
+        if check:
+            assert flag[0] >= 1, f"exit flag {flag[0]}"
+        self.last_region = int(region[0])
+        self.uprev = u[0].copy()
+        return self.uprev.copy()
