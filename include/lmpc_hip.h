@@ -714,6 +714,99 @@ int lmpc_explicit_eval(lmpc_explicit *e, int64_t N, const double *theta, double 
 const char *lmpc_explicit_last_error(const lmpc_explicit *e);
 void lmpc_explicit_free(lmpc_explicit *e);
 
+/*
+ * The scenario loop: the closed loop of the reference's Simulation (src/simulation.jl:37-116) for N independent
+ * scenarios, WITH what lmpc_simulate* leaves out -- a disturbance trajectory d acting on the plant (Gd) and on the
+ * measurement (Dd), an affine-parameter trajectory p, plant and measurement offsets, optional additive measurement
+ * noise, the generated state observer in the loop, the outputs y / ym / xhat / d next to x / u, and the running cost and
+ * worst constraint violation of every scenario (evaluate_cost / constraint_violation, src/utils.jl:397-425).
+ * Lock-step, shaped like lmpc_simulate_ref_device: per time step a PRE kernel, the handle's batched solve, a POST
+ * kernel, all enqueued on `stream`; no host synchronisation inside (the once-per-handle probe that
+ * lmpc_solve_batch_device documents is the one exception, as everywhere).  Binary64.  Every handle the plain solve
+ * accepts works (is_avi, hybrid / branch and bound, proximal-point), because the solve is the handle's own.  The
+ * scenario-asynchronous machinery ("sim_async", run-ahead, "sim_keep_factor") does not apply to this loop, and the
+ * offset-free observer (lmpc_compute_control_observer_device) is not part of it.
+ *
+ * Step k (0-based), per scenario:
+ *   PRE   d_k = column k of d;  ym_j = h_offset_j + sum_i C_ji x_i + sum_q Dd_jq d_q (+ noise_j of column k), summed in
+ *         exactly that order with separate multiply and add;  y_j = sum_i C_ji x_i + sum_q Dd_jq d_q (from 0, same
+ *         order) with an observer -- simulation.jl:95 -- and y = ym without one;
+ *         xhat <- mpc_correct_state(xhat, ym, d_k) with the handle's lmpc_set_observer arrays, the arithmetic of
+ *         lmpc_correct_state_device bit for bit; without an observer xhat = x;
+ *         theta = [xhat; r-block; d-block; uprev; p-block]:  r column k, or columns k+1 .. k+H with r.H > 0;  d and p
+ *         column k, or columns k .. k+H-1 (simulation.jl:101-104); columns past the end repeat the last one.
+ *   solve u = the handle's solve of theta (nout == nu); warm != 0: from the previous step's final working set (the first
+ *         step cold), as lmpc_simulate_ref_device does.
+ *   POST  running cost and violation on (x_k, u_k), see lmpc_sim_cost;  xhat <- mpc_predict_state(xhat, u, d_k), the
+ *         arithmetic of lmpc_predict_state_device bit for bit;  x <- f_offset + F x + G u + Gd d_k by the SAME row sums
+ *         on `plant`, so that one plant step equals lmpc_predict_state_device called with the plant's array;
+ *         uprev <- u; trajectories; flag_min.
+ * Consequence of the unfused plant step: with no d, no offsets and no observer this loop is NOT bit-identical to
+ * lmpc_simulate_ref_device, whose plant step is a chain of fused multiply-adds.
+ *
+ * The blocks' k0 is ignored (the loop sets it).  d.w is nd (or 0: d_k = 0 and no d block in theta), noise.w is ny (or
+ * 0: none; noise.H must be 0), p.w the base parameter count, r.w the reference's width.  A block with src == NULL and
+ * w > 0 gives zeros.  Output trajectories are step-major like U_traj: Y_traj / Ym_traj T x N x ny, Xhat_traj T x N x nx
+ * (the corrected estimate the controller saw), D_traj T x N x nd.
+ */
+typedef struct lmpc_sim_cost {
+    int32_t ny;                          /* rows of C = length of the reference column the cost reads            */
+    int32_t nc;                          /* constraint rows                                                      */
+    const double *C, *Q, *R, *Rr, *S;    /* HOST, dense row-major: C ny x nx, Q ny x ny, R and Rr nu x nu, S nx x nu;
+                                          * NULL = zero (the term is left out)                                   */
+    const double *Ax, *Au, *lb, *ub;     /* HOST, dense row-major: Ax nc x nx, Au nc x nu (NULL = zero), lb, ub nc */
+} lmpc_sim_cost;
+/* Cost (evaluate_cost, utils.jl:397-411):  0.5 * sum_k [ e_k'Q e_k + u_k'R u_k + du_k'Rr du_k + x_k'S u_k ],
+ * e_k = C x_k - r_k (r_k = column k of r, held at its last column; zeros without r), du_k = u_k - u_{k-1} with
+ * u_{-1} = 0 whatever uprev holds (diff([zeros(nu) us])), x_k the state BEFORE step k's move.  Order of summation, the
+ * same in the loop and in lmpc_evaluate_cost_device: a form a'M b is sum_j a_j * (sum_l M_jl b_l), inner and outer sums
+ * from 0 in index order; (C x)_j from 0 in index order, then minus r_j; a step's four terms are added to 0 in the order
+ * written; the steps' values are added to 0 in the order k = 0, 1, ...; the product with 0.5 comes last.  Separate
+ * multiply and add throughout.
+ * Violation (constraint_violation, utils.jl:417-425): rows lb <= Ax x_k + Au u_k <= ub; v_j = sum Ax_ji x_i, then
+ * + sum Au_jl u_l (from 0, index order); per step max over j of max(lb_j - v_j, v_j - ub_j, 0); the loop keeps the
+ * maximum over the steps.  Both bit for bit what the stand-alone functions below give on the stored X_traj / U_traj. */
+typedef struct lmpc_scenario_sim {
+    int32_t nx, nu, nd, ny;              /* plant dimensions; nd = model.nd (ONE column of d); nx <= 32, nd, ny <= 32 */
+    const double *plant;                 /* HOST, nx rows [f_offset_i, F_i(nx), G_i(nu), Gd_i(nd)]: the TRUE plant, in
+                                          * the MPC_PLANT_DYNAMICS layout of lmpc_observer                        */
+    const double *measurement;           /* HOST, ny rows [h_offset_j, C_j(nx), Dd_j(nd)], or NULL with ny == 0  */
+    lmpc_block r, d, p, noise;           /* DEVICE trajectories (per scenario or shared), H > 0 = preview        */
+    int32_t nuprev, use_observer, warm;  /* use_observer != 0: the handle's lmpc_set_observer arrays run in the loop */
+    double *Y_traj, *Ym_traj, *Xhat_traj, *D_traj;   /* DEVICE, optional outputs, or NULL                        */
+    const lmpc_sim_cost *cost;           /* HOST, optional                                                       */
+    double *cost_out, *violation_out;    /* DEVICE, N doubles each, or NULL                                      */
+} lmpc_scenario_sim;
+/* Host-only check of a descriptor against a handle's dimensions (no GPU touched): `observer` = the dimensions
+ * lmpc_set_observer was given (arrays not read) or NULL = none set.  LMPC_OK, or LMPC_ERR_BADARG with a text in
+ * lmpc_last_error(NULL) that names the offending field first: nx > 32, nu != nout, a negative width or preview length
+ * ("d.w", "r.H", ...), d.w / noise.w that disagree with nd / ny, use_observer without an observer, an observer set with
+ * other nx / nu / nd / ny than the descriptor, block widths that do not add up to nth ("nth"), outputs asked for
+ * without their inputs.  lmpc_simulate_scenario* runs the same check first, with the handle's own dimensions. */
+int lmpc_scenario_check(int nth, int nout, const lmpc_observer *observer, const lmpc_scenario_sim *s);
+/*   x      N records of nx: in = initial TRUE states, out = states after T steps
+ *   xhat   N records of nx, in/out: the observer's state; NULL = it starts at x (set_state!, simulation.jl:92) and is
+ *          kept in the handle's scratch; must be NULL without use_observer
+ *   uprev  N records of nuprev, in/out (NULL allowed when nuprev == 0)
+ *   U_traj T x N x nu, X_traj (T+1) x N x nx, flag_min N: as lmpc_simulate_device, any may be NULL
+ * lmpc_simulate_scenario_device: DEVICE pointers except where marked HOST; asynchronous on `stream` (the HOST arrays
+ * are read before the call returns).  lmpc_simulate_scenario: the same call with every DEVICE array (the blocks'
+ * sources and the descriptor's outputs included) given as a HOST array; synchronous; uprev NULL = zeros. */
+int lmpc_simulate_scenario_device(lmpc_handle *h, int64_t N, int T, const lmpc_scenario_sim *s, double *x, double *xhat,
+                                  double *uprev, double *U_traj, double *X_traj, int32_t *flag_min, void *stream);
+int lmpc_simulate_scenario(lmpc_handle *h, int64_t N, int T, const lmpc_scenario_sim *s, double *x, double *xhat,
+                           double *uprev, double *U_traj, double *X_traj, int32_t *flag_min);
+/* Scoring of a stored run, one thread per scenario: X = the states x_0 .. x_{T-1}, step-major (the first T slices of an
+ * X_traj), U = T x N x nu as U_traj.  r: the reference trajectory as in the loop (column k at step k; NULL = zeros).
+ * cost_out: N doubles.  violation_out: N doubles (maximum over the steps) and / or violation_steps: T x N, the
+ * per-step values the reference's constraint_violation(c, xs, us) returns.  DEVICE arrays, asynchronous on `stream`.
+ * lmpc_evaluate_cost_device reads the weights of `cost`, lmpc_constraint_violation_device the rows of `rows`. */
+int lmpc_evaluate_cost_device(lmpc_handle *h, int64_t N, int T, int nx, int nu, const lmpc_sim_cost *cost, const double *X,
+                              const double *U, const lmpc_block *r, double *cost_out, void *stream);
+int lmpc_constraint_violation_device(lmpc_handle *h, int64_t N, int T, int nx, int nu, const lmpc_sim_cost *rows,
+                                     const double *X, const double *U, double *violation_out, double *violation_steps,
+                                     void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,6 +36,8 @@ SYMBOLS = (
     "lmpc_explicit_default_opts", "lmpc_explicit_build_ldp", "lmpc_explicit_build", "lmpc_explicit_info",
     "lmpc_explicit_region", "lmpc_explicit_blob", "lmpc_explicit_training", "lmpc_explicit_locate_host",
     "lmpc_explicit_eval_device", "lmpc_explicit_eval", "lmpc_explicit_last_error", "lmpc_explicit_free",
+    "lmpc_scenario_check", "lmpc_simulate_scenario_device", "lmpc_simulate_scenario", "lmpc_evaluate_cost_device",
+    "lmpc_constraint_violation_device",
 )
 
 
@@ -73,6 +75,23 @@ class Observer(ctypes.Structure):
     _fields_ = [("n_state", ctypes.c_int32), ("n_control", ctypes.c_int32), ("n_disturbance", ctypes.c_int32),
                 ("n_measurement", ctypes.c_int32), ("plant_dynamics", ctypes.c_void_p),
                 ("measurement_function", ctypes.c_void_p), ("k_transpose", ctypes.c_void_p)]
+
+
+class SimCost(ctypes.Structure):
+    """`lmpc_sim_cost`: weights of evaluate_cost and rows of constraint_violation (reference utils.jl:397-425)."""
+    _fields_ = [("ny", ctypes.c_int32), ("nc", ctypes.c_int32)] + \
+               [(k, ctypes.c_void_p) for k in ("C", "Q", "R", "Rr", "S", "Ax", "Au", "lb", "ub")]
+
+
+class ScenarioSim(ctypes.Structure):
+    """`lmpc_scenario_sim`: descriptor of the scenario loop (lmpc_simulate_scenario*)."""
+    _fields_ = [("nx", ctypes.c_int32), ("nu", ctypes.c_int32), ("nd", ctypes.c_int32), ("ny", ctypes.c_int32),
+                ("plant", ctypes.c_void_p), ("measurement", ctypes.c_void_p),
+                ("r", Block), ("d", Block), ("p", Block), ("noise", Block),
+                ("nuprev", ctypes.c_int32), ("use_observer", ctypes.c_int32), ("warm", ctypes.c_int32),
+                ("Y_traj", ctypes.c_void_p), ("Ym_traj", ctypes.c_void_p), ("Xhat_traj", ctypes.c_void_p),
+                ("D_traj", ctypes.c_void_p), ("cost", ctypes.POINTER(SimCost)),
+                ("cost_out", ctypes.c_void_p), ("violation_out", ctypes.c_void_p)]
 
 
 _lib = None
@@ -202,6 +221,17 @@ def lib():
     L.lmpc_unpin_host.restype = i32
     L.lmpc_last_error.argtypes = [vp]
     L.lmpc_last_error.restype = ctypes.c_char_p
+    sp = ctypes.POINTER(ScenarioSim)
+    L.lmpc_scenario_check.argtypes = [i32, i32, ctypes.POINTER(Observer), sp]
+    L.lmpc_scenario_check.restype = i32
+    L.lmpc_simulate_scenario_device.argtypes = [vp, i64, i32, sp] + [vp] * 7
+    L.lmpc_simulate_scenario_device.restype = i32
+    L.lmpc_simulate_scenario.argtypes = [vp, i64, i32, sp] + [vp] * 6
+    L.lmpc_simulate_scenario.restype = i32
+    L.lmpc_evaluate_cost_device.argtypes = [vp, i64, i32, i32, i32, ctypes.POINTER(SimCost), vp, vp, bp, vp, vp]
+    L.lmpc_evaluate_cost_device.restype = i32
+    L.lmpc_constraint_violation_device.argtypes = [vp, i64, i32, i32, i32, ctypes.POINTER(SimCost), vp, vp, vp, vp, vp]
+    L.lmpc_constraint_violation_device.restype = i32
     _lib = L
     return L
 

@@ -819,6 +819,7 @@ static void preload_code(lmpc_handle *h) {
     hipFuncAttributes fa;
     (void)hipFuncGetAttributes(&fa, (const void *)screen_kernel<8, 7, 0>);         // this unit: screening and lane kernels
     loop_preload();                                                                // ... the closed-loop / controller unit
+    scenario_preload();                                                            // ... the scenario loop's unit
     if (h->avi) avi_preload(h);
     else {
         if (fast_covers(h)) fast_preload(h);
@@ -1321,6 +1322,7 @@ int lmpc_release_scratch(lmpc_handle *h) {
     rel(h->ccTheta); rel(h->ccAct); rel(h->ccFlag); h->ccCap = 0; h->ccWarmN = -1;
     rel(h->ccStage); rel(h->ccStageFlag); h->ccStageCap = 0; h->ccStagePer = 0;
     rel(h->ccObsScratch); h->ccObsCap = 0;
+    rel(h->scnC); rel(h->scnScr); h->scnCCap = h->scnScrCap = 0;
     rel(h->dOvfList); h->ovfCap = 0; rel(h->dOvfList1); h->ovfCap1 = 0; rel(h->dBigR); rel(h->dBigI);
     rel(h->dBnbR); rel(h->dBnbI); h->bnbBytesR = h->bnbBytesI = 0;
     rel(h->dRowBnb); h->rowBnbBytes = 0;
@@ -1359,7 +1361,7 @@ void lmpc_free(lmpc_handle *h) {
     hipFree(h->dStat);
     hipFree(h->simTheta); hipFree(h->simTheta2); hipFree(h->simU); hipFree(h->simFG); hipFree(h->simFlag); hipFree(h->simAct); hipFree(h->simK);
     hipFree(h->ccT2S); hipFree(h->ccTheta); hipFree(h->ccAct); hipFree(h->ccFlag); hipFree(h->obsC);
-    hipFree(h->ccStage); hipFree(h->ccStageFlag); hipFree(h->ccObsScratch);
+    hipFree(h->ccStage); hipFree(h->ccStageFlag); hipFree(h->ccObsScratch); hipFree(h->scnC); hipFree(h->scnScr);
     if (h->hFastErr) {
         if (*h->hFastErr != 0) std::fprintf(stderr, "lmpc_free: unreported error word %d of the one-launch kernel\n", (int)*h->hFastErr);
         hipHostFree(const_cast<int32_t *>(h->hFastErr));

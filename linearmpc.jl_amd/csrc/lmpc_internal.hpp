@@ -181,6 +181,10 @@ struct lmpc_handle {
     int obsNx = 0, obsNu = 0, obsNd = 0, obsNy = 0;
     double *ccObsScratch = nullptr;     // lmpc_compute_control_observer: state and disturbance split from the observer state
     int64_t ccObsCap = 0;
+    // scenario loop (lmpc_scenario.hip): the run's constants (true plant, measurement, cost weights, constraint rows) and
+    // its per-run scratch (observer state the caller does not keep, previous control of the cost's du term)
+    double *scnC = nullptr, *scnScr = nullptr;
+    size_t scnCCap = 0, scnScrCap = 0;
     double *ccStage = nullptr;          // host-pointer entry point: device copies of the five argument arrays
     int32_t *ccStageFlag = nullptr;
     int64_t ccStageCap = 0;
@@ -291,6 +295,7 @@ int api_wave_probe(lmpc_handle *h, const double *theta, int64_t nprob, hipStream
 int api_launch_wave_f32(lmpc_handle *h, const float *dC, int64_t nprob, const float *theta, float *x, int32_t *flag, int32_t *iters,
                         uint64_t *active, const uint64_t *warm, hipStream_t st);
 void loop_preload();
+void scenario_preload();
 
 // four problems per wavefront (lmpc_row_inst.hip): capacity the batch would run at on that kernel (0: it does not take
 // the batch), and its launch as the only pass (pass 0) or the first of two (pass 1) of a wavefront-kernel call

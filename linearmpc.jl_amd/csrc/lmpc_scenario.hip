@@ -1,0 +1,366 @@
+// C ABI of liblmpc_hip.so, the scenario loop: closed-loop simulation of N scenarios with disturbance, affine
+// parameters, plant / measurement offsets and the generated state observer (lmpc_simulate_scenario*), and the
+// scoring of a run (lmpc_evaluate_cost_device, lmpc_constraint_violation_device).  Lock-step like
+// lmpc_simulate_ref_device: per step a PRE kernel, the handle's solve (api_launch), a POST kernel
+// (lmpc_scenario_kernels.hpp); nothing but enqueues on the caller's stream.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "lmpc_internal.hpp"
+#include "lmpc_scenario_kernels.hpp"
+
+using namespace lmpc;
+
+namespace {
+
+ScnBlock blk(const lmpc_block &b) {
+    return ScnBlock{b.src, b.stride, b.w, b.T > 0 ? b.T : 1, b.k0, b.H};
+}
+int bwidth(const lmpc_block &b) { return b.w * (b.H > 0 ? b.H : 1); }
+
+// every check that needs no device; `obs`: the dimensions lmpc_set_observer was given, or nullptr.  "" = fine,
+// otherwise the text, which starts with the offending field's name
+std::string scenario_problem(int nth, int nout, const lmpc_observer *obs, const lmpc_scenario_sim *s) {
+    if (!s) return "s: NULL descriptor";
+    auto bad = [](const char *f, const std::string &why) { return std::string(f) + ": " + why; };
+    if (s->nx < 1 || s->nx > 32) return bad("nx", "1 <= nx <= 32, got " + std::to_string(s->nx));
+    if (s->nu != nout || s->nu < 0 || s->nu > 64)
+        return bad("nu", "must equal the handle's nout = " + std::to_string(nout) + " (and be <= 64), got " + std::to_string(s->nu));
+    if (s->nd < 0 || s->nd > 32) return bad("nd", "0 <= nd <= 32, got " + std::to_string(s->nd));
+    if (s->ny < 0 || s->ny > 32) return bad("ny", "0 <= ny <= 32, got " + std::to_string(s->ny));
+    if (!s->plant) return bad("plant", "NULL");
+    if (s->ny > 0 && !s->measurement) return bad("measurement", "NULL with ny > 0");
+    const lmpc_block *bs[4] = {&s->r, &s->d, &s->p, &s->noise};
+    const char *bn[4] = {"r", "d", "p", "noise"};
+    for (int b = 0; b < 4; b++) {
+        if (bs[b]->w < 0) return bad((std::string(bn[b]) + ".w").c_str(), "negative width");
+        if (bs[b]->H < 0) return bad((std::string(bn[b]) + ".H").c_str(), "negative preview length");
+        if (bs[b]->src && bs[b]->w > 0 && bs[b]->T < 1) return bad((std::string(bn[b]) + ".T").c_str(), "no columns");
+        if (bs[b]->stride < 0) return bad((std::string(bn[b]) + ".stride").c_str(), "negative stride");
+    }
+    if (s->d.w != 0 && s->d.w != s->nd) return bad("d.w", "must be nd = " + std::to_string(s->nd) + " (or 0: no disturbance), got " + std::to_string(s->d.w));
+    if (s->noise.w != 0 && s->noise.w != s->ny) return bad("noise.w", "must be ny = " + std::to_string(s->ny) + " (or 0: no noise), got " + std::to_string(s->noise.w));
+    if (s->noise.H != 0) return bad("noise.H", "the noise block has no preview");
+    if (s->nuprev < 0 || s->nuprev > s->nu) return bad("nuprev", "0 <= nuprev <= nu, got " + std::to_string(s->nuprev));
+    if (s->use_observer) {
+        if (!obs) return bad("use_observer", "lmpc_set_observer has not been called on this handle");
+        if (s->ny < 1) return bad("ny", "an observer needs a measurement (ny >= 1)");
+        if (obs->n_state != s->nx) return bad("nx", "the observer was set with n_state = " + std::to_string(obs->n_state) + ", the descriptor says " + std::to_string(s->nx));
+        if (obs->n_control != s->nu) return bad("nu", "the observer was set with n_control = " + std::to_string(obs->n_control) + ", the descriptor says " + std::to_string(s->nu));
+        if (obs->n_disturbance != s->nd) return bad("nd", "the observer was set with n_disturbance = " + std::to_string(obs->n_disturbance) + ", the descriptor says " + std::to_string(s->nd));
+        if (obs->n_measurement != s->ny) return bad("ny", "the observer was set with n_measurement = " + std::to_string(obs->n_measurement) + ", the descriptor says " + std::to_string(s->ny));
+    }
+    const int sum = s->nx + bwidth(s->r) + bwidth(s->d) + s->nuprev + bwidth(s->p);
+    if (sum != nth)
+        return bad("nth", "nx + width(r) + width(d) + nuprev + width(p) = " + std::to_string(sum) + " must equal the handle's nth = " + std::to_string(nth));
+    if ((s->Y_traj || s->Ym_traj) && s->ny == 0) return bad(s->Y_traj ? "Y_traj" : "Ym_traj", "asked for with ny = 0");
+    if (s->D_traj && s->nd == 0) return bad("D_traj", "asked for with nd = 0");
+    if (s->cost_out && !s->cost) return bad("cost_out", "asked for without cost");
+    if (s->violation_out && !s->cost) return bad("violation_out", "asked for without cost");
+    if (const lmpc_sim_cost *c = s->cost) {
+        if (c->ny < 0 || c->ny > 32) return bad("cost.ny", "0 <= ny <= 32, got " + std::to_string(c->ny));
+        if (c->nc < 0) return bad("cost.nc", "negative row count");
+        if (c->Q && (!c->C || c->ny == 0)) return bad("cost.C", "Q given without C (ny rows)");
+        if (c->C && s->r.w > 0 && s->r.w != c->ny) return bad("cost.ny", "must equal r.w = " + std::to_string(s->r.w) + ", got " + std::to_string(c->ny));
+        if (c->nc > 0 && (!c->lb || !c->ub)) return bad("cost.lb", "lb and ub are required with nc > 0");
+    }
+    return "";
+}
+
+// the run's constants in one host vector + their offsets; cost may be nullptr
+ScnConst pack_constants(std::vector<double> &v, int nx, int nu, int nd, int ny, const double *plant, const double *meas,
+                        const lmpc_sim_cost *c) {
+    ScnConst K{nullptr, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, 0, 0};
+    auto put = [&](const double *src, size_t cnt) -> int {
+        if (!src || cnt == 0) return -1;
+        const int off = (int)v.size();
+        v.insert(v.end(), src, src + cnt);
+        return off;
+    };
+    if (plant) K.plant = put(plant, (size_t)nx * (1 + nx + nu + nd));
+    if (meas && ny > 0) K.meas = put(meas, (size_t)ny * (1 + nx + nd));
+    if (c) {
+        K.nyc = c->C ? c->ny : 0; K.nc = c->nc;
+        K.cC = put(c->C, (size_t)c->ny * nx); K.cQ = put(c->Q, (size_t)c->ny * c->ny);
+        K.cR = put(c->R, (size_t)nu * nu); K.cRr = put(c->Rr, (size_t)nu * nu); K.cS = put(c->S, (size_t)nx * nu);
+        K.cAx = put(c->Ax, (size_t)c->nc * nx); K.cAu = put(c->Au, (size_t)c->nc * nu);
+        K.clb = put(c->lb, (size_t)c->nc); K.cub = put(c->ub, (size_t)c->nc);
+    }
+    if (v.empty()) v.push_back(0.0);
+    return K;
+}
+
+int upload_constants(lmpc_handle *h, const std::vector<double> &v, ScnConst &K, hipStream_t st) {
+    if (v.size() > h->scnCCap) {
+        hipFree(h->scnC); h->scnC = nullptr; h->scnCCap = 0;
+        HIP_TRY(h, hipMalloc(&h->scnC, sizeof(double) * v.size()));
+        h->scnCCap = v.size();
+    }
+    HIP_TRY(h, hipMemcpyAsync(h->scnC, v.data(), sizeof(double) * v.size(), hipMemcpyHostToDevice, st));
+    K.c = h->scnC;
+    return LMPC_OK;
+}
+
+int need_device(lmpc_handle *h) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(h, LMPC_ERR_NOGPU, "lmpc: no HIP device available (this library has no CPU path)");
+    return LMPC_OK;
+}
+
+template <int NXT>
+void launch_pre(const ScnPre &A, const ScnConst &K, hipStream_t st) {
+    const unsigned grid = (unsigned)((A.n + 255) / 256);
+    hipLaunchKernelGGL(scenario_pre_kernel<NXT>, dim3(grid), dim3(256), sizeof(double) * 256 * (size_t)A.nx, st, A, K);
+}
+template <int NXT>
+void launch_post(const ScnPost &A, const ScnConst &K, bool cost, hipStream_t st) {
+    const unsigned grid = (unsigned)((A.n + 255) / 256);
+    if (cost) hipLaunchKernelGGL((scenario_post_kernel<NXT, true>), dim3(grid), dim3(256), 0, st, A, K);
+    else hipLaunchKernelGGL((scenario_post_kernel<NXT, false>), dim3(grid), dim3(256), 0, st, A, K);
+}
+#define LMPC_SCN_NX(nx, CALL)                                                                                           \
+    switch (nx) {                                                                                                       \
+        case 1: CALL(1); break; case 2: CALL(2); break; case 3: CALL(3); break; case 4: CALL(4); break;                 \
+        case 5: CALL(5); break; case 6: CALL(6); break; case 7: CALL(7); break; case 8: CALL(8); break;                 \
+        default: CALL(0); break;                                                                                        \
+    }
+
+}  // namespace
+
+namespace lmpc {
+void scenario_preload() {
+    hipFuncAttributes fa;
+    (void)hipFuncGetAttributes(&fa, (const void *)scenario_pre_kernel<0>);
+    (void)hipGetLastError();
+}
+}  // namespace lmpc
+
+extern "C" {
+
+int lmpc_scenario_check(int nth, int nout, const lmpc_observer *observer, const lmpc_scenario_sim *s) {
+    const std::string msg = scenario_problem(nth, nout, observer, s);
+    if (!msg.empty()) return fail(nullptr, LMPC_ERR_BADARG, "lmpc_scenario_check: " + msg);
+    return LMPC_OK;
+}
+
+int lmpc_simulate_scenario_device(lmpc_handle *h, int64_t N, int T, const lmpc_scenario_sim *s, double *x, double *xhat,
+                                  double *uprev, double *U_traj, double *X_traj, int32_t *flag_min, void *stream) {
+    if (!h) return LMPC_ERR_BADARG;
+    lmpc_observer od{h->obsNx, h->obsNu, h->obsNd, h->obsNy, nullptr, nullptr, nullptr};
+    std::string msg = scenario_problem(h->P.nth, h->P.nout, h->obsC ? &od : nullptr, s);
+    if (msg.empty()) {
+        if (N < 0) msg = "N: negative";
+        else if (T < 0) msg = "T: negative";
+        else if (N > 0 && !x) msg = "x: NULL";
+        else if (N > 0 && s->nuprev > 0 && !uprev) msg = "uprev: NULL with nuprev > 0";
+        else if (xhat && !s->use_observer) msg = "xhat: given without use_observer";
+    }
+    if (!msg.empty()) return fail(h, LMPC_ERR_BADARG, "lmpc_simulate_scenario_device: " + msg);
+    if (N == 0 || T == 0) return LMPC_OK;
+    { const int rcd = need_device(h); if (rcd != LMPC_OK) return rcd; }
+    LMPC_ENTER_DEVICE(h);
+    hipStream_t st = (hipStream_t)stream;
+    { const int rce = api_ensure_sim(h, N); if (rce != LMPC_OK) return rce; }
+    const int nx = s->nx, nu = s->nu, nd = s->nd, ny = s->ny, nup = s->nuprev;
+    std::vector<double> hostC;
+    ScnConst K = pack_constants(hostC, nx, nu, nd, ny, s->plant, s->measurement, s->cost);
+    { const int rcu = upload_constants(h, hostC, K, st); if (rcu != LMPC_OK) return rcu; }
+    const bool obs = s->use_observer != 0;
+    const bool wantCost = s->cost && (s->cost_out || s->violation_out);
+    const bool needUlast = wantCost && s->cost_out && s->cost->Rr;
+    // per-run scratch: the observer state when the caller keeps none, the previous control of the cost's du term
+    const size_t needScr = (size_t)N * ((obs && !xhat ? (size_t)nx : 0) + (needUlast ? (size_t)nu : 0));
+    if (needScr > h->scnScrCap) {
+        hipFree(h->scnScr); h->scnScr = nullptr; h->scnScrCap = 0;
+        HIP_TRY(h, hipMalloc(&h->scnScr, sizeof(double) * needScr));
+        h->scnScrCap = needScr;
+    }
+    double *scr = h->scnScr;
+    if (obs && !xhat) {                                // set_state!(mpc, x0), simulation.jl:92
+        xhat = scr; scr += (size_t)N * nx;
+        HIP_TRY(h, hipMemcpyAsync(xhat, x, sizeof(double) * (size_t)N * nx, hipMemcpyDeviceToDevice, st));
+    }
+    double *ulast = needUlast ? scr : nullptr;
+    if (X_traj) HIP_TRY(h, hipMemcpyAsync(X_traj, x, sizeof(double) * (size_t)N * nx, hipMemcpyDeviceToDevice, st));
+    const size_t obs_nd = (size_t)h->obsNx * (1 + h->obsNx + h->obsNu + h->obsNd);
+    const size_t obs_nm = (size_t)h->obsNy * (1 + h->obsNx + h->obsNd);
+    ScnPre A{};
+    A.x = x; A.xhat = obs ? xhat : nullptr; A.uprev = uprev; A.theta = h->simTheta;
+    A.obs_meas = obs ? h->obsC + obs_nd : nullptr; A.obs_kt = obs ? h->obsC + obs_nd + obs_nm : nullptr;
+    A.r = blk(s->r); A.d = blk(s->d); A.p = blk(s->p); A.noise = blk(s->noise);
+    A.nx = nx; A.ny = ny; A.nd = nd; A.nup = nup; A.n = (long long)N;
+    ScnPost B{};
+    B.x = x; B.xhat = obs ? xhat : nullptr; B.uprev = uprev; B.u = h->simU; B.flag = h->simFlag;
+    B.obs_dyn = obs ? h->obsC : nullptr; B.d = A.d; B.r = A.r;
+    B.flag_min = flag_min; B.cost = wantCost ? s->cost_out : nullptr; B.viol = wantCost ? s->violation_out : nullptr;
+    B.ulast = ulast; B.nx = nx; B.nu = nu; B.nd = nd; B.nup = nup; B.n = (long long)N;
+    for (int k = 0; k < T; k++) {
+        A.k = k;
+        A.r.k0 = A.r.H > 0 ? k + 1 : k;               // simulation.jl:102 get_preview(rs, k, Np) / rs[:, k]
+        A.d.k0 = k; A.p.k0 = k;                       // :103-104 get_preview(ds, k - 1, Np) / ds[:, k]
+        A.ym_out = s->Ym_traj ? s->Ym_traj + (size_t)k * N * ny : nullptr;
+        A.y_out = s->Y_traj ? s->Y_traj + (size_t)k * N * ny : nullptr;
+        A.xhat_out = s->Xhat_traj ? s->Xhat_traj + (size_t)k * N * nx : nullptr;
+        A.d_out = s->D_traj ? s->D_traj + (size_t)k * N * nd : nullptr;
+#define LMPC_PRE(NX) launch_pre<NX>(A, K, st)
+        LMPC_SCN_NX(nx, LMPC_PRE)
+#undef LMPC_PRE
+        HIP_TRY(h, hipGetLastError());
+        // warm start = the previous step's final working set, the first step cold (as lmpc_simulate_ref_device)
+        const uint64_t *wm = (s->warm && k > 0) ? h->simAct : nullptr;
+        const int rc = api_launch(h, N, h->simTheta, h->simU, h->simFlag, nullptr, s->warm ? h->simAct : nullptr, wm, st);
+        if (rc != LMPC_OK) return rc;
+        B.k = k; B.first = k == 0; B.last = k == T - 1;
+        B.xtraj_next = X_traj ? X_traj + (size_t)(k + 1) * N * nx : nullptr;
+        B.utraj = U_traj ? U_traj + (size_t)k * N * nu : nullptr;
+#define LMPC_POST(NX) launch_post<NX>(B, K, wantCost, st)
+        LMPC_SCN_NX(nx, LMPC_POST)
+#undef LMPC_POST
+        HIP_TRY(h, hipGetLastError());
+    }
+    return LMPC_OK;
+}
+
+int lmpc_simulate_scenario(lmpc_handle *h, int64_t N, int T, const lmpc_scenario_sim *s, double *x, double *xhat,
+                           double *uprev, double *U_traj, double *X_traj, int32_t *flag_min) {
+    if (!h) return LMPC_ERR_BADARG;
+    {   // the refusals first, on the caller's descriptor: nothing is allocated for a call that cannot run
+        lmpc_observer od{h->obsNx, h->obsNu, h->obsNd, h->obsNy, nullptr, nullptr, nullptr};
+        std::string msg = scenario_problem(h->P.nth, h->P.nout, h->obsC ? &od : nullptr, s);
+        if (msg.empty()) {
+            if (N < 0) msg = "N: negative";
+            else if (T < 0) msg = "T: negative";
+            else if (N > 0 && !x) msg = "x: NULL";
+            else if (xhat && !s->use_observer) msg = "xhat: given without use_observer";
+        }
+        if (!msg.empty()) return fail(h, LMPC_ERR_BADARG, "lmpc_simulate_scenario: " + msg);
+    }
+    if (N == 0 || T == 0) return LMPC_OK;
+    { const int rcd = need_device(h); if (rcd != LMPC_OK) return rcd; }
+    LMPC_ENTER_DEVICE(h);
+    std::vector<void *> owned;
+    auto cleanup = [&]() { for (void *p : owned) hipFree(p); };
+#define SCN_TRY(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { cleanup(); \
+        return fail(h, LMPC_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); } } while (0)
+    lmpc_scenario_sim d = *s;
+    const int nx = s->nx, nu = s->nu, nd = s->nd, ny = s->ny, nup = s->nuprev;
+    auto dev_alloc = [&](size_t cnt, void **out) -> hipError_t {
+        const hipError_t e = hipMalloc(out, cnt ? cnt : 1);
+        if (e == hipSuccess) owned.push_back(*out);
+        return e;
+    };
+    // trajectories: one matrix per scenario (stride apart) or one shared matrix
+    lmpc_block *bs[4] = {&d.r, &d.d, &d.p, &d.noise};
+    for (lmpc_block *b : bs) {
+        if (!b->src || b->w <= 0) { b->src = nullptr; continue; }
+        const size_t cnt = b->stride > 0 ? (size_t)(N - 1) * (size_t)b->stride + (size_t)b->w * b->T : (size_t)b->w * b->T;
+        void *p = nullptr;
+        SCN_TRY(dev_alloc(sizeof(double) * cnt, &p));
+        SCN_TRY(hipMemcpy(p, b->src, sizeof(double) * cnt, hipMemcpyHostToDevice));
+        b->src = static_cast<const double *>(p);
+    }
+    struct Out { void *host; void *dev; size_t bytes; };
+    std::vector<Out> outs;
+    auto io = [&](void *host, size_t bytes, bool in, void **devp) -> hipError_t {
+        *devp = nullptr;
+        if (!host) return hipSuccess;
+        hipError_t e = dev_alloc(bytes, devp);
+        if (e != hipSuccess) return e;
+        if (in) e = hipMemcpy(*devp, host, bytes, hipMemcpyHostToDevice);
+        outs.push_back(Out{host, *devp, bytes});
+        return e;
+    };
+    void *dx, *dxh, *dup = nullptr, *dU, *dX, *dfm, *dY, *dYm, *dXh, *dD, *dco, *dvo;
+    SCN_TRY(io(x, sizeof(double) * (size_t)N * nx, true, &dx));
+    SCN_TRY(io(xhat, sizeof(double) * (size_t)N * nx, true, &dxh));
+    if (nup > 0) {                                     // NULL = zeros, as in lmpc_simulate
+        if (uprev) SCN_TRY(io(uprev, sizeof(double) * (size_t)N * nup, true, &dup));
+        else { SCN_TRY(dev_alloc(sizeof(double) * (size_t)N * nup, &dup)); SCN_TRY(hipMemset(dup, 0, sizeof(double) * (size_t)N * nup)); }
+    }
+    SCN_TRY(io(U_traj, sizeof(double) * (size_t)T * N * nu, false, &dU));
+    SCN_TRY(io(X_traj, sizeof(double) * (size_t)(T + 1) * N * nx, false, &dX));
+    SCN_TRY(io(flag_min, sizeof(int32_t) * (size_t)N, false, &dfm));
+    SCN_TRY(io(s->Y_traj, sizeof(double) * (size_t)T * N * ny, false, &dY));
+    SCN_TRY(io(s->Ym_traj, sizeof(double) * (size_t)T * N * ny, false, &dYm));
+    SCN_TRY(io(s->Xhat_traj, sizeof(double) * (size_t)T * N * nx, false, &dXh));
+    SCN_TRY(io(s->D_traj, sizeof(double) * (size_t)T * N * nd, false, &dD));
+    SCN_TRY(io(s->cost_out, sizeof(double) * (size_t)N, false, &dco));
+    SCN_TRY(io(s->violation_out, sizeof(double) * (size_t)N, false, &dvo));
+    d.Y_traj = (double *)dY; d.Ym_traj = (double *)dYm; d.Xhat_traj = (double *)dXh; d.D_traj = (double *)dD;
+    d.cost_out = (double *)dco; d.violation_out = (double *)dvo;
+    const int rc = lmpc_simulate_scenario_device(h, N, T, &d, (double *)dx, (double *)dxh, (double *)dup, (double *)dU,
+                                                 (double *)dX, (int32_t *)dfm, nullptr);
+    if (rc == LMPC_OK) {
+        SCN_TRY(hipDeviceSynchronize());
+        for (const Out &o : outs) SCN_TRY(hipMemcpy(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost));
+    }
+#undef SCN_TRY
+    cleanup();
+    return rc;
+}
+
+int lmpc_evaluate_cost_device(lmpc_handle *h, int64_t N, int T, int nx, int nu, const lmpc_sim_cost *cost, const double *X,
+                              const double *U, const lmpc_block *r, double *cost_out, void *stream) {
+    if (!h) return LMPC_ERR_BADARG;
+    std::string msg;
+    if (N < 0) msg = "N: negative";
+    else if (T < 0) msg = "T: negative";
+    else if (nx < 1 || nx > 32) msg = "nx: 1 <= nx <= 32";
+    else if (nu < 0 || nu > 64) msg = "nu: 0 <= nu <= 64";
+    else if (!cost) msg = "cost: NULL";
+    else if (cost->ny < 0 || cost->ny > 32) msg = "cost.ny: 0 <= ny <= 32";
+    else if (cost->Q && (!cost->C || cost->ny == 0)) msg = "cost.C: Q given without C (ny rows)";
+    else if (r && r->src && cost->C && r->w != cost->ny) msg = "r.w: must equal cost.ny";
+    else if (r && r->src && (r->T < 1 || r->stride < 0)) msg = "r.T: no columns, or negative stride";
+    else if (N > 0 && T > 0 && (!X || !U || !cost_out)) msg = "X / U / cost_out: NULL";
+    if (!msg.empty()) return fail(h, LMPC_ERR_BADARG, "lmpc_evaluate_cost_device: " + msg);
+    if (N == 0) return LMPC_OK;
+    { const int rcd = need_device(h); if (rcd != LMPC_OK) return rcd; }
+    LMPC_ENTER_DEVICE(h);
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<double> hostC;
+    lmpc_sim_cost c = *cost;
+    c.nc = 0; c.Ax = c.Au = c.lb = c.ub = nullptr;
+    ScnConst K = pack_constants(hostC, nx, nu, 0, 0, nullptr, nullptr, &c);
+    { const int rcu = upload_constants(h, hostC, K, st); if (rcu != LMPC_OK) return rcu; }
+    ScnBlock br{nullptr, 0, 0, 1, 0, 0};
+    if (r && r->src && cost->C) br = blk(*r);
+    hipLaunchKernelGGL(scenario_cost_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, K, X, U, br, nx, nu, T,
+                       cost_out, (long long)N);
+    HIP_TRY(h, hipGetLastError());
+    return LMPC_OK;
+}
+
+int lmpc_constraint_violation_device(lmpc_handle *h, int64_t N, int T, int nx, int nu, const lmpc_sim_cost *rows, const double *X,
+                                     const double *U, double *violation_out, double *violation_steps, void *stream) {
+    if (!h) return LMPC_ERR_BADARG;
+    std::string msg;
+    if (N < 0) msg = "N: negative";
+    else if (T < 0) msg = "T: negative";
+    else if (nx < 1 || nx > 32) msg = "nx: 1 <= nx <= 32";
+    else if (nu < 0 || nu > 64) msg = "nu: 0 <= nu <= 64";
+    else if (!rows) msg = "rows: NULL";
+    else if (rows->nc < 0) msg = "rows.nc: negative row count";
+    else if (rows->nc > 0 && (!rows->lb || !rows->ub)) msg = "rows.lb: lb and ub are required with nc > 0";
+    else if (N > 0 && T > 0 && (!X || !U || (!violation_out && !violation_steps))) msg = "X / U / violation_out: NULL";
+    if (!msg.empty()) return fail(h, LMPC_ERR_BADARG, "lmpc_constraint_violation_device: " + msg);
+    if (N == 0) return LMPC_OK;
+    { const int rcd = need_device(h); if (rcd != LMPC_OK) return rcd; }
+    LMPC_ENTER_DEVICE(h);
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<double> hostC;
+    lmpc_sim_cost c = *rows;
+    c.C = c.Q = c.R = c.Rr = c.S = nullptr;
+    ScnConst K = pack_constants(hostC, nx, nu, 0, 0, nullptr, nullptr, &c);
+    { const int rcu = upload_constants(h, hostC, K, st); if (rcu != LMPC_OK) return rcu; }
+    hipLaunchKernelGGL(scenario_violation_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, K, X, U, nx, nu, T,
+                       violation_out, violation_steps, (long long)N);
+    HIP_TRY(h, hipGetLastError());
+    return LMPC_OK;
+}
+
+}  // extern "C"

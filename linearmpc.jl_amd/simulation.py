@@ -1,0 +1,251 @@
+"""Mirror of the reference's closed-loop simulation (/root/reference/src/simulation.jl:1-134) for MANY scenarios
+at once, on the scenario loop of the library (`lmpc_simulate_scenario_device`, include/lmpc_hip.h):
+
+    Plant(F, G, Gd, f_offset, C, Dd, h_offset)    the true plant and its measurement (model.jl:17-30)
+    Scenario(x0, N, r, d, p, noise)               simulation.jl:13-35; x0 (nx,) or (N_scen, nx); r, d, p, noise
+                                                  (w, T) shared by all scenarios or (N_scen, w, T)
+    Simulation(mpc, scenario, plant, observer)    simulation.jl:37-116 -> ts, ys, us, xs, rs, ds, xhats, yms, flag_min
+    evaluate_cost / constraint_violation          utils.jl:397-425, on the device
+
+Callbacks and nonlinear dynamics (`scenario.callback`, `scenario.dynamics`) have no counterpart: the plant is the
+affine one the kernels step.  An MPC with reference condensation is refused (its theta block is not a cut of r).
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from .solver import BatchedQP
+
+__all__ = ["Plant", "Scenario", "Simulation", "evaluate_cost", "constraint_violation"]
+
+
+class Plant:
+    """x+ = F x + G u + Gd d + f_offset,  y = C x + Dd d + h_offset."""
+
+    def __init__(self, F, G, Gd=None, f_offset=None, C=None, Dd=None, h_offset=None):
+        self.F = np.atleast_2d(np.asarray(F, float))
+        self.nx = self.F.shape[0]
+        self.G = np.asarray(G, float).reshape(self.nx, -1)
+        self.nu = self.G.shape[1]
+        self.Gd = np.zeros((self.nx, 0)) if Gd is None else np.asarray(Gd, float).reshape(self.nx, -1)
+        self.nd = self.Gd.shape[1]
+        self.f_offset = np.zeros(self.nx) if f_offset is None else np.asarray(f_offset, float).reshape(self.nx)
+        self.C = np.eye(self.nx) if C is None else np.asarray(C, float).reshape(-1, self.nx)
+        self.ny = self.C.shape[0]
+        self.Dd = np.zeros((self.ny, self.nd)) if Dd is None else np.asarray(Dd, float).reshape(self.ny, self.nd)
+        self.h_offset = np.zeros(self.ny) if h_offset is None else np.asarray(h_offset, float).reshape(self.ny)
+
+    def dynamics_rows(self):
+        """MPC_PLANT_DYNAMICS layout (reference src/observer.jl:136): rows [f_offset_i, F_i, G_i, Gd_i]."""
+        return np.ascontiguousarray(np.hstack([self.f_offset[:, None], self.F, self.G, self.Gd]))
+
+    def measurement_rows(self):
+        """MPC_MEASUREMENT_FUNCTION layout (:137): rows [h_offset_j, C_j, Dd_j]."""
+        return np.ascontiguousarray(np.hstack([self.h_offset[:, None], self.C, self.Dd]))
+
+
+class Scenario:
+    """simulation.jl:13-35 for N_scen scenarios.  Trajectories keep their own length; `trajectory` gives them over
+    the N steps of the run, cut or held at the last column (simulation.jl:69-88)."""
+
+    def __init__(self, x0, N=1000, r=None, d=None, p=None, noise=None):
+        x0 = np.asarray(x0, float)
+        self.single = x0.ndim == 1
+        self.x0 = np.ascontiguousarray(np.atleast_2d(x0))
+        self.n_scen, self.N = self.x0.shape[0], int(N)
+        self.r, self.d, self.p, self.noise = (self._traj(a, k) for a, k in ((r, "r"), (d, "d"), (p, "p"), (noise, "noise")))
+
+    def _traj(self, a, name):
+        if a is None or np.size(a) == 0:
+            return None
+        a = np.asarray(a, float)
+        if a.ndim == 1:
+            a = a[:, None]
+        if a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[0] != self.n_scen):
+            raise ValueError(f"{name} must have shape (w, T) or ({self.n_scen}, w, T), got {a.shape}")
+        return a
+
+    def trajectory(self, name, w=0):
+        """The (w, N) or (N_scen, w, N) array the reference's loop indexes: columns beyond the given ones repeat the
+        last, columns beyond the run are cut; None -> zeros (w, N)."""
+        a = getattr(self, name)
+        if a is None:
+            return np.zeros((w, self.N))
+        Tc = a.shape[-1]
+        idx = np.minimum(np.arange(self.N), Tc - 1)
+        return np.ascontiguousarray(a[..., idx])
+
+    def block_spec(self, name, H=0, w=0):
+        """What becomes the `lmpc_block` of a trajectory: dict(data, stride, w, T, H) with `data` laid out column
+        after column per scenario ((T, w) or (N_scen, T, w); None = zeros), stride 0 for a shared trajectory and
+        w * T for one per scenario; the columns are those of the run (at most N)."""
+        a = getattr(self, name)
+        if a is None:
+            return dict(data=None, stride=0, w=int(w), T=1, H=int(H))
+        a = a[..., :self.N]
+        w_, Tc = a.shape[-2], a.shape[-1]
+        return dict(data=np.ascontiguousarray(np.swapaxes(a, -1, -2)), stride=w_ * Tc if a.ndim == 3 else 0,
+                    w=int(w_), T=int(Tc), H=int(H))
+
+
+def scenario_blocks(mpc, scenario):
+    """The four block specs of a run: column or preview follows the MPC's settings as simulation.jl:74,81,89 (and
+    the widths of theta) have it."""
+    if mpc.reference_condensation:
+        raise ValueError("reference condensation is not available in the scenario loop")
+    Np = mpc.Np
+    specs = {
+        "r": scenario.block_spec("r", Np if (mpc.reference_preview and mpc.nr > 0) else 0, mpc.ny if mpc.nr > 0 else 0),
+        "d": scenario.block_spec("d", Np if (mpc.disturbance_preview and mpc.nd > 0) else 0, mpc.nd_base),
+        "p": scenario.block_spec("p", Np if (mpc.parameter_preview and mpc.np > 0) else 0, mpc.np_base),
+        "noise": scenario.block_spec("noise", 0, 0),
+    }
+    if mpc.nr == 0:                          # no reference in theta: the trajectory only serves the cost
+        specs["r"] = dict(data=None, stride=0, w=0, T=1, H=0)
+    for k, w in (("r", mpc.ny if mpc.nr > 0 else 0), ("d", mpc.nd_base), ("p", mpc.np_base)):
+        if specs[k]["data"] is not None and specs[k]["w"] != w:
+            raise ValueError(f"{k} trajectory must have {w} rows, got {specs[k]['w']}")
+    return specs
+
+
+def _observer_arrays(observer):
+    if observer is None:
+        return None
+    if hasattr(observer, "codegen_arrays"):
+        observer = observer.codegen_arrays()
+    dyn, meas, kt = (np.asarray(a, float) for a in observer)
+    return dyn, meas, kt
+
+
+class Simulation:
+    """`Simulation(mpc, scenario)` of the reference for every scenario at once.  mpc: an `MPC` of this package;
+    plant: the true `Plant`; observer: None, an object with `codegen_arrays()` or the triple (MPC_PLANT_DYNAMICS,
+    MPC_MEASUREMENT_FUNCTION, K_TRANSPOSE_OBSERVER) of the generated observer (src/observer.jl:124-141).
+    Fields as in the reference, one leading scenario axis unless x0 was a single vector: xs, xhats (nx, N), us
+    (nu, N), ys, yms (ny, N), rs, ds, ts, and flag_min (smallest exit flag per scenario)."""
+
+    def __init__(self, mpc, scenario, plant, observer=None, warm=False, cost=None):
+        import torch
+        from .mpc import ExplicitMPC
+        if isinstance(mpc, ExplicitMPC):
+            raise NotImplementedError("the scenario loop runs the implicit controller (see DESIGN.md)")
+        model: BatchedQP = mpc.control_model()
+        self.mpc, self.scenario, self.plant, self.model = mpc, scenario, plant, model
+        dev = torch.device("cuda", model.device)
+        T, S = scenario.N, scenario.n_scen
+        if plant.nx != mpc.nx or plant.nu != mpc.nu:
+            raise ValueError("plant and controller disagree on nx / nu")
+        if plant.nd != mpc.nd_base:
+            raise ValueError(f"the plant has {plant.nd} disturbances, the controller's theta {mpc.nd_base}")
+        obs = _observer_arrays(observer)
+        if obs is not None:
+            model.set_observer(*obs, plant.nx, plant.nu, plant.nd, plant.ny)
+        specs = scenario_blocks(mpc, scenario)
+        up = lambda sp: None if sp["data"] is None else torch.from_numpy(np.swapaxes(sp["data"], -1, -2).copy()).to(dev)
+        x = torch.from_numpy(scenario.x0.copy()).to(dev)
+        uprev = None
+        if mpc.nuprev:
+            uprev = torch.from_numpy(np.tile(np.asarray(mpc.uprev, float)[:mpc.nuprev], (S, 1))).to(dev)
+        out = model.simulate_scenario(
+            x, T, plant.dynamics_rows(), plant.measurement_rows(), nd=plant.nd, ny=plant.ny,
+            r=up(specs["r"]), d=up(specs["d"]), p=up(specs["p"]), noise=up(specs["noise"]),
+            r_preview=specs["r"]["H"], d_preview=specs["d"]["H"], p_preview=specs["p"]["H"],
+            r_width=specs["r"]["w"], d_width=specs["d"]["w"], p_width=specs["p"]["w"], uprev=uprev,
+            use_observer=obs is not None, warm=warm, cost=cost,
+            want=("U", "X", "Y", "Ym", "Xhat") + (("D",) if plant.nd else ()),
+            want_cost=cost is not None, want_violation=cost is not None and cost[0].nc > 0)
+        torch.cuda.synchronize(dev)
+        model.check()
+        per = lambda t: np.ascontiguousarray(t.cpu().numpy().transpose(1, 2, 0))      # (T, S, w) -> (S, w, T)
+        self.xs, self.us = per(out["X"][:T]), per(out["U"])
+        self.ys, self.yms, self.xhats = per(out["Y"]), per(out["Ym"]), per(out["Xhat"])
+        self.ds = per(out["D"]) if plant.nd else np.zeros((S, 0, T))
+        rs = scenario.trajectory("r", mpc.ny)
+        self.rs = np.broadcast_to(rs, (S,) + rs.shape[-2:]).copy()
+        self.x_final = out["x"].cpu().numpy()
+        self.flag_min = out["flag_min"].cpu().numpy()
+        self.cost = out["cost"].cpu().numpy() if "cost" in out else None
+        self.violation = out["violation"].cpu().numpy() if "violation" in out else None
+        self.ts = np.arange(T, dtype=float)
+        if scenario.single:
+            for k in ("xs", "us", "ys", "yms", "xhats", "ds", "rs"):
+                setattr(self, k, getattr(self, k)[0])
+
+
+_scoring = {}
+
+
+def _scoring_model(device=0):
+    """The scoring kernels read nothing of a handle but its GPU: any handle serves, this one holds a 1 x 1 problem."""
+    if device not in _scoring:
+        one = np.ones((1, 1))
+        _scoring[device] = BatchedQP.from_mpqp(one, np.zeros(1), one, np.zeros((0, 1)), np.ones(1), -np.ones(1), one * 0.0,
+                                               device=device)
+    return _scoring[device]
+
+
+def _step_major(a, w):
+    """(w, T) or (S, w, T) host array -> (T, S, w) contiguous, and whether it was a single scenario."""
+    a = np.asarray(a, float)
+    if a.ndim == 1:
+        a = a.reshape(w, -1) if w else a[None]
+    single = a.ndim == 2
+    a = a[None] if single else a
+    return np.ascontiguousarray(a.transpose(2, 0, 1)), single
+
+
+def evaluate_cost(sim, C=None, Q=None, R=None, Rr=None, S=None, xs=None, us=None, rs=None, model=None):
+    """`evaluate_cost(mpc, xs, us, rs; Q, R, Rr, S)` (utils.jl:397-411) on the device: 0.5 sum_k (C x_k - r_k)'Q(..) +
+    u'Ru + du'Rr du + x'Su per scenario.  `sim`: a Simulation (its xs, us, rs and handle), or None with xs, us
+    [, rs] given as (w, T) / (N_scen, w, T) arrays.  C defaults to the simulation's plant.C.  Returns a float for a
+    single scenario, else an (N_scen,) array."""
+    import torch
+    if sim is not None:
+        xs = sim.xs if xs is None else xs
+        us = sim.us if us is None else us
+        rs = sim.rs if rs is None else rs
+        model = sim.model if model is None else model
+        C = sim.plant.C if C is None else C
+    model = _scoring_model() if model is None else model
+    dev = torch.device("cuda", model.device)
+    xs = np.asarray(xs, float)
+    nx = xs.shape[-2] if xs.ndim > 1 else 1
+    us = np.asarray(us, float)
+    nu = us.shape[-2] if us.ndim > 1 else 1
+    X, single = _step_major(xs, nx)
+    U, _ = _step_major(us, nu)
+    cost = BatchedQP.sim_cost(nx, nu, C=C, Q=Q, R=R, Rr=Rr, S=S)
+    r = None
+    if rs is not None and np.size(rs) and cost[0].ny > 0:
+        rs = np.asarray(rs, float).reshape((-1, cost[0].ny, X.shape[0]) if np.ndim(rs) != 2 else (cost[0].ny, -1))
+        r = torch.from_numpy(np.ascontiguousarray(rs)).to(dev)
+    out = model.evaluate_cost_device(torch.from_numpy(X).to(dev), torch.from_numpy(U).to(dev), cost, r)
+    torch.cuda.synchronize(dev)
+    out = out.cpu().numpy()
+    return float(out[0]) if single else out
+
+
+def constraint_violation(Ax, Au, lb, ub, xs, us, model=None):
+    """`constraint_violation(c, xs, us)` (utils.jl:417-425) on the device for rows lb <= Ax x + Au u <= ub: the
+    violation max(lb - v, v - ub, 0) over the rows, per step.  xs (nx,) / us (nu,): one number; (nx, T) / (nu, T):
+    an array of T; (N_scen, nx, T): (N_scen, T)."""
+    import torch
+    lb, ub = np.asarray(lb, float).reshape(-1), np.asarray(ub, float).reshape(-1)
+    nc = lb.size
+    nx = np.asarray(Ax, float).reshape(nc, -1).shape[1] if Ax is not None else np.asarray(xs).shape[-2 if np.ndim(xs) > 1 else 0]
+    nu = np.asarray(Au, float).reshape(nc, -1).shape[1] if Au is not None else np.asarray(us).shape[-2 if np.ndim(us) > 1 else 0]
+    xs, us = np.asarray(xs, float), np.asarray(us, float)
+    point = xs.ndim == 1
+    if point:
+        xs, us = xs.reshape(nx, 1), us.reshape(nu, 1)
+    if xs.shape[-1] != us.shape[-1]:
+        raise AssertionError("xs and us must have as many columns")           # utils.jl:423
+    X, single = _step_major(xs, nx)
+    U, _ = _step_major(us, nu)
+    model = _scoring_model() if model is None else model
+    dev = torch.device("cuda", model.device)
+    rows = BatchedQP.sim_cost(nx, nu, Ax=Ax, Au=Au, lb=lb, ub=ub)
+    out = model.constraint_violation_device(torch.from_numpy(X).to(dev), torch.from_numpy(U).to(dev), rows, per_step=True)
+    torch.cuda.synchronize(dev)
+    out = out.cpu().numpy().T                                                  # (S, T)
+    return float(out[0, 0]) if point else (out[0] if single else out)

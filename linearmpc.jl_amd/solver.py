@@ -497,6 +497,146 @@ class BatchedQP:
         return dict(x=x.cpu().numpy(), U=U.cpu().numpy(), X=X.cpu().numpy(),
                     uprev=None if up is None else up.cpu().numpy(), flag_min=fm.cpu().numpy())
 
+    # ------------------------------------------------------------------ scenario loop
+    @staticmethod
+    def sim_cost(nx, nu, C=None, Q=None, R=None, Rr=None, S=None, Ax=None, Au=None, lb=None, ub=None):
+        """`lmpc_sim_cost` from host arrays (any may be None = zero): returns (struct, arrays to keep alive)."""
+        keep = {}
+
+        def mat(a, rows, cols, name):
+            if a is None:
+                return None
+            a = np.asarray(a, float)
+            if a.ndim == 1 and rows == cols and a.size == rows:          # a weight given by its diagonal
+                a = np.diag(a)
+            keep[name] = _f64(a.reshape(rows, cols))
+            return keep[name].ctypes.data
+
+        ny = 0 if C is None else int(np.atleast_2d(np.asarray(C, float)).reshape(-1, nx).shape[0])
+        nc = 0 if lb is None else int(np.asarray(lb).size)
+        c = _cabi.SimCost(ny, nc, mat(C, ny, nx, "C"), mat(Q, ny, ny, "Q"), mat(R, nu, nu, "R"), mat(Rr, nu, nu, "Rr"),
+                          mat(S, nx, nu, "S"), mat(Ax, nc, nx, "Ax"), mat(Au, nc, nu, "Au"), mat(lb, nc, 1, "lb"),
+                          mat(ub, nc, 1, "ub"))
+        return c, keep
+
+    def scenario_descriptor(self, plant, nx, nd=0, measurement=None, ny=0, r=None, d=None, p=None, noise=None,
+                            nuprev=0, use_observer=False, warm=False, cost=None):
+        """`lmpc_scenario_sim` from host constants and ready-made blocks (`Block` or None = left out).  Returns
+        (struct, keep-alive list)."""
+        pl = _f64(np.asarray(plant, float).reshape(-1))
+        me = None if measurement is None else _f64(np.asarray(measurement, float).reshape(-1))
+        s = _cabi.ScenarioSim()
+        s.nx, s.nu, s.nd, s.ny = int(nx), self.nout, int(nd), int(ny)
+        s.plant = pl.ctypes.data
+        s.measurement = me.ctypes.data if me is not None else None
+        for name, b in (("r", r), ("d", d), ("p", p), ("noise", noise)):
+            setattr(s, name, b if b is not None else Block(None, 0, 0, 1, 0, 0))
+        s.nuprev, s.use_observer, s.warm = int(nuprev), int(bool(use_observer)), int(bool(warm))
+        keep = [pl, me]
+        if cost is not None:
+            c, ck = cost if isinstance(cost, tuple) else (cost, None)
+            s.cost = ctypes.pointer(c)
+            keep += [c, ck]
+        return s, keep
+
+    def scenario_check(self, desc, observer_dims="handle"):
+        """`lmpc_scenario_check` of a descriptor against this handle's dimensions (host only)."""
+        od = getattr(self, "_obs", None) if observer_dims == "handle" else observer_dims
+        o = None if od is None else ctypes.byref(Observer(*[int(v) for v in od], None, None, None))
+        check(lib().lmpc_scenario_check(self.nth, self.nout, o, ctypes.byref(desc)))
+
+    def simulate_scenario(self, x, T, plant, measurement=None, nd=0, ny=0, r=None, d=None, p=None, noise=None,
+                          r_preview=0, d_preview=0, p_preview=0, r_width=0, d_width=None, p_width=0, xhat=None,
+                          uprev=None, use_observer=False, warm=False, cost=None, want=("U", "X"), want_cost=False,
+                          want_violation=False, stream=None):
+        """The scenario loop (`lmpc_simulate_scenario_device`): torch CUDA tensors in and out, enqueued on `stream`
+        (default: torch's current stream), not synchronised.
+
+        x (N, nx) float64: true states, advanced in place; xhat (N, nx) or None; uprev (N, nuprev) or None (zeros
+        when the handle's theta has a uprev block).  plant: nx rows [f_offset, F, G, Gd]; measurement: ny rows
+        [h_offset, C, Dd] (host arrays).  r / d / p / noise: (w,), (w, Tc) shared or (N, w, Tc) per scenario, or None
+        = zeros of width r_width / d_width (default nd) / p_width; *_preview = Np or 0.  cost: `sim_cost(...)`.
+        want: which of "U", "X", "Y", "Ym", "Xhat", "D" to store.  Returns a dict of tensors (step-major, as the C
+        side lays them out) plus x, xhat, uprev, flag_min and, if asked for, cost / violation."""
+        import torch
+        f64, dv = torch.float64, self.device
+        if not (x.is_cuda and x.dtype == f64 and x.is_contiguous() and x.dim() == 2 and x.device.index == dv):
+            raise ValueError("x must be a contiguous float64 CUDA tensor of shape (N, nx) on this handle's GPU")
+        N, nx = int(x.shape[0]), int(x.shape[1])
+        dev, nu, T = x.device, self.nout, int(T)
+        d_width = int(nd) if d_width is None else int(d_width)
+        keep = []
+
+        def block(t, w0, H):
+            if t is None:
+                return Block(None, 0, int(w0), 1, 0, int(H)) if w0 else None
+            if t.dim() == 3 and t.shape[0] != N:
+                raise ValueError("a per-scenario trajectory must have shape (N, w, T)")
+            b, k = self._block(t.to(dev), H, 0)
+            keep.append(k)
+            return b
+
+        br, bd = block(r, r_width, r_preview), block(d, d_width, d_preview)
+        bp, bn = block(p, p_width, p_preview), block(noise, 0, 0)
+        nup = self.nth - nx - sum(b.w * (b.H if b.H > 0 else 1) for b in (br, bd, bp) if b is not None)
+        if uprev is None and 0 < nup <= nu:
+            uprev = torch.zeros((N, nup), dtype=f64, device=dev)
+        nup = 0 if uprev is None else int(uprev.shape[1])
+        out = dict(x=x, xhat=xhat, uprev=uprev, flag_min=torch.empty(N, dtype=torch.int32, device=dev))
+        shapes = dict(U=(T, N, nu), X=(T + 1, N, nx), Y=(T, N, ny), Ym=(T, N, ny), Xhat=(T, N, nx), D=(T, N, nd))
+        for k in want:
+            out[k] = torch.empty(shapes[k], dtype=f64, device=dev)
+        desc, hk = self.scenario_descriptor(plant, nx, nd, measurement, ny, br, bd, bp, bn, nup, use_observer, warm, cost)
+        keep.append(hk)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        desc.Y_traj, desc.Ym_traj = ptr(out.get("Y")), ptr(out.get("Ym"))
+        desc.Xhat_traj, desc.D_traj = ptr(out.get("Xhat")), ptr(out.get("D"))
+        if want_cost:
+            out["cost"] = torch.empty(N, dtype=f64, device=dev)
+            desc.cost_out = out["cost"].data_ptr()
+        if want_violation:
+            out["violation"] = torch.empty(N, dtype=f64, device=dev)
+            desc.violation_out = out["violation"].data_ptr()
+        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        check(lib().lmpc_simulate_scenario_device(
+            self._h, N, T, ctypes.byref(desc), _vp(x.data_ptr()), _dev_arg(xhat, "xhat", f64, N * nx, dv),
+            _dev_arg(uprev, "uprev", f64, N * nup, dv), _vp(ptr(out.get("U"))), _vp(ptr(out.get("X"))),
+            _vp(out["flag_min"].data_ptr()), _vp(st)), self._h)
+        out["_keep"] = keep                      # the launches are asynchronous: keep the sources alive
+        return out
+
+    def evaluate_cost_device(self, X, U, cost, r=None, stream=None):
+        """`lmpc_evaluate_cost_device`: X (>= T, N, nx) and U (T, N, nu) step-major CUDA tensors, cost =
+        `sim_cost(...)`, r as in `simulate_scenario`.  Returns the (N,) cost tensor (not synchronised)."""
+        import torch
+        T, N, nu = (int(v) for v in U.shape)
+        nx = int(X.shape[2])
+        c, ck = cost
+        br, kr = self._block(r, 0, 0)
+        out = torch.empty(N, dtype=torch.float64, device=U.device)
+        st = torch.cuda.current_stream(U.device).cuda_stream if stream is None else stream
+        check(lib().lmpc_evaluate_cost_device(
+            self._h, N, T, nx, nu, ctypes.byref(c), _dev_arg(X[:T], "X", torch.float64, T * N * nx, self.device, False),
+            _dev_arg(U, "U", torch.float64, T * N * nu, self.device, False),
+            ctypes.byref(br) if br is not None else None, _vp(out.data_ptr()), _vp(st)), self._h)
+        out._lmpc_keep = (kr, ck)
+        return out
+
+    def constraint_violation_device(self, X, U, rows, per_step=False, stream=None):
+        """`lmpc_constraint_violation_device`: worst violation per scenario (N,), or per step (T, N)."""
+        import torch
+        T, N, nu = (int(v) for v in U.shape)
+        nx = int(X.shape[2])
+        c, ck = rows
+        out = torch.empty((T, N) if per_step else (N,), dtype=torch.float64, device=U.device)
+        st = torch.cuda.current_stream(U.device).cuda_stream if stream is None else stream
+        check(lib().lmpc_constraint_violation_device(
+            self._h, N, T, nx, nu, ctypes.byref(c), _dev_arg(X[:T], "X", torch.float64, T * N * nx, self.device, False),
+            _dev_arg(U, "U", torch.float64, T * N * nu, self.device, False),
+            None if per_step else _vp(out.data_ptr()), _vp(out.data_ptr()) if per_step else None, _vp(st)), self._h)
+        out._lmpc_keep = ck
+        return out
+
     # ------------------------------------------------------------------ generated-controller entry point
     def set_parameter_layout(self, nx, nr=0, nd=0, nuprev=0, np_=0, preview_horizon=0, traj2setpoint=None):
         """`lmpc_set_parameter_layout`: N_STATE, N_REFERENCE, N_DISTURBANCE, N_CONTROL_PREV,
