@@ -1,6 +1,8 @@
 """The scenario loop on the GPU (lmpc_simulate_scenario_device): bit for bit against the composition of the entry
-points that existed before it, the reference's own closed-loop assertions through `Simulation`, the cost and
-constraint-violation scoring, and the independence of scenarios."""
+points that existed before it AND against the host reference loop of tests/scenario_reference.py (numpy + the CPU
+oracle on the handle's own pack, no call into the library) at every state-size instantiation of the glue kernels,
+the reference's own closed-loop assertions through `Simulation`, the cost and constraint-violation scoring, and the
+independence of scenarios."""
 import numpy as np
 import pytest
 
@@ -123,7 +125,28 @@ def _both(lmpc, prob, x0, T, obs=None, warm=False, **traj):
     plant = _plant(lmpc, prob)
     sim = lmpc.Simulation(mpc, lmpc.Scenario(x0, N=T, **traj), plant, observer=obs, warm=warm)
     ref = _composed(lmpc, mpc, plant, obs, x0, T, warm=warm, **traj)
+    if not mpc.control_model().is_avi:                    # the host reference loop as well (its oracle is the LDP one)
+        _assert_identical(sim, _host_reference(mpc, prob, x0, T, obs, warm, **traj), T)
     return sim, ref, mpc
+
+
+def _oracle_settings(mpc):
+    from oracle import ldp as oldp
+    s = oldp.default_settings()
+    for name in ("primal_tol", "dual_tol", "zero_tol", "progress_tol", "fval_bound", "rho_soft", "cycle_tol", "iter_limit"):
+        setattr(s, name, getattr(mpc.settings, name))
+    return s
+
+
+def _host_reference(mpc, prob, x0, T, obs=None, warm=False, **traj):
+    """reference_run on the handle's own pack, in the tuple _assert_identical reads"""
+    import scenario_reference as sr
+    from conftest import oracle_ldp_from
+    dims, previews = sr.dims_of(prob)
+    ref = sr.reference_run(oracle_ldp_from(mpc.control_model().ldp()), dims, sr.plant_of(prob), x0, T, observer=obs,
+                           previews=previews, uprev0=getattr(prob, "uprev0", None), warm=warm,
+                           settings=_oracle_settings(mpc), **traj)
+    return ref.xs, ref.us, ref.xhats, ref.yms, ref.ys, ref.flag_min
 
 
 def _assert_identical(sim, ref, T):
@@ -401,3 +424,197 @@ def test_host_pointer_twin_gives_the_same_run(lmpc):
     assert np.array_equal(U.transpose(1, 2, 0), sim.us) and np.array_equal(X[:T].transpose(1, 2, 0), sim.xs)
     assert np.array_equal(Y.transpose(1, 2, 0), sim.ys) and np.array_equal(fm, sim.flag_min)
     assert np.array_equal(x, sim.x_final) and np.array_equal(up[:, 0], sim.us[:, 0, -1])
+
+
+# ------------------------------------------------------------------ the host reference loop, bit for bit
+# tests/scenario_reference.py restates the loop in numpy + the CPU oracle; the cases (scenario_reference.CASES) and the
+# conditions that keep them from passing emptily are checked on the host first (tests/test_scenario_host.py).
+def _cases(group):
+    import scenario_reference as sr
+    return [pytest.param(c, id=c.name) for c in group(sr)]
+
+
+def _gpu_and_reference(lmpc, case, mpc=None):
+    import scenario_reference as sr
+    from conftest import oracle_ldp_from
+    data = sr.case_data(case)
+    mpc = _mpc(lmpc, data.prob) if mpc is None else mpc
+    cost = None if data.cost is None else lmpc.BatchedQP.sim_cost(case.nx, case.nu, **data.cost)
+    traj = {k: getattr(data, k) for k in ("r", "d", "p", "noise") if getattr(data, k) is not None}
+    sim = lmpc.Simulation(mpc, lmpc.Scenario(data.x0, N=case.T, **traj), _plant(lmpc, data.prob), observer=data.kf,
+                          warm=case.warm, cost=cost)
+    ref = sr.run_case(case, oracle_ldp_from(mpc.control_model().ldp()), data, settings=_oracle_settings(mpc))
+    return sim, ref, data, mpc
+
+
+def _assert_bitwise(case, sim, ref):
+    """np.array_equal on every output, no scenario or step left out.  Walks the steps in causal order first (PRE
+    outputs, then u, then the POST state) so that a failure names the first array and step that differ."""
+    T = case.T
+    for k in range(T):
+        nxt = sim.xs[..., k + 1] if k + 1 < T else sim.x_final
+        for name, got, want in (("xs", sim.xs[..., k], ref.xs[k]), ("ds", sim.ds[..., k], ref.ds[k]),
+                                ("yms", sim.yms[..., k], ref.yms[k]), ("ys", sim.ys[..., k], ref.ys[k]),
+                                ("xhats", sim.xhats[..., k], ref.xhats[k]), ("us", sim.us[..., k], ref.us[k]),
+                                ("x after the step", nxt, ref.xs[k + 1])):
+            if not np.array_equal(got, want):
+                bad = np.flatnonzero((got != want).any(axis=1))
+                raise AssertionError(f"{case.name}: first difference in {name} at step {k}: {bad.size} of {len(got)} scenarios "
+                                     f"(first {bad[:5]}), max |diff| = {np.abs(got - want).max():.3e}")
+    step = lambda a: a.transpose(1, 2, 0)
+    assert np.array_equal(sim.xs, step(ref.xs[:T])) and np.array_equal(sim.x_final, ref.xs[T])
+    assert np.array_equal(sim.us, step(ref.us)) and np.array_equal(sim.xhats, step(ref.xhats))
+    assert np.array_equal(sim.yms, step(ref.yms)) and np.array_equal(sim.ys, step(ref.ys))
+    assert np.array_equal(sim.ds, step(ref.ds))
+    assert np.array_equal(sim.flag_min, ref.flag_min)
+    if case.cost:
+        assert np.array_equal(sim.cost, ref.cost), np.abs(sim.cost - ref.cost).max()
+        assert np.array_equal(sim.violation, ref.violation)
+
+
+def _run_and_compare(lmpc, case, mpc=None):
+    import scenario_reference as sr
+    sim, ref, data, mpc = _gpu_and_reference(lmpc, case, mpc)
+    _assert_bitwise(case, sim, ref)
+    sr.check_conditions(case, ref, sim)
+    return sim, ref, data, mpc
+
+
+@pytest.mark.parametrize("case", _cases(lambda sr: sr.SWEEP))
+def test_every_state_size_equals_the_host_reference(lmpc, case):
+    # scenario_pre_kernel<NX> / scenario_post_kernel<NX, false>: NX = 1 .. 8 unrolled, 9 / 17 / 32 the generic form;
+    # nu = 2, ny = 3, nd = 2, uprev in theta, noise, S = 300 (a ragged second workgroup)
+    _, _, _, mpc = _run_and_compare(lmpc, case)
+    if case.nx == 32:
+        assert mpc.control_model().nth >= 34
+
+
+@pytest.mark.parametrize("case", _cases(lambda sr: sr.PREVIEWS))
+def test_all_previews_at_once_equal_the_host_reference(lmpc, case):
+    # r, d and p previews with nuprev = nu: a record of 26 and one of 64 doubles; short (held) and shared trajectories
+    _, _, data, mpc = _run_and_compare(lmpc, case)
+    nth = mpc.control_model().nth
+    assert (16 < nth <= 32) if case.name.endswith("26") else nth >= 60
+    assert data.r.shape[-1] < case.T and any(a.ndim == 2 for a in (data.r, data.d, data.p))
+
+
+@pytest.mark.parametrize("case", _cases(lambda sr: sr.SIZES))
+def test_batch_and_run_sizes_equal_the_host_reference(lmpc, case):
+    # S = 1, 255, 256, 257, 1000 (one lane, a workgroup less one, exactly one, one more, a ragged fourth) and
+    # T = 1 (first and last in one POST launch), 2
+    _run_and_compare(lmpc, case)
+
+
+def _direct_run(lmpc, mpc, case, data, keep_xhat):
+    """model.simulate_scenario as Simulation calls it, optionally with the caller's own xhat buffer"""
+    import torch
+    from linearmpc_jl_amd.simulation import scenario_blocks
+    model = mpc.control_model()
+    plant = _plant(lmpc, data.prob)
+    dev = torch.device("cuda", model.device)
+    traj = {k: getattr(data, k) for k in ("r", "d", "p", "noise") if getattr(data, k) is not None}
+    specs = scenario_blocks(mpc, lmpc.Scenario(data.x0, N=case.T, **traj))
+    up = lambda sp: None if sp["data"] is None else torch.from_numpy(np.swapaxes(sp["data"], -1, -2).copy()).to(dev)
+    model.set_observer(*data.kf.codegen_arrays(), plant.nx, plant.nu, plant.nd, plant.ny)
+    x = torch.from_numpy(data.x0.copy()).to(dev)
+    xhat = x.clone() if keep_xhat else None
+    uprev = torch.from_numpy(np.tile(np.asarray(mpc.uprev, float)[:mpc.nuprev], (case.S, 1))).to(dev)
+    cost = lmpc.BatchedQP.sim_cost(case.nx, case.nu, **data.cost)
+    out = model.simulate_scenario(
+        x, case.T, plant.dynamics_rows(), plant.measurement_rows(), nd=plant.nd, ny=plant.ny, r=up(specs["r"]),
+        d=up(specs["d"]), p=up(specs["p"]), noise=up(specs["noise"]), r_preview=specs["r"]["H"], d_preview=specs["d"]["H"],
+        p_preview=specs["p"]["H"], r_width=specs["r"]["w"], d_width=specs["d"]["w"], p_width=specs["p"]["w"], xhat=xhat,
+        uprev=uprev, use_observer=True, warm=case.warm, cost=cost, want=("U", "X", "Y", "Ym", "Xhat", "D"), want_cost=True,
+        want_violation=True)
+    torch.cuda.synchronize(dev)
+    model.check()
+    return {k: v.cpu().numpy() for k, v in out.items() if isinstance(v, torch.Tensor)}
+
+
+def test_cost_inside_the_loop_with_observer_and_rr(lmpc):
+    # COST = true with an observer and Rr together: the per-run scratch is [xhat | ulast]; then the same run with the
+    # caller keeping xhat, scratch = [ulast] alone -- the same numbers
+    import scenario_reference as sr
+    case = sr.COST
+    sim, ref, data, mpc = _run_and_compare(lmpc, case)
+    assert data.cost["Rr"] is not None and data.cost["Ax"].shape == (4, case.nx) and case.nu == 3
+    for keep in (False, True):
+        out = _direct_run(lmpc, mpc, case, data, keep_xhat=keep)
+        for key, want in (("U", ref.us), ("X", ref.xs), ("Y", ref.ys), ("Ym", ref.yms), ("Xhat", ref.xhats), ("D", ref.ds),
+                          ("x", ref.xs[-1]), ("flag_min", ref.flag_min), ("cost", ref.cost), ("violation", ref.violation),
+                          ("uprev", ref.uprev_final)):
+            assert np.array_equal(out[key], want), (keep, key)
+        if keep:
+            assert np.array_equal(out["xhat"], ref.xhat_final)
+
+
+def test_one_handle_several_runs(lmpc):
+    # S = 200, then 2000 (the scratch and the outputs of the first run regrow), then 50 (what the larger run left
+    # in cost / viol / ulast / flag_min must not be read): each run equals the reference
+    import scenario_reference as sr
+    mpc, model = None, None
+    for case in sr.RERUN:
+        _, _, _, mpc = _run_and_compare(lmpc, case, mpc)
+        assert model is None or mpc.control_model() is model
+        model = mpc.control_model()
+
+
+@pytest.mark.parametrize("case", _cases(lambda sr: sr.SCORING))
+def test_stand_alone_scoring_equals_the_host_reference(lmpc, case):
+    # scenario_cost_kernel / scenario_violation_kernel on stored trajectories at nx = 32, nu = 8 and at nx = 3:
+    # bitwise the reference's cost / violation / per-step violation, and the in-loop values
+    import torch
+    import scenario_reference as sr
+    sim, ref, data, mpc = _run_and_compare(lmpc, case)
+    model = mpc.control_model()
+    dev = torch.device("cuda", model.device)
+    X = torch.from_numpy(np.ascontiguousarray(sim.xs.transpose(2, 0, 1))).to(dev)
+    U = torch.from_numpy(np.ascontiguousarray(sim.us.transpose(2, 0, 1))).to(dev)
+    rs = sr.run_trajectory(data.r, case.S, case.T)
+    k = data.cost
+    weights = lmpc.BatchedQP.sim_cost(case.nx, case.nu, C=k["C"], Q=k["Q"], R=k["R"], Rr=k["Rr"], S=k["S"])
+    rows = lmpc.BatchedQP.sim_cost(case.nx, case.nu, Ax=k["Ax"], Au=k["Au"], lb=k["lb"], ub=k["ub"])
+    cost = model.evaluate_cost_device(X, U, weights, torch.from_numpy(np.ascontiguousarray(rs)).to(dev))
+    worst = model.constraint_violation_device(X, U, rows)
+    steps = model.constraint_violation_device(X, U, rows, per_step=True)
+    torch.cuda.synchronize(dev)
+    model.check()
+    cost, worst, steps = cost.cpu().numpy(), worst.cpu().numpy(), steps.cpu().numpy()
+    assert np.array_equal(cost, ref.cost) and np.array_equal(cost, sim.cost)
+    assert np.array_equal(worst, ref.violation) and np.array_equal(worst, sim.violation)
+    assert steps.shape == (case.T, case.S) and np.array_equal(steps, ref.violation_steps)
+    # the package's own wrappers on the same trajectories
+    assert np.array_equal(lmpc.evaluate_cost(sim, C=k["C"], Q=k["Q"], R=k["R"], Rr=k["Rr"], S=k["S"]), ref.cost)
+    assert np.array_equal(lmpc.constraint_violation(k["Ax"], k["Au"], k["lb"], k["ub"], sim.xs, sim.us, model=model),
+                          ref.violation_steps.T)
+
+
+def test_host_pointer_twin_equals_the_host_reference(lmpc):
+    # lmpc_simulate_scenario at nx = 6 with the observer, d and noise: host arrays in and out
+    import ctypes
+    import scenario_reference as sr
+    from conftest import oracle_ldp_from
+    from linearmpc_jl_amd._cabi import Block, check
+    case = sr.TWIN
+    data = sr.case_data(case)
+    mpc, plant = _mpc(lmpc, data.prob), _plant(lmpc, data.prob)
+    model = mpc.control_model()
+    S, T, nx, nu, ny, nd = case.S, case.T, case.nx, case.nu, case.ny, case.nd
+    model.set_observer(*data.kf.codegen_arrays(), nx, nu, nd, ny)
+    lay = lambda a: np.ascontiguousarray(np.swapaxes(a, 1, 2))             # (S, w, T) -> (S, T, w): column after column
+    r, d, v = lay(data.r), lay(data.d), lay(data.noise)
+    blk = lambda a, w: Block(a.ctypes.data, w * T, w, T, 0, 0)
+    desc, keep = model.scenario_descriptor(plant.dynamics_rows(), nx, nd, plant.measurement_rows(), ny, r=blk(r, ny),
+                                           d=blk(d, nd), noise=blk(v, ny), nuprev=nu, use_observer=True)
+    x, up = data.x0.copy(), np.zeros((S, nu))
+    U, X, fm = np.empty((T, S, nu)), np.empty((T + 1, S, nx)), np.empty(S, np.int32)
+    Y, Ym, Xh, D = np.empty((T, S, ny)), np.empty((T, S, ny)), np.empty((T, S, nx)), np.empty((T, S, nd))
+    desc.Y_traj, desc.Ym_traj, desc.Xhat_traj, desc.D_traj = (a.ctypes.data for a in (Y, Ym, Xh, D))
+    vp = lambda a: ctypes.c_void_p(a.ctypes.data)
+    check(lmpc.lib().lmpc_simulate_scenario(model._h, S, T, ctypes.byref(desc), vp(x), None, vp(up), vp(U), vp(X), vp(fm)),
+          model._h)
+    ref = sr.run_case(case, oracle_ldp_from(model.ldp()), data, settings=_oracle_settings(mpc))
+    sr.check_conditions(case, ref)
+    for name, got, want in (("X", X, ref.xs), ("U", U, ref.us), ("Y", Y, ref.ys), ("Ym", Ym, ref.yms), ("Xhat", Xh, ref.xhats),
+                            ("D", D, ref.ds), ("x", x, ref.xs[-1]), ("uprev", up, ref.uprev_final), ("flag_min", fm, ref.flag_min)):
+        assert np.array_equal(got, want), name
