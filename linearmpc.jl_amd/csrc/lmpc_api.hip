@@ -34,6 +34,14 @@ int fail(lmpc_handle *h, int code, const std::string &msg) {
     return code;
 }
 
+int need_device(lmpc_handle *h, int *count) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(h, LMPC_ERR_NOGPU, "lmpc: no HIP device available (this library has no CPU path)");
+    if (count) *count = ndev;
+    return LMPC_OK;
+}
+
 }  // namespace lmpc
 
 namespace {
@@ -82,8 +90,7 @@ void fill_layout(lmpc_handle *h) {
 int finalize_handle(lmpc_handle *h) {
     const HostPack &P = h->P;
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(h, LMPC_ERR_NOGPU, "lmpc: no HIP device available (this library has no CPU path)");
+    { const int rcd = need_device(h, &ndev); if (rcd != LMPC_OK) return rcd; }
     if (h->device < 0 || h->device >= ndev) return fail(h, LMPC_ERR_BADARG, "lmpc: bad device ordinal");
     int nBinary = 0;
     for (int j = 0; j < P.m; j++) nBinary += (P.sense[j] & SENSE_BINARY) ? 1 : 0;
@@ -1064,9 +1071,7 @@ int lmpc_solve_batch_f32_device(lmpc_handle *h, int64_t N, const float *theta, f
         return fail(h, LMPC_ERR_BADARG, "lmpc_solve_batch_f32_device: NULL array or negative N");
     if (N == 0) return LMPC_OK;
     if (N > (int64_t)0x7fffffff * 64) return fail(h, LMPC_ERR_BADARG, "lmpc: batch too large for one launch");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(h, LMPC_ERR_NOGPU, "lmpc: no HIP device available (this library has no CPU path)");
+    LMPC_NEED_DEVICE(h);
     LMPC_ENTER_DEVICE(h);
     int rc = ensure_f32(h);
     if (rc != LMPC_OK) return rc;
@@ -1082,11 +1087,7 @@ int lmpc_solve_one(lmpc_handle *h, const double *theta, double *x) {
     const size_t nth = (size_t)h->P.nth, nout = (size_t)h->P.nout;
     if (!x || (nth > 0 && !theta)) return fail(h, LMPC_ERR_BADARG, "lmpc_solve_one: NULL array");
     const size_t oX = (sizeof(double) * nth + 63) & ~(size_t)63, oF = oX + ((sizeof(double) * nout + 63) & ~(size_t)63);
-    if (!h->oneHost) {
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-            return fail(h, LMPC_ERR_NOGPU, "lmpc: no HIP device available (this library has no CPU path)");
-    }
+    if (!h->oneHost) LMPC_NEED_DEVICE(h);
     LMPC_ENTER_DEVICE(h);
     if (!h->oneHost) {
         char *hp = nullptr;

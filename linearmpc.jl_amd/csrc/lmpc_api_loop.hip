@@ -27,6 +27,56 @@ void loop_preload() {
 }
 }  // namespace lmpc
 
+namespace {
+// What a closed loop lends to api_launch through the handle -- lmpc_simulate_device: the fused plant step, the
+// scenario-asynchronous rounds, the kept factors, profiling switched off; lmpc_compute_control_device: the gather -- is
+// taken back when the entry point returns, on EVERY path: the handle is then as an ordinary solve expects it.
+struct HandleLoan {
+    lmpc_handle *h;
+    const bool prof;
+    explicit HandleLoan(lmpc_handle *h_) : h(h_), prof(h_->prof) {}
+    HandleLoan(const HandleLoan &) = delete;
+    HandleLoan &operator=(const HandleLoan &) = delete;
+    ~HandleLoan() {
+        h->L.sim = SimFuse{}; h->L.gat = GatherArgs{}; h->waveSim = WaveSim{};
+        h->keepOn = false; h->raWarm = false;
+        h->asyncPhase = 0; h->asyncT = 0; h->asyncCap = 0; h->asyncResetPark = false;
+        h->asyncX = h->asyncR = h->asyncUp = nullptr;
+        h->asyncListIn = h->asyncCntIn = nullptr;
+        h->prof = prof;
+    }
+};
+
+// host-pointer closed loop in either precision: device copies of the caller's arrays around lmpc_simulate_device /
+// lmpc_simulate_f32_device.  uprev == NULL: zeros, and nothing copied back.  The binary64 loop only enqueues, so the
+// device is synchronised before the results are read; the binary32 one leaves that to the blocking copies.
+template <typename R>
+int simulate_host(lmpc_handle *h, int64_t N, int T, int nx, int nr, int nuprev, const double *F, const double *G, R *x,
+                  const R *r, R *uprev, R *U_traj, R *X_traj, int32_t *flag_min, int warm) {
+    if (!h) return LMPC_ERR_BADARG;
+    if (N <= 0 || T <= 0) return N < 0 || T < 0 ? LMPC_ERR_BADARG : LMPC_OK;
+    LMPC_ENTER_DEVICE(h);
+    const size_t n = (size_t)N, nu = (size_t)h->P.nout;
+    Staging sg;
+    R *dx = static_cast<R *>(sg.out(x, sizeof(R) * n * nx, true));
+    R *dr = nr > 0 ? static_cast<R *>(sg.in(r, sizeof(R) * n * nr)) : nullptr, *du = nullptr;
+    if (nuprev > 0) du = static_cast<R *>(uprev ? sg.out(uprev, sizeof(R) * n * nuprev, true) : sg.zeros(sizeof(R) * n * nuprev));
+    R *dU = static_cast<R *>(sg.out(U_traj, sizeof(R) * T * n * nu));
+    R *dX = static_cast<R *>(sg.out(X_traj, sizeof(R) * (T + 1) * n * nx));
+    int32_t *df = static_cast<int32_t *>(sg.out(flag_min, sizeof(int32_t) * n));
+    if (sg.err != hipSuccess) return sg.fail(h);
+    int rc;
+    if constexpr (std::is_same<R, double>::value) {
+        rc = lmpc_simulate_device(h, N, T, nx, nr, nuprev, F, G, dx, dr, du, dU, dX, df, warm, nullptr);
+        if (rc == LMPC_OK) sg.ok(hipDeviceSynchronize(), "hipDeviceSynchronize");
+    } else {
+        rc = lmpc_simulate_f32_device(h, N, T, nx, nr, nuprev, F, G, dx, dr, du, dU, dX, df, warm, nullptr);
+    }
+    if (rc == LMPC_OK && !(sg.err == hipSuccess && sg.download_all())) return sg.fail(h);
+    return rc;
+}
+}  // namespace
+
 extern "C" {
 
 // per-scenario kept closed-loop state of the wavefront path (working set + factorisation, lmpc_wave_kernel.hpp): makes
@@ -108,6 +158,7 @@ int lmpc_simulate_device(lmpc_handle *h, int64_t N, int T, int nx, int nr, int n
     // in registers through its unconstrained steps and only the steps that need iterations go through the
     // iterating kernel, one round per such step.  The host reads the work-list counters after every
     // streaming pass (one stream synchronisation per round) and stops when nothing is queued any more.
+    const HandleLoan loan(h);
     if (asyncLoop) {
         h->asyncX = x; h->asyncR = r; h->asyncUp = nuprev > 0 ? uprev : nullptr;
         HIP_TRY(h, hipMemcpyAsync(h->dC + h->L.oFG, F, sizeof(double) * nx * nx, hipMemcpyHostToDevice, st));
@@ -115,21 +166,16 @@ int lmpc_simulate_device(lmpc_handle *h, int64_t N, int T, int nx, int nr, int n
         if (!h->simK) HIP_TRY(h, hipMalloc(&h->simK, sizeof(int32_t) * (size_t)h->simCap));
         HIP_TRY(h, hipMemsetAsync(h->simK, 0, sizeof(int32_t) * (size_t)N, st));
         if (warm) HIP_TRY(h, hipMemsetAsync(h->simAct, 0, sizeof(uint64_t) * (size_t)N * (size_t)h->P.words(), st));   // first step is cold
-        const bool prof = h->prof;
         h->prof = false;
         h->asyncT = T;
         h->L.sim = SimFuse{h->simFG, h->simTheta, flag_min, nullptr, nx, nu, nr, nuprev, 0, h->simK, U_traj, X_traj,
                            (long long)N};
-        h->keepOn = false; h->raWarm = warm != 0;
+        h->raWarm = warm != 0;
         if (h->useWave && runAhead && warm && T > 1 && wave_first_pass_cap(h, N) > 0) {
             // (a first pass at a smaller capacity is in sight: it writes every scenario's state out after each step, so
             // that a step which outgrows it restarts exactly where the step-synchronous loop would)
             const int rck = ensure_keep(h, N, st);
-            if (rck != LMPC_OK) {                     // (leave the handle as an ordinary solve expects it)
-                h->L.sim = SimFuse{}; h->waveSim = WaveSim{}; h->raWarm = false; h->asyncT = 0; h->prof = prof;
-                h->asyncX = h->asyncR = h->asyncUp = nullptr;
-                return rck;
-            }
+            if (rck != LMPC_OK) return rck;
         }
         if (h->useWave) h->waveSim = WaveSim{h->simFG, h->simK, U_traj, X_traj, flag_min, nx, nu, nr, nuprev, (long long)N, -1, runAhead ? T : 0};
         constexpr int kBurst = 2;   // steps a scenario of a (short) work list may run ahead before it is parked
@@ -192,14 +238,8 @@ int lmpc_simulate_device(lmpc_handle *h, int64_t N, int T, int nx, int nr, int n
         if (rc == LMPC_OK && !drained)
             rc = fail(h, LMPC_ERR_HIP, "lmpc_simulate: the scenario-asynchronous loop hit its pass limit with scenarios "
                                        "still queued (lmpc_set_option(\"sim_async\", 0) runs the step-synchronous loop)");
-        h->asyncPhase = 0;
-        h->asyncListIn = h->asyncCntIn = nullptr;
         // the last streaming pass queued nothing, so no iterating kernel cleared the other counter set
         if (h->dCount) { hipMemsetAsync(h->dCount, 0, sizeof(int32_t) * 3 * kShards * kCountStride, st); h->countSet = 0; }
-        h->L.sim = SimFuse{};
-        h->waveSim = WaveSim{};
-        h->keepOn = false; h->raWarm = false;
-        h->prof = prof;
         if (rc != LMPC_OK) return rc;
         hipLaunchKernelGGL(unpack_theta_kernel, dim3(grid), dim3(256), 0, st, h->simTheta, x, nuprev > 0 ? uprev : nullptr,
                            nx, nr, nuprev, (long long)N);
@@ -221,7 +261,6 @@ int lmpc_simulate_device(lmpc_handle *h, int64_t N, int T, int nx, int nr, int n
                         warm ? h->simAct : nullptr, wm, st);
             std::swap(cur, nxt);
         }
-        h->L.sim = SimFuse{};
         if (rc != LMPC_OK) return rc;
         hipLaunchKernelGGL(unpack_theta_kernel, dim3(grid), dim3(256), 0, st, cur, x, nuprev > 0 ? uprev : nullptr, nx,
                            nr, nuprev, (long long)N);
@@ -233,7 +272,6 @@ int lmpc_simulate_device(lmpc_handle *h, int64_t N, int T, int nx, int nr, int n
     // starts from the factor as it stands -- what DAQP_WARMSTART means in libdaqp, whose workspace is simply not
     // cleared between two calls (codegen/mpc_update_qp.c:44-54) -- instead of re-appending the rows of the mask one
     // by one.  Option "sim_keep_factor" 0 (or no memory for it): the mask-based warm start of the other paths.
-    h->keepOn = false;
     if (h->useWave && !h->avi && warm && !h->bnb && h->simKeep && T > 1) {
         const int rck = ensure_keep(h, N, st);
         if (rck != LMPC_OK) return rck;
@@ -254,9 +292,6 @@ int lmpc_simulate_device(lmpc_handle *h, int64_t N, int T, int nx, int nr, int n
             rc = api_launch(h, N, h->simTheta, U_traj ? U_traj + (size_t)k * N * nu : nullptr, nullptr, nullptr,
                         warm ? h->simAct : nullptr, wm, st);
         }
-        h->L.sim = SimFuse{};
-        h->waveSim = WaveSim{};
-        h->keepOn = false;
         if (rc != LMPC_OK) return rc;
         hipLaunchKernelGGL(unpack_theta_kernel, dim3(grid), dim3(256), 0, st, h->simTheta, x, nuprev > 0 ? uprev : nullptr,
                            nx, nr, nuprev, (long long)N);
@@ -268,16 +303,15 @@ int lmpc_simulate_device(lmpc_handle *h, int64_t N, int T, int nx, int nr, int n
         // codegen/mpc_update_qp.c:44-47); the first step is always cold
         const uint64_t *wm = (warm && k > 0) ? h->simAct : nullptr;
         int rc = api_launch(h, N, h->simTheta, h->simU, h->simFlag, nullptr, warm ? h->simAct : nullptr, wm, st);
-        if (rc != LMPC_OK) { h->keepOn = false; return rc; }
+        if (rc != LMPC_OK) return rc;
         const bool last = k == T - 1;
         hipLaunchKernelGGL(plant_theta_kernel<double>, dim3(grid), dim3(256), 0, st, h->simTheta, h->P.nth, nr, h->simU,
                            h->simFlag, h->simFG, nx, nu, nuprev,
                            X_traj ? X_traj + (size_t)(k + 1) * N * nx : nullptr,
                            U_traj ? U_traj + (size_t)k * N * nu : nullptr, flag_min, k == 0 ? 1 : 0,
                            last ? x : nullptr, (last && nuprev > 0) ? uprev : nullptr, (long long)N);
-        if (hipGetLastError() != hipSuccess) { h->keepOn = false; return fail(h, LMPC_ERR_HIP, "lmpc_simulate_device: plant step launch"); }
+        if (hipGetLastError() != hipSuccess) return fail(h, LMPC_ERR_HIP, "lmpc_simulate_device: plant step launch");
     }
-    h->keepOn = false;
     return LMPC_OK;
 }
 
@@ -291,9 +325,7 @@ int lmpc_simulate_f32_device(lmpc_handle *h, int64_t N, int T, int nx, int nr, i
         return fail(h, LMPC_ERR_BADARG, "lmpc_simulate_f32_device: theta = [x; r; uprev] must match the handle "
                                         "(nx + nr + nuprev == nth, nout == nu, nx <= 32)");
     if (N == 0 || T == 0) return LMPC_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(h, LMPC_ERR_NOGPU, "lmpc: no HIP device available (this library has no CPU path)");
+    LMPC_NEED_DEVICE(h);
     LMPC_ENTER_DEVICE(h);
     int rc = api_ensure_f32(h);
     if (rc != LMPC_OK) return rc;
@@ -324,52 +356,6 @@ int lmpc_simulate_f32_device(lmpc_handle *h, int64_t N, int T, int nx, int nr, i
     return LMPC_OK;
 }
 
-int lmpc_simulate_f32(lmpc_handle *h, int64_t N, int T, int nx, int nr, int nuprev, const double *F, const double *G,
-                      float *x, const float *r, float *uprev, float *U_traj, float *X_traj, int32_t *flag_min,
-                      int warm) {
-    if (!h) return LMPC_ERR_BADARG;
-    if (N <= 0 || T <= 0) return N < 0 || T < 0 ? LMPC_ERR_BADARG : LMPC_OK;
-    LMPC_ENTER_DEVICE(h);
-    const int nu = h->P.nout;
-    float *dx = nullptr, *dr = nullptr, *du = nullptr, *dU = nullptr, *dX = nullptr;
-    int32_t *df = nullptr;
-    auto cleanup = [&]() { hipFree(dx); hipFree(dr); hipFree(du); hipFree(dU); hipFree(dX); hipFree(df); };
-#define SIMF_TRY(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { cleanup(); \
-        return fail(h, LMPC_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); } } while (0)
-    SIMF_TRY(hipMalloc(&dx, sizeof(float) * (size_t)N * nx));
-    SIMF_TRY(hipMemcpy(dx, x, sizeof(float) * (size_t)N * nx, hipMemcpyHostToDevice));
-    if (r && nr > 0) {
-        SIMF_TRY(hipMalloc(&dr, sizeof(float) * (size_t)N * nr));
-        SIMF_TRY(hipMemcpy(dr, r, sizeof(float) * (size_t)N * nr, hipMemcpyHostToDevice));
-    }
-    if (nuprev > 0) {                                    // NULL = zeros, as in lmpc_simulate
-        SIMF_TRY(hipMalloc(&du, sizeof(float) * (size_t)N * nuprev));
-        if (uprev) SIMF_TRY(hipMemcpy(du, uprev, sizeof(float) * (size_t)N * nuprev, hipMemcpyHostToDevice));
-        else SIMF_TRY(hipMemset(du, 0, sizeof(float) * (size_t)N * nuprev));
-    }
-    if (U_traj) SIMF_TRY(hipMalloc(&dU, sizeof(float) * (size_t)T * N * nu));
-    if (X_traj) SIMF_TRY(hipMalloc(&dX, sizeof(float) * (size_t)(T + 1) * N * nx));
-    if (flag_min) SIMF_TRY(hipMalloc(&df, sizeof(int32_t) * (size_t)N));
-    int rc = lmpc_simulate_f32_device(h, N, T, nx, nr, nuprev, F, G, dx, dr, du, dU, dX, df, warm, nullptr);
-    if (rc != LMPC_OK) { cleanup(); return rc; }
-    SIMF_TRY(hipMemcpy(x, dx, sizeof(float) * (size_t)N * nx, hipMemcpyDeviceToHost));
-    if (du && uprev) SIMF_TRY(hipMemcpy(uprev, du, sizeof(float) * (size_t)N * nuprev, hipMemcpyDeviceToHost));
-    if (dU) SIMF_TRY(hipMemcpy(U_traj, dU, sizeof(float) * (size_t)T * N * nu, hipMemcpyDeviceToHost));
-    if (dX) SIMF_TRY(hipMemcpy(X_traj, dX, sizeof(float) * (size_t)(T + 1) * N * nx, hipMemcpyDeviceToHost));
-    if (df) SIMF_TRY(hipMemcpy(flag_min, df, sizeof(int32_t) * (size_t)N, hipMemcpyDeviceToHost));
-#undef SIMF_TRY
-    cleanup();
-    return LMPC_OK;
-}
-
-namespace {
-ThetaBlock to_block(const lmpc_block *b) {
-    ThetaBlock t{nullptr, 0, 0, 1, 0, 0};
-    if (b) { t.src = b->src; t.stride = b->stride; t.w = b->w; t.T = b->T > 0 ? b->T : 1; t.k0 = b->k0; t.H = b->H; }
-    return t;
-}
-}  // namespace
-
 int lmpc_form_parameter_device(lmpc_handle *h, int64_t N, double *theta, const double *x, int nx,
                                const lmpc_block *r, const lmpc_block *d, const double *uprev, int nuprev,
                                const lmpc_block *p, void *stream) {
@@ -382,9 +368,7 @@ int lmpc_form_parameter_device(lmpc_handle *h, int64_t N, double *theta, const d
         return fail(h, LMPC_ERR_BADARG, "lmpc_form_parameter_device: blocks do not add up to the handle's nth = " +
                                             std::to_string(h->P.nth));
     if (N == 0 || h->P.nth == 0) return LMPC_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(h, LMPC_ERR_NOGPU, "lmpc: no HIP device available (this library has no CPU path)");
+    LMPC_NEED_DEVICE(h);
     LMPC_ENTER_DEVICE(h);
     const long long total = (long long)N * h->P.nth;
     hipLaunchKernelGGL(form_parameter_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
@@ -404,9 +388,7 @@ int lmpc_simulate_ref_device(lmpc_handle *h, int64_t N, int T, int nx, const lmp
         return fail(h, LMPC_ERR_BADARG, "lmpc_simulate_ref_device: theta = [x; r-block; uprev] must match the handle "
                                         "(nx + width(r) + nuprev == nth, nout == nu, nx <= 32)");
     if (N == 0 || T == 0) return LMPC_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(h, LMPC_ERR_NOGPU, "lmpc: no HIP device available (this library has no CPU path)");
+    LMPC_NEED_DEVICE(h);
     LMPC_ENTER_DEVICE(h);
     hipStream_t st = (hipStream_t)stream;
     { const int rce = api_ensure_sim(h, N); if (rce != LMPC_OK) return rce; }
@@ -423,17 +405,11 @@ int lmpc_simulate_ref_device(lmpc_handle *h, int64_t N, int T, int nx, const lmp
         const uint64_t *wm = (warm && k > 0) ? h->simAct : nullptr;
         int rc = api_launch(h, N, h->simTheta, h->simU, h->simFlag, nullptr, warm ? h->simAct : nullptr, wm, st);
         if (rc != LMPC_OK) return rc;
-        {
-#define LMPC_PK(NX) hipLaunchKernelGGL(plant_kernel<NX>, dim3(grid), dim3(256), 0, st, x, uprev, h->simU, h->simFlag, h->simFG, nx, \
-                           nu, nuprev, X_traj ? X_traj + (size_t)(k + 1) * N * nx : nullptr, \
-                           U_traj ? U_traj + (size_t)k * N * nu : nullptr, flag_min, k == 0 ? 1 : 0, (long long)N)
-            switch (nx) {
-                case 1: LMPC_PK(1); break; case 2: LMPC_PK(2); break; case 3: LMPC_PK(3); break; case 4: LMPC_PK(4); break;
-                case 5: LMPC_PK(5); break; case 6: LMPC_PK(6); break; case 7: LMPC_PK(7); break; case 8: LMPC_PK(8); break;
-                default: LMPC_PK(0); break;
-            }
-#undef LMPC_PK
-        }
+        dispatch_nx(nx, [&](auto NX) {
+            hipLaunchKernelGGL(plant_kernel<decltype(NX)::value>, dim3(grid), dim3(256), 0, st, x, uprev, h->simU, h->simFlag, h->simFG, nx,
+                               nu, nuprev, X_traj ? X_traj + (size_t)(k + 1) * N * nx : nullptr,
+                               U_traj ? U_traj + (size_t)k * N * nu : nullptr, flag_min, k == 0 ? 1 : 0, (long long)N);
+        });
         HIP_TRY(h, hipGetLastError());
     }
     return LMPC_OK;
@@ -449,9 +425,7 @@ int lmpc_set_parameter_layout(lmpc_handle *h, const lmpc_param_layout *l) {
     if (l->n_state + l->n_reference + l->n_disturbance + l->n_control_prev + l->n_affine_parameter != h->P.nth)
         return fail(h, LMPC_ERR_BADARG, "lmpc_set_parameter_layout: blocks do not add up to the handle's nth = " +
                                             std::to_string(h->P.nth));
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(h, LMPC_ERR_NOGPU, "lmpc: no HIP device available (this library has no CPU path)");
+    LMPC_NEED_DEVICE(h);
     LMPC_ENTER_DEVICE(h);
     hipFree(h->ccT2S);
     h->ccT2S = nullptr;
@@ -474,9 +448,7 @@ int lmpc_compute_control_device(lmpc_handle *h, int64_t N, double *control, cons
     if (N < 0 || (N > 0 && (!control || (h->ccNx > 0 && !state))))
         return fail(h, LMPC_ERR_BADARG, "lmpc_compute_control: NULL control/state or negative N");
     if (N == 0) return LMPC_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(h, LMPC_ERR_NOGPU, "lmpc: no HIP device available (this library has no CPU path)");
+    LMPC_NEED_DEVICE(h);
     LMPC_ENTER_DEVICE(h);
     hipStream_t st = (hipStream_t)stream;
     const size_t w = (size_t)h->P.words();
@@ -492,12 +464,12 @@ int lmpc_compute_control_device(lmpc_handle *h, int64_t N, double *control, cons
     // five arrays itself (GatherArgs) and hands the records of the problems that need iterations to the
     // iterating kernel through ccTheta -- no theta buffer is written or read for the others
     if (api_will_screen(h, N) && h->ccNph == 0 && h->ccFused) {
+        const HandleLoan loan(h);
         h->L.gat = GatherArgs{state, reference, disturbance, control, affine_parameter, h->ccTheta,
                               h->ccNx, h->ccNr, h->ccNd, h->ccNup, h->ccNp, h->P.nout};
         const bool use_warm_g = warm && h->ccWarmN == N;
         int rcg = api_launch(h, N, h->ccTheta, control, exitflag ? exitflag : h->ccFlag, nullptr, warm ? h->ccAct : nullptr,
                          use_warm_g ? h->ccAct : nullptr, st);
-        h->L.gat = GatherArgs{};
         if (rcg != LMPC_OK) return rcg;
         h->ccWarmN = warm ? N : -1;
         return LMPC_OK;
@@ -527,9 +499,7 @@ int lmpc_compute_control(lmpc_handle *h, int64_t N, double *control, const doubl
     if (N < 0 || (N > 0 && (!control || (h->ccNx > 0 && !state))))
         return fail(h, LMPC_ERR_BADARG, "lmpc_compute_control: NULL control/state or negative N");
     if (N == 0) return LMPC_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(h, LMPC_ERR_NOGPU, "lmpc: no HIP device available (this library has no CPU path)");
+    LMPC_NEED_DEVICE(h);
     LMPC_ENTER_DEVICE(h);
     const int nu = h->P.nout;
     const size_t wr = (size_t)h->ccNr * (h->ccNph > 0 ? h->ccNph : 1);
@@ -584,25 +554,18 @@ int lmpc_compute_control(lmpc_handle *h, int64_t N, double *control, const doubl
         HIP_TRY(h, hipMalloc(&h->ccStageFlag, sizeof(int32_t) * (size_t)N));
         h->ccStageCap = N; h->ccStagePer = per;
     }
-    double *cur = h->ccStage;
-    auto up = [&](const double *src, size_t w, double **dst) -> hipError_t {
-        *dst = nullptr;
-        if (!src || w == 0) return hipSuccess;
-        *dst = cur;
-        cur += (size_t)N * w;
-        return hipMemcpy(*dst, src, sizeof(double) * (size_t)N * w, hipMemcpyHostToDevice);
+    Staging sg(h->ccStage);                            // carved from the handle's block: nothing is allocated per call
+    auto up = [&](const double *src, size_t w) {
+        return w ? static_cast<double *>(sg.in(src, sizeof(double) * (size_t)N * w)) : nullptr;
     };
-    double *dc, *ds, *dr, *dd, *dp;
-    HIP_TRY(h, up(control, (size_t)nu, &dc));
-    HIP_TRY(h, up(state, (size_t)h->ccNx, &ds));
-    HIP_TRY(h, up(reference, wr, &dr));
-    HIP_TRY(h, up(disturbance, (size_t)h->ccNd, &dd));
-    HIP_TRY(h, up(affine_parameter, (size_t)h->ccNp, &dp));
-    int rc = lmpc_compute_control_device(h, N, dc, ds, dr, dd, dp, h->ccStageFlag, warm, nullptr);
-    if (rc != LMPC_OK) return rc;
-    HIP_TRY(h, hipMemcpy(control, dc, sizeof(double) * (size_t)N * nu, hipMemcpyDeviceToHost));
-    if (exitflag) HIP_TRY(h, hipMemcpy(exitflag, h->ccStageFlag, sizeof(int32_t) * (size_t)N, hipMemcpyDeviceToHost));
-    return LMPC_OK;
+    double *dc = static_cast<double *>(sg.out(control, sizeof(double) * (size_t)N * nu, true));
+    double *ds = up(state, (size_t)h->ccNx), *dr = up(reference, wr), *dd = up(disturbance, (size_t)h->ccNd),
+           *dp = up(affine_parameter, (size_t)h->ccNp);
+    sg.out_from(exitflag, h->ccStageFlag, sizeof(int32_t) * (size_t)N);
+    if (sg.err != hipSuccess) return sg.fail(h);
+    const int rc = lmpc_compute_control_device(h, N, dc, ds, dr, dd, dp, h->ccStageFlag, warm, nullptr);
+    if (rc == LMPC_OK && !sg.download_all()) return sg.fail(h);
+    return rc;
 }
 
 int lmpc_compute_control_observer_device(lmpc_handle *h, int64_t N, double *control, const double *observer_state,
@@ -616,9 +579,7 @@ int lmpc_compute_control_observer_device(lmpc_handle *h, int64_t N, double *cont
         return fail(h, LMPC_ERR_BADARG, "lmpc_compute_control_observer: NULL array, negative N, or more measured "
                                         "disturbances than the layout's n_disturbance");
     if (N == 0) return LMPC_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(h, LMPC_ERR_NOGPU, "lmpc: no HIP device available (this library has no CPU path)");
+    LMPC_NEED_DEVICE(h);
     LMPC_ENTER_DEVICE(h);
     const size_t per = (size_t)h->ccNx + h->ccNd;
     if (N > h->ccObsCap) {
@@ -644,9 +605,7 @@ int lmpc_set_observer(lmpc_handle *h, const lmpc_observer *o) {
     if (o->n_state <= 0 || o->n_state > 32 || o->n_control < 0 || o->n_disturbance < 0 || o->n_measurement <= 0 ||
         !o->plant_dynamics || !o->measurement_function || !o->k_transpose)
         return fail(h, LMPC_ERR_BADARG, "lmpc_set_observer: sizes (1 <= n_state <= 32, n_measurement >= 1) or NULL array");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(h, LMPC_ERR_NOGPU, "lmpc: no HIP device available (this library has no CPU path)");
+    LMPC_NEED_DEVICE(h);
     LMPC_ENTER_DEVICE(h);
     const size_t nd_ = (size_t)o->n_state * (1 + o->n_state + o->n_control + o->n_disturbance);
     const size_t nm_ = (size_t)o->n_measurement * (1 + o->n_state + o->n_disturbance);
@@ -669,14 +628,10 @@ int lmpc_predict_state_device(lmpc_handle *h, int64_t N, double *state, const do
         return fail(h, LMPC_ERR_BADARG, "lmpc_predict_state: NULL state/control or negative N");
     if (N == 0) return LMPC_OK;
     LMPC_ENTER_DEVICE(h);
-#define LMPC_PS(NX) hipLaunchKernelGGL(predict_state_kernel<NX>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, \
-        (hipStream_t)stream, state, control, disturbance, h->obsC, h->obsNx, h->obsNu, h->obsNd, (long long)N)
-    switch (h->obsNx) {
-        case 1: LMPC_PS(1); break; case 2: LMPC_PS(2); break; case 3: LMPC_PS(3); break; case 4: LMPC_PS(4); break;
-        case 5: LMPC_PS(5); break; case 6: LMPC_PS(6); break; case 7: LMPC_PS(7); break; case 8: LMPC_PS(8); break;
-        default: LMPC_PS(0); break;
-    }
-#undef LMPC_PS
+    dispatch_nx(h->obsNx, [&](auto NX) {
+        hipLaunchKernelGGL(predict_state_kernel<decltype(NX)::value>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0,
+                           (hipStream_t)stream, state, control, disturbance, h->obsC, h->obsNx, h->obsNu, h->obsNd, (long long)N);
+    });
     HIP_TRY(h, hipGetLastError());
     return LMPC_OK;
 }
@@ -691,15 +646,11 @@ int lmpc_correct_state_device(lmpc_handle *h, int64_t N, double *state, const do
     LMPC_ENTER_DEVICE(h);
     const size_t nd_ = (size_t)h->obsNx * (1 + h->obsNx + h->obsNu + h->obsNd);
     const size_t nm_ = (size_t)h->obsNy * (1 + h->obsNx + h->obsNd);
-#define LMPC_CS(NX) hipLaunchKernelGGL(correct_state_kernel<NX>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, \
-        (hipStream_t)stream, state, measurement, disturbance, h->obsC + nd_, h->obsC + nd_ + nm_, h->obsNx, \
-        h->obsNy, h->obsNd, (long long)N)
-    switch (h->obsNx) {
-        case 1: LMPC_CS(1); break; case 2: LMPC_CS(2); break; case 3: LMPC_CS(3); break; case 4: LMPC_CS(4); break;
-        case 5: LMPC_CS(5); break; case 6: LMPC_CS(6); break; case 7: LMPC_CS(7); break; case 8: LMPC_CS(8); break;
-        default: LMPC_CS(0); break;
-    }
-#undef LMPC_CS
+    dispatch_nx(h->obsNx, [&](auto NX) {
+        hipLaunchKernelGGL(correct_state_kernel<decltype(NX)::value>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0,
+                           (hipStream_t)stream, state, measurement, disturbance, h->obsC + nd_, h->obsC + nd_ + nm_, h->obsNx,
+                           h->obsNy, h->obsNd, (long long)N);
+    });
     HIP_TRY(h, hipGetLastError());
     return LMPC_OK;
 }
@@ -711,31 +662,17 @@ int observer_host(lmpc_handle *h, int64_t N, double *state, const double *in, in
     if (!h->obsC) return fail(h, LMPC_ERR_BADARG, "lmpc observer: call lmpc_set_observer first");
     if (N < 0 || (N > 0 && (!state || (win > 0 && !in)))) return fail(h, LMPC_ERR_BADARG, "lmpc observer: NULL array or negative N");
     if (N == 0) return LMPC_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(h, LMPC_ERR_NOGPU, "lmpc: no HIP device available (this library has no CPU path)");
+    LMPC_NEED_DEVICE(h);
     LMPC_ENTER_DEVICE(h);
-    double *ds = nullptr, *di = nullptr, *dd = nullptr;
-    auto cleanup = [&]() { hipFree(ds); hipFree(di); hipFree(dd); };
-#define OB_TRY(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { cleanup(); \
-        return fail(h, LMPC_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); } } while (0)
-    const size_t nx = (size_t)h->obsNx, nd = (size_t)h->obsNd;
-    OB_TRY(hipMalloc(&ds, sizeof(double) * N * nx));
-    OB_TRY(hipMemcpy(ds, state, sizeof(double) * N * nx, hipMemcpyHostToDevice));
-    if (win > 0) {
-        OB_TRY(hipMalloc(&di, sizeof(double) * N * win));
-        OB_TRY(hipMemcpy(di, in, sizeof(double) * N * win, hipMemcpyHostToDevice));
-    }
-    if (dist && nd > 0) {
-        OB_TRY(hipMalloc(&dd, sizeof(double) * N * nd));
-        OB_TRY(hipMemcpy(dd, dist, sizeof(double) * N * nd, hipMemcpyHostToDevice));
-    }
-    int rc = predict ? lmpc_predict_state_device(h, N, ds, di, dd, nullptr) : lmpc_correct_state_device(h, N, ds, di, dd, nullptr);
-    if (rc != LMPC_OK) { cleanup(); return rc; }
-    OB_TRY(hipMemcpy(state, ds, sizeof(double) * N * nx, hipMemcpyDeviceToHost));
-#undef OB_TRY
-    cleanup();
-    return LMPC_OK;
+    const size_t n = (size_t)N, nx = (size_t)h->obsNx, nd = (size_t)h->obsNd;
+    Staging sg;
+    double *ds = static_cast<double *>(sg.out(state, sizeof(double) * n * nx, true));
+    double *di = win > 0 ? static_cast<double *>(sg.in(in, sizeof(double) * n * win)) : nullptr;
+    double *dd = nd > 0 ? static_cast<double *>(sg.in(dist, sizeof(double) * n * nd)) : nullptr;
+    if (sg.err != hipSuccess) return sg.fail(h);
+    const int rc = predict ? lmpc_predict_state_device(h, N, ds, di, dd, nullptr) : lmpc_correct_state_device(h, N, ds, di, dd, nullptr);
+    if (rc == LMPC_OK && !sg.download_all()) return sg.fail(h);
+    return rc;
 }
 }  // namespace
 
@@ -750,41 +687,13 @@ int lmpc_correct_state(lmpc_handle *h, int64_t N, double *state, const double *m
 int lmpc_simulate(lmpc_handle *h, int64_t N, int T, int nx, int nr, int nuprev, const double *F, const double *G,
                   double *x, const double *r, double *uprev, double *U_traj, double *X_traj, int32_t *flag_min,
                   int warm) {
-    if (!h) return LMPC_ERR_BADARG;
-    if (N <= 0 || T <= 0) return N < 0 || T < 0 ? LMPC_ERR_BADARG : LMPC_OK;
-    LMPC_ENTER_DEVICE(h);
-    const int nu = h->P.nout;
-    double *dx = nullptr, *dr = nullptr, *du = nullptr, *dU = nullptr, *dX = nullptr;
-    int32_t *df = nullptr;
-    auto cleanup = [&]() { hipFree(dx); hipFree(dr); hipFree(du); hipFree(dU); hipFree(dX); hipFree(df); };
-#define SIM_TRY(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { cleanup(); \
-        return fail(h, LMPC_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); } } while (0)
-    SIM_TRY(hipMalloc(&dx, sizeof(double) * (size_t)N * nx));
-    SIM_TRY(hipMemcpy(dx, x, sizeof(double) * (size_t)N * nx, hipMemcpyHostToDevice));
-    if (r && nr > 0) {
-        SIM_TRY(hipMalloc(&dr, sizeof(double) * (size_t)N * nr));
-        SIM_TRY(hipMemcpy(dr, r, sizeof(double) * (size_t)N * nr, hipMemcpyHostToDevice));
-    }
-    if (nuprev > 0) {
-        SIM_TRY(hipMalloc(&du, sizeof(double) * (size_t)N * nuprev));
-        if (uprev) SIM_TRY(hipMemcpy(du, uprev, sizeof(double) * (size_t)N * nuprev, hipMemcpyHostToDevice));
-        else SIM_TRY(hipMemset(du, 0, sizeof(double) * (size_t)N * nuprev));
-    }
-    if (U_traj) SIM_TRY(hipMalloc(&dU, sizeof(double) * (size_t)T * N * nu));
-    if (X_traj) SIM_TRY(hipMalloc(&dX, sizeof(double) * (size_t)(T + 1) * N * nx));
-    if (flag_min) SIM_TRY(hipMalloc(&df, sizeof(int32_t) * (size_t)N));
-    int rc = lmpc_simulate_device(h, N, T, nx, nr, nuprev, F, G, dx, dr, du, dU, dX, df, warm, nullptr);
-    if (rc == LMPC_OK) {
-        SIM_TRY(hipDeviceSynchronize());
-        SIM_TRY(hipMemcpy(x, dx, sizeof(double) * (size_t)N * nx, hipMemcpyDeviceToHost));
-        if (uprev && nuprev > 0) SIM_TRY(hipMemcpy(uprev, du, sizeof(double) * (size_t)N * nuprev, hipMemcpyDeviceToHost));
-        if (U_traj) SIM_TRY(hipMemcpy(U_traj, dU, sizeof(double) * (size_t)T * N * nu, hipMemcpyDeviceToHost));
-        if (X_traj) SIM_TRY(hipMemcpy(X_traj, dX, sizeof(double) * (size_t)(T + 1) * N * nx, hipMemcpyDeviceToHost));
-        if (flag_min) SIM_TRY(hipMemcpy(flag_min, df, sizeof(int32_t) * (size_t)N, hipMemcpyDeviceToHost));
-    }
-#undef SIM_TRY
-    cleanup();
-    return rc;
+    return simulate_host<double>(h, N, T, nx, nr, nuprev, F, G, x, r, uprev, U_traj, X_traj, flag_min, warm);
+}
+
+int lmpc_simulate_f32(lmpc_handle *h, int64_t N, int T, int nx, int nr, int nuprev, const double *F, const double *G,
+                      float *x, const float *r, float *uprev, float *U_traj, float *X_traj, int32_t *flag_min,
+                      int warm) {
+    return simulate_host<float>(h, N, T, nx, nr, nuprev, F, G, x, r, uprev, U_traj, X_traj, flag_min, warm);
 }
 
 }  // extern "C"

@@ -26,8 +26,7 @@ void avi_fill_settings(lmpc_handle *h) {
 int finalize_avi(lmpc_handle *h) {
     const HostPack &P = h->P;
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(h, LMPC_ERR_NOGPU, "lmpc: no HIP device available (this library has no CPU path)");
+    { const int rcd = need_device(h, &ndev); if (rcd != LMPC_OK) return rcd; }
     if (h->device < 0 || h->device >= ndev) return fail(h, LMPC_ERR_BADARG, "lmpc: bad device ordinal");
     const int cap = P.n + 1 + P.nsoft;
     if (P.n > kAviMaxN || P.m > kAviMaxM || P.m < 1 || cap > kAviMaxCap)

@@ -9,6 +9,7 @@
 #include <cstdint>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/lmpc_hip.h"
@@ -238,6 +239,77 @@ int check_fast_err(lmpc_handle *h);
         if (e__ != hipSuccess)                                                               \
             return lmpc::fail(h, LMPC_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
     } while (0)
+
+// LMPC_OK, or LMPC_ERR_NOGPU with the library's one text for it; `count`: the number of devices, for the callers that
+// go on to check an ordinal (h == nullptr: the text goes where a failed setup's does)
+int need_device(lmpc_handle *h, int *count = nullptr);
+#define LMPC_NEED_DEVICE(h) do { const int rcd__ = lmpc::need_device(h); if (rcd__ != LMPC_OK) return rcd__; } while (0)
+
+// The glue kernels' state count as a template argument: f(std::integral_constant<int, NXT>) with NXT = nx for
+// 1 <= nx <= 8 (compile-time state count), NXT = 0 (run-time nx) for everything else
+template <class F>
+void dispatch_nx(int nx, F &&f) {
+    switch (nx) {
+#define LMPC_NX_CASE(NX) case NX: f(std::integral_constant<int, NX>{}); break;
+        LMPC_NX_CASE(1) LMPC_NX_CASE(2) LMPC_NX_CASE(3) LMPC_NX_CASE(4)
+        LMPC_NX_CASE(5) LMPC_NX_CASE(6) LMPC_NX_CASE(7) LMPC_NX_CASE(8)
+#undef LMPC_NX_CASE
+        default: f(std::integral_constant<int, 0>{}); break;
+    }
+}
+
+// Device copies of the arrays of one host-pointer call, released when the call returns.  A NULL host array gives a
+// NULL device array.  The first HIP error sticks (`err`, `what`): every later request does nothing and returns NULL,
+// so a wrapper asks for all its arrays and tests once.  With an `arena` the arrays are carved from that block, which
+// the caller keeps, instead of being allocated.
+struct Staging {
+    struct Back { void *host; const void *dev; size_t bytes; };
+    std::vector<void *> owned;
+    std::vector<Back> back;
+    char *arena = nullptr;
+    hipError_t err = hipSuccess;
+    const char *what = "";
+    Staging() = default;
+    explicit Staging(void *block) : arena(static_cast<char *>(block)) {}
+    Staging(const Staging &) = delete;
+    Staging &operator=(const Staging &) = delete;
+    ~Staging() { for (void *p : owned) (void)hipFree(p); }
+    bool ok(hipError_t e, const char *call) {
+        if (e != hipSuccess && err == hipSuccess) { err = e; what = call; }
+        return err == hipSuccess;
+    }
+    void *alloc(size_t bytes) {
+        void *p = arena;
+        if (err != hipSuccess) return nullptr;
+        if (arena) { arena += bytes; return p; }
+        if (!ok(hipMalloc(&p, bytes ? bytes : 1), "hipMalloc")) return nullptr;
+        owned.push_back(p);
+        return p;
+    }
+    void *zeros(size_t bytes) {
+        void *p = alloc(bytes);
+        if (p) ok(hipMemset(p, 0, bytes), "hipMemset");
+        return p;
+    }
+    void *in(const void *host, size_t bytes) {
+        void *p = host ? alloc(bytes) : nullptr;
+        if (p) ok(hipMemcpy(p, host, bytes, hipMemcpyHostToDevice), "hipMemcpy");
+        return p;
+    }
+    // an array download_all() copies back: the helper's own (uploaded first with `upload`), or one at `dev`
+    void *out(void *host, size_t bytes, bool upload = false) {
+        void *p = !host ? nullptr : upload ? in(host, bytes) : alloc(bytes);
+        if (p) back.push_back(Back{host, p, bytes});
+        return p;
+    }
+    void out_from(void *host, const void *dev, size_t bytes) { if (host) back.push_back(Back{host, dev, bytes}); }
+    bool download_all() {
+        for (const Back &b : back)
+            if (!ok(hipMemcpy(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost), "hipMemcpy")) break;
+        return err == hipSuccess;
+    }
+    int fail(lmpc_handle *h) const { return lmpc::fail(h, LMPC_ERR_HIP, std::string(what) + ": " + hipGetErrorString(err)); }
+};
 
 // Every entry point works on the handle's GPU and hands the caller's current device back when it returns
 // (a host application with several GPUs keeps its own notion of "current device").

@@ -306,9 +306,7 @@ int solve_host(lmpc_handle *h, size_t rs, int64_t N, const void *theta, void *x,
     if (N < 0 || (N > 0 && (!x || !flag || (h->P.nth > 0 && !theta))))
         return fail(h, LMPC_ERR_BADARG, std::string(who) + ": NULL array or negative N");
     if (N == 0) return LMPC_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(h, LMPC_ERR_NOGPU, "lmpc: no HIP device available (this library has no CPU path)");
+    LMPC_NEED_DEVICE(h);
     LMPC_ENTER_DEVICE(h);
     PinScope pin;
     const HostMode mode = host_mode(pin, h, rs, N, theta, x, flag, iters, active, warm);
@@ -428,8 +426,7 @@ int lmpc_setup_multi(lmpc_multi **out, int n, int m, int ms, int nth, int nout, 
     if (!out) return mfail(nullptr, LMPC_ERR_BADARG, "lmpc_setup_multi: out is NULL");
     *out = nullptr;
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return mfail(nullptr, LMPC_ERR_NOGPU, "lmpc: no HIP device available (this library has no CPU path)");
+    { const int rcd = need_device(nullptr, &ndev); if (rcd != LMPC_OK) return rcd; }
     if (n_devices <= 0) { n_devices = ndev; devices = nullptr; }      // all visible devices
     lmpc_multi *hm = new lmpc_multi();
     // LMPC_MULTI_TRANSPORT=copy: the gather runs as peer copies instead of RCCL pairs (lmpc_multi_set_option

@@ -16,9 +16,6 @@ using namespace lmpc;
 
 namespace {
 
-ScnBlock blk(const lmpc_block &b) {
-    return ScnBlock{b.src, b.stride, b.w, b.T > 0 ? b.T : 1, b.k0, b.H};
-}
 int bwidth(const lmpc_block &b) { return b.w * (b.H > 0 ? b.H : 1); }
 
 // every check that needs no device; `obs`: the dimensions lmpc_set_observer was given, or nullptr.  "" = fine,
@@ -104,31 +101,6 @@ int upload_constants(lmpc_handle *h, const std::vector<double> &v, ScnConst &K, 
     return LMPC_OK;
 }
 
-int need_device(lmpc_handle *h) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(h, LMPC_ERR_NOGPU, "lmpc: no HIP device available (this library has no CPU path)");
-    return LMPC_OK;
-}
-
-template <int NXT>
-void launch_pre(const ScnPre &A, const ScnConst &K, hipStream_t st) {
-    const unsigned grid = (unsigned)((A.n + 255) / 256);
-    hipLaunchKernelGGL(scenario_pre_kernel<NXT>, dim3(grid), dim3(256), sizeof(double) * 256 * (size_t)A.nx, st, A, K);
-}
-template <int NXT>
-void launch_post(const ScnPost &A, const ScnConst &K, bool cost, hipStream_t st) {
-    const unsigned grid = (unsigned)((A.n + 255) / 256);
-    if (cost) hipLaunchKernelGGL((scenario_post_kernel<NXT, true>), dim3(grid), dim3(256), 0, st, A, K);
-    else hipLaunchKernelGGL((scenario_post_kernel<NXT, false>), dim3(grid), dim3(256), 0, st, A, K);
-}
-#define LMPC_SCN_NX(nx, CALL)                                                                                           \
-    switch (nx) {                                                                                                       \
-        case 1: CALL(1); break; case 2: CALL(2); break; case 3: CALL(3); break; case 4: CALL(4); break;                 \
-        case 5: CALL(5); break; case 6: CALL(6); break; case 7: CALL(7); break; case 8: CALL(8); break;                 \
-        default: CALL(0); break;                                                                                        \
-    }
-
 }  // namespace
 
 namespace lmpc {
@@ -161,7 +133,7 @@ int lmpc_simulate_scenario_device(lmpc_handle *h, int64_t N, int T, const lmpc_s
     }
     if (!msg.empty()) return fail(h, LMPC_ERR_BADARG, "lmpc_simulate_scenario_device: " + msg);
     if (N == 0 || T == 0) return LMPC_OK;
-    { const int rcd = need_device(h); if (rcd != LMPC_OK) return rcd; }
+    LMPC_NEED_DEVICE(h);
     LMPC_ENTER_DEVICE(h);
     hipStream_t st = (hipStream_t)stream;
     { const int rce = api_ensure_sim(h, N); if (rce != LMPC_OK) return rce; }
@@ -191,13 +163,14 @@ int lmpc_simulate_scenario_device(lmpc_handle *h, int64_t N, int T, const lmpc_s
     ScnPre A{};
     A.x = x; A.xhat = obs ? xhat : nullptr; A.uprev = uprev; A.theta = h->simTheta;
     A.obs_meas = obs ? h->obsC + obs_nd : nullptr; A.obs_kt = obs ? h->obsC + obs_nd + obs_nm : nullptr;
-    A.r = blk(s->r); A.d = blk(s->d); A.p = blk(s->p); A.noise = blk(s->noise);
+    A.r = to_block(&s->r); A.d = to_block(&s->d); A.p = to_block(&s->p); A.noise = to_block(&s->noise);
     A.nx = nx; A.ny = ny; A.nd = nd; A.nup = nup; A.n = (long long)N;
     ScnPost B{};
     B.x = x; B.xhat = obs ? xhat : nullptr; B.uprev = uprev; B.u = h->simU; B.flag = h->simFlag;
     B.obs_dyn = obs ? h->obsC : nullptr; B.d = A.d; B.r = A.r;
     B.flag_min = flag_min; B.cost = wantCost ? s->cost_out : nullptr; B.viol = wantCost ? s->violation_out : nullptr;
     B.ulast = ulast; B.nx = nx; B.nu = nu; B.nd = nd; B.nup = nup; B.n = (long long)N;
+    const unsigned grid = (unsigned)((N + 255) / 256);
     for (int k = 0; k < T; k++) {
         A.k = k;
         A.r.k0 = A.r.H > 0 ? k + 1 : k;               // simulation.jl:102 get_preview(rs, k, Np) / rs[:, k]
@@ -206,9 +179,9 @@ int lmpc_simulate_scenario_device(lmpc_handle *h, int64_t N, int T, const lmpc_s
         A.y_out = s->Y_traj ? s->Y_traj + (size_t)k * N * ny : nullptr;
         A.xhat_out = s->Xhat_traj ? s->Xhat_traj + (size_t)k * N * nx : nullptr;
         A.d_out = s->D_traj ? s->D_traj + (size_t)k * N * nd : nullptr;
-#define LMPC_PRE(NX) launch_pre<NX>(A, K, st)
-        LMPC_SCN_NX(nx, LMPC_PRE)
-#undef LMPC_PRE
+        dispatch_nx(nx, [&](auto NX) {
+            hipLaunchKernelGGL(scenario_pre_kernel<decltype(NX)::value>, dim3(grid), dim3(256), sizeof(double) * 256 * (size_t)nx, st, A, K);
+        });
         HIP_TRY(h, hipGetLastError());
         // warm start = the previous step's final working set, the first step cold (as lmpc_simulate_ref_device)
         const uint64_t *wm = (s->warm && k > 0) ? h->simAct : nullptr;
@@ -217,9 +190,10 @@ int lmpc_simulate_scenario_device(lmpc_handle *h, int64_t N, int T, const lmpc_s
         B.k = k; B.first = k == 0; B.last = k == T - 1;
         B.xtraj_next = X_traj ? X_traj + (size_t)(k + 1) * N * nx : nullptr;
         B.utraj = U_traj ? U_traj + (size_t)k * N * nu : nullptr;
-#define LMPC_POST(NX) launch_post<NX>(B, K, wantCost, st)
-        LMPC_SCN_NX(nx, LMPC_POST)
-#undef LMPC_POST
+        dispatch_nx(nx, [&](auto NX) {
+            if (wantCost) hipLaunchKernelGGL((scenario_post_kernel<decltype(NX)::value, true>), dim3(grid), dim3(256), 0, st, B, K);
+            else hipLaunchKernelGGL((scenario_post_kernel<decltype(NX)::value, false>), dim3(grid), dim3(256), 0, st, B, K);
+        });
         HIP_TRY(h, hipGetLastError());
     }
     return LMPC_OK;
@@ -240,66 +214,31 @@ int lmpc_simulate_scenario(lmpc_handle *h, int64_t N, int T, const lmpc_scenario
         if (!msg.empty()) return fail(h, LMPC_ERR_BADARG, "lmpc_simulate_scenario: " + msg);
     }
     if (N == 0 || T == 0) return LMPC_OK;
-    { const int rcd = need_device(h); if (rcd != LMPC_OK) return rcd; }
+    LMPC_NEED_DEVICE(h);
     LMPC_ENTER_DEVICE(h);
-    std::vector<void *> owned;
-    auto cleanup = [&]() { for (void *p : owned) hipFree(p); };
-#define SCN_TRY(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { cleanup(); \
-        return fail(h, LMPC_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); } } while (0)
+    Staging sg;
     lmpc_scenario_sim d = *s;
-    const int nx = s->nx, nu = s->nu, nd = s->nd, ny = s->ny, nup = s->nuprev;
-    auto dev_alloc = [&](size_t cnt, void **out) -> hipError_t {
-        const hipError_t e = hipMalloc(out, cnt ? cnt : 1);
-        if (e == hipSuccess) owned.push_back(*out);
-        return e;
-    };
+    const size_t nx = (size_t)s->nx, nu = (size_t)s->nu, nd = (size_t)s->nd, ny = (size_t)s->ny, nup = (size_t)s->nuprev;
+    const size_t n = (size_t)N, R = sizeof(double);
     // trajectories: one matrix per scenario (stride apart) or one shared matrix
-    lmpc_block *bs[4] = {&d.r, &d.d, &d.p, &d.noise};
-    for (lmpc_block *b : bs) {
-        if (!b->src || b->w <= 0) { b->src = nullptr; continue; }
-        const size_t cnt = b->stride > 0 ? (size_t)(N - 1) * (size_t)b->stride + (size_t)b->w * b->T : (size_t)b->w * b->T;
-        void *p = nullptr;
-        SCN_TRY(dev_alloc(sizeof(double) * cnt, &p));
-        SCN_TRY(hipMemcpy(p, b->src, sizeof(double) * cnt, hipMemcpyHostToDevice));
-        b->src = static_cast<const double *>(p);
+    for (lmpc_block *b : {&d.r, &d.d, &d.p, &d.noise}) {
+        const size_t cnt = (b->stride > 0 ? (n - 1) * (size_t)b->stride : 0) + (size_t)b->w * b->T;
+        b->src = b->src && b->w > 0 ? static_cast<const double *>(sg.in(b->src, R * cnt)) : nullptr;
     }
-    struct Out { void *host; void *dev; size_t bytes; };
-    std::vector<Out> outs;
-    auto io = [&](void *host, size_t bytes, bool in, void **devp) -> hipError_t {
-        *devp = nullptr;
-        if (!host) return hipSuccess;
-        hipError_t e = dev_alloc(bytes, devp);
-        if (e != hipSuccess) return e;
-        if (in) e = hipMemcpy(*devp, host, bytes, hipMemcpyHostToDevice);
-        outs.push_back(Out{host, *devp, bytes});
-        return e;
-    };
-    void *dx, *dxh, *dup = nullptr, *dU, *dX, *dfm, *dY, *dYm, *dXh, *dD, *dco, *dvo;
-    SCN_TRY(io(x, sizeof(double) * (size_t)N * nx, true, &dx));
-    SCN_TRY(io(xhat, sizeof(double) * (size_t)N * nx, true, &dxh));
-    if (nup > 0) {                                     // NULL = zeros, as in lmpc_simulate
-        if (uprev) SCN_TRY(io(uprev, sizeof(double) * (size_t)N * nup, true, &dup));
-        else { SCN_TRY(dev_alloc(sizeof(double) * (size_t)N * nup, &dup)); SCN_TRY(hipMemset(dup, 0, sizeof(double) * (size_t)N * nup)); }
-    }
-    SCN_TRY(io(U_traj, sizeof(double) * (size_t)T * N * nu, false, &dU));
-    SCN_TRY(io(X_traj, sizeof(double) * (size_t)(T + 1) * N * nx, false, &dX));
-    SCN_TRY(io(flag_min, sizeof(int32_t) * (size_t)N, false, &dfm));
-    SCN_TRY(io(s->Y_traj, sizeof(double) * (size_t)T * N * ny, false, &dY));
-    SCN_TRY(io(s->Ym_traj, sizeof(double) * (size_t)T * N * ny, false, &dYm));
-    SCN_TRY(io(s->Xhat_traj, sizeof(double) * (size_t)T * N * nx, false, &dXh));
-    SCN_TRY(io(s->D_traj, sizeof(double) * (size_t)T * N * nd, false, &dD));
-    SCN_TRY(io(s->cost_out, sizeof(double) * (size_t)N, false, &dco));
-    SCN_TRY(io(s->violation_out, sizeof(double) * (size_t)N, false, &dvo));
-    d.Y_traj = (double *)dY; d.Ym_traj = (double *)dYm; d.Xhat_traj = (double *)dXh; d.D_traj = (double *)dD;
-    d.cost_out = (double *)dco; d.violation_out = (double *)dvo;
-    const int rc = lmpc_simulate_scenario_device(h, N, T, &d, (double *)dx, (double *)dxh, (double *)dup, (double *)dU,
-                                                 (double *)dX, (int32_t *)dfm, nullptr);
-    if (rc == LMPC_OK) {
-        SCN_TRY(hipDeviceSynchronize());
-        for (const Out &o : outs) SCN_TRY(hipMemcpy(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost));
-    }
-#undef SCN_TRY
-    cleanup();
+    double *dx = (double *)sg.out(x, R * n * nx, true), *dxh = (double *)sg.out(xhat, R * n * nx, true);
+    double *dup = nullptr;                             // NULL = zeros, as in lmpc_simulate
+    if (nup > 0) dup = (double *)(uprev ? sg.out(uprev, R * n * nup, true) : sg.zeros(R * n * nup));
+    double *dU = (double *)sg.out(U_traj, R * T * n * nu), *dX = (double *)sg.out(X_traj, R * (T + 1) * n * nx);
+    int32_t *dfm = (int32_t *)sg.out(flag_min, sizeof(int32_t) * n);
+    d.Y_traj = (double *)sg.out(s->Y_traj, R * T * n * ny);
+    d.Ym_traj = (double *)sg.out(s->Ym_traj, R * T * n * ny);
+    d.Xhat_traj = (double *)sg.out(s->Xhat_traj, R * T * n * nx);
+    d.D_traj = (double *)sg.out(s->D_traj, R * T * n * nd);
+    d.cost_out = (double *)sg.out(s->cost_out, R * n);
+    d.violation_out = (double *)sg.out(s->violation_out, R * n);
+    if (sg.err != hipSuccess) return sg.fail(h);
+    const int rc = lmpc_simulate_scenario_device(h, N, T, &d, dx, dxh, dup, dU, dX, dfm, nullptr);
+    if (rc == LMPC_OK && (!sg.ok(hipDeviceSynchronize(), "hipDeviceSynchronize") || !sg.download_all())) return sg.fail(h);
     return rc;
 }
 
@@ -319,7 +258,7 @@ int lmpc_evaluate_cost_device(lmpc_handle *h, int64_t N, int T, int nx, int nu, 
     else if (N > 0 && T > 0 && (!X || !U || !cost_out)) msg = "X / U / cost_out: NULL";
     if (!msg.empty()) return fail(h, LMPC_ERR_BADARG, "lmpc_evaluate_cost_device: " + msg);
     if (N == 0) return LMPC_OK;
-    { const int rcd = need_device(h); if (rcd != LMPC_OK) return rcd; }
+    LMPC_NEED_DEVICE(h);
     LMPC_ENTER_DEVICE(h);
     hipStream_t st = (hipStream_t)stream;
     std::vector<double> hostC;
@@ -327,8 +266,7 @@ int lmpc_evaluate_cost_device(lmpc_handle *h, int64_t N, int T, int nx, int nu, 
     c.nc = 0; c.Ax = c.Au = c.lb = c.ub = nullptr;
     ScnConst K = pack_constants(hostC, nx, nu, 0, 0, nullptr, nullptr, &c);
     { const int rcu = upload_constants(h, hostC, K, st); if (rcu != LMPC_OK) return rcu; }
-    ScnBlock br{nullptr, 0, 0, 1, 0, 0};
-    if (r && r->src && cost->C) br = blk(*r);
+    const ThetaBlock br = to_block(r && r->src && cost->C ? r : nullptr);
     hipLaunchKernelGGL(scenario_cost_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, K, X, U, br, nx, nu, T,
                        cost_out, (long long)N);
     HIP_TRY(h, hipGetLastError());
@@ -349,7 +287,7 @@ int lmpc_constraint_violation_device(lmpc_handle *h, int64_t N, int T, int nx, i
     else if (N > 0 && T > 0 && (!X || !U || (!violation_out && !violation_steps))) msg = "X / U / violation_out: NULL";
     if (!msg.empty()) return fail(h, LMPC_ERR_BADARG, "lmpc_constraint_violation_device: " + msg);
     if (N == 0) return LMPC_OK;
-    { const int rcd = need_device(h); if (rcd != LMPC_OK) return rcd; }
+    LMPC_NEED_DEVICE(h);
     LMPC_ENTER_DEVICE(h);
     hipStream_t st = (hipStream_t)stream;
     std::vector<double> hostC;

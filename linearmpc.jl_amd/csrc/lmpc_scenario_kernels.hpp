@@ -5,24 +5,18 @@
 // stand-alone scoring kernels over stored trajectories (reference src/utils.jl:397-425).
 //
 // Arithmetic: every sum is written with separate multiply and add (__dmul_rn / __dadd_rn: nothing fuses), in the
-// order the public header states, so that (a) the observer steps are predict_state_kernel / correct_state_kernel
-// bit for bit, (b) one plant step is predict_state_kernel on the plant's MPC_PLANT_DYNAMICS array, (c) the
-// in-loop cost / violation equal the stand-alone kernels on the stored trajectories.
+// order the public header states.  The observer steps and the plant step are lmpc_sim_kernels.hpp's dynamics_rows /
+// correct_row, the functions predict_state_kernel / correct_state_kernel are made of; theta's blocks are its
+// ThetaBlock / block_at / block_entry (form_parameter_kernel's); the in-loop cost / violation are the step functions
+// below, which the stand-alone scoring kernels call in the same order.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-namespace lmpc {
+#include "lmpc_sim_kernels.hpp"
 
-// an lmpc_block on the device (the layout of lmpc_sim_kernels.hpp's ThetaBlock): `w` values per column, `T` columns
-// stored column by column, one matrix per scenario `stride` doubles apart or one shared (stride 0); H > 0 = preview
-struct ScnBlock {
-    const double *src;
-    long long stride;
-    int w, T, k0, H;
-    __host__ __device__ int width() const { return w * (H > 0 ? H : 1); }
-};
+namespace lmpc {
 
 // device-side constants of one scenario run, all in one buffer (`c`), offsets in doubles (-1 = absent)
 struct ScnConst {
@@ -32,40 +26,6 @@ struct ScnConst {
     int cAx, cAu, clb, cub;          // constraint rows: Ax nc x nx, Au nc x nu, lb, ub
     int nyc, nc;
 };
-
-// column `col` of a block (clamped to the trajectory, simulation.jl:72,79,87 "hold last"), entry q; NULL = 0
-__device__ __forceinline__ double scn_block_at(const ScnBlock &b, long long i, int col, int q) {
-    if (b.src == nullptr) return 0.0;
-    col = col < b.T ? col : b.T - 1;
-    col = col > 0 ? col : 0;
-    return b.src[i * b.stride + (long long)col * b.w + q];
-}
-
-// rows of an MPC_PLANT_DYNAMICS array applied to xo: predict_state_kernel's sums, term by term
-template <int NXT>
-__device__ __forceinline__ void scn_dynamics(const double *__restrict__ dyn, const double *xo, double *xn, int nx, int nu, int nd,
-                                             const double *__restrict__ u, const ScnBlock &d, long long i, int k) {
-    const int stride = 1 + nx + nu + nd;
-    auto row = [&](int a) -> double {
-        const double *r = dyn + a * stride;
-        double acc = r[0];
-        if constexpr (NXT > 0) {
-#pragma unroll
-            for (int c = 0; c < NXT; c++) acc = __dadd_rn(acc, __dmul_rn(r[1 + c], xo[c]));
-        } else {
-            for (int c = 0; c < nx; c++) acc = __dadd_rn(acc, __dmul_rn(r[1 + c], xo[c]));
-        }
-        for (int l = 0; l < nu; l++) acc = __dadd_rn(acc, __dmul_rn(r[1 + nx + l], u[l]));
-        for (int q = 0; q < nd; q++) acc = __dadd_rn(acc, __dmul_rn(r[1 + nx + nu + q], scn_block_at(d, i, k, q)));
-        return acc;
-    };
-    if constexpr (NXT > 0) {
-#pragma unroll
-        for (int a = 0; a < NXT; a++) xn[a] = row(a);
-    } else {
-        for (int a = 0; a < nx; a++) xn[a] = row(a);
-    }
-}
 
 // sum_j a_j * (sum_l M[j, l] b_l): inner sums from 0 in index order, then the outer one likewise
 __device__ __forceinline__ double scn_quad(const double *__restrict__ M, const double *a, int na, const double *b, int nb) {
@@ -81,14 +41,14 @@ __device__ __forceinline__ double scn_quad(const double *__restrict__ M, const d
 // one step's cost term (NOT halved) of evaluate_cost (utils.jl:403-409):  e'Qe + u'Ru + du'Rr du + x'Su with
 // e = C x - r, added in that order starting from 0; absent weights add nothing.  r == nullptr: zeros.
 __device__ __forceinline__ double scn_step_cost(const ScnConst &K, const double *x, int nx, const double *u, const double *ulast,
-                                                int nu, const ScnBlock &r, long long i, int k) {
+                                                int nu, const ThetaBlock &r, long long i, int k) {
     double c = 0.0;
     if (K.cC >= 0 && K.cQ >= 0) {
         double e[32];
         for (int j = 0; j < K.nyc; j++) {
             double t = 0.0;
             for (int a = 0; a < nx; a++) t = __dadd_rn(t, __dmul_rn(K.c[K.cC + j * nx + a], x[a]));
-            e[j] = __dsub_rn(t, r.w > 0 ? scn_block_at(r, i, k, j) : 0.0);
+            e[j] = __dsub_rn(t, r.w > 0 ? block_at(r, i, k, j) : 0.0);
         }
         c = __dadd_rn(c, scn_quad(K.c + K.cQ, e, K.nyc, e, K.nyc));
     }
@@ -123,15 +83,15 @@ struct ScnPre {
     const double *uprev;              // N x nup
     double *theta;                    // N x nth (out)
     const double *obs_meas, *obs_kt;  // the handle's MPC_MEASUREMENT_FUNCTION / K_TRANSPOSE_OBSERVER
-    ScnBlock r, d, p, noise;        // r.k0 / d.k0 / p.k0: first column of this step's theta block
+    ThetaBlock r, d, p, noise;        // r.k0 / d.k0 / p.k0: first column of this step's theta block
     double *ym_out, *y_out, *xhat_out, *d_out;   // this step's slices of the optional trajectories
     int nx, ny, nd, nup, k;
     long long n;
 };
 
 // PRE kernel of step k.  Phase 1, one lane per scenario: ym_j = h_j + sum_i C_ji x_i + sum_q Dd_jq d_q (+ v_j),
-// y_j = sum_i C_ji x_i + sum_q Dd_jq d_q with an observer (else y = ym), xhat <- correct(xhat, ym, d_k) exactly as
-// correct_state_kernel (else xhat = x), the estimate into LDS.  Phase 2, the workgroup together: its 256 records
+// y_j = sum_i C_ji x_i + sum_q Dd_jq d_q with an observer (else y = ym), xhat <- correct(xhat, ym, d_k) by correct_row,
+// measurement by measurement (else xhat = x), the estimate into LDS.  Phase 2, the workgroup together: its 256 records
 // theta = [xhat; r-block; d-block; uprev; p-block] entry by entry, consecutive lanes on consecutive addresses
 // (form_parameter_kernel's property; a record can be 60+ doubles wide).  Dynamic LDS: 256 * nx doubles.
 template <int NXT>
@@ -143,105 +103,51 @@ __global__ __launch_bounds__(256) void scenario_pre_kernel(ScnPre A, ScnConst K)
     const long long i = base + threadIdx.x;
     if (i < A.n) {
         double xo[NXA], xh[NXA], xn[NXA];
-        if constexpr (NXT > 0) {
-#pragma unroll
-            for (int c = 0; c < NXT; c++) xo[c] = A.x[i * NXT + c];
-        } else {
-            for (int c = 0; c < nx; c++) xo[c] = A.x[i * nx + c];
-        }
+        auto dk = [&](int q) { return block_at(A.d, i, A.k, q); };
+        for_nx<NXT>(nx, [&](int c) { xo[c] = A.x[i * nx + c]; });
         const bool obs = A.xhat != nullptr;
-        if (obs) {
-            if constexpr (NXT > 0) {
-#pragma unroll
-                for (int c = 0; c < NXT; c++) { xh[c] = A.xhat[i * NXT + c]; xn[c] = xh[c]; }
-            } else {
-                for (int c = 0; c < nx; c++) { xh[c] = A.xhat[i * nx + c]; xn[c] = xh[c]; }
-            }
-        } else {
-            if constexpr (NXT > 0) {
-#pragma unroll
-                for (int c = 0; c < NXT; c++) xn[c] = xo[c];
-            } else {
-                for (int c = 0; c < nx; c++) xn[c] = xo[c];
-            }
-        }
+        if (obs) for_nx<NXT>(nx, [&](int c) { xh[c] = A.xhat[i * nx + c]; xn[c] = xh[c]; });
+        else for_nx<NXT>(nx, [&](int c) { xn[c] = xo[c]; });
         const int ms = 1 + nx + A.nd;
         for (int j = 0; j < A.ny; j++) {
             const double *mr = K.c + K.meas + j * ms;
             double ym = mr[0], y = 0.0;
-            if constexpr (NXT > 0) {
-#pragma unroll
-                for (int c = 0; c < NXT; c++) {
-                    const double t = __dmul_rn(mr[1 + c], xo[c]);
-                    ym = __dadd_rn(ym, t); y = __dadd_rn(y, t);
-                }
-            } else {
-                for (int c = 0; c < nx; c++) {
-                    const double t = __dmul_rn(mr[1 + c], xo[c]);
-                    ym = __dadd_rn(ym, t); y = __dadd_rn(y, t);
-                }
-            }
+            for_nx<NXT>(nx, [&](int c) {
+                const double t = __dmul_rn(mr[1 + c], xo[c]);
+                ym = __dadd_rn(ym, t); y = __dadd_rn(y, t);
+            });
             for (int q = 0; q < A.nd; q++) {
-                const double t = __dmul_rn(mr[1 + nx + q], scn_block_at(A.d, i, A.k, q));
+                const double t = __dmul_rn(mr[1 + nx + q], dk(q));
                 ym = __dadd_rn(ym, t); y = __dadd_rn(y, t);
             }
-            if (A.noise.w > 0) ym = __dadd_rn(ym, scn_block_at(A.noise, i, A.k, j));
+            if (A.noise.w > 0) ym = __dadd_rn(ym, block_at(A.noise, i, A.k, j));
             if (A.ym_out) A.ym_out[i * A.ny + j] = ym;
             if (A.y_out) A.y_out[i * A.ny + j] = obs ? y : ym;
-            if (obs) {
-                // correct_state_kernel, row j: innovation against the OBSERVER's model, then the gain
-                const double *orow = A.obs_meas + j * ms;
-                double inno = __dsub_rn(ym, orow[0]);
-                if constexpr (NXT > 0) {
-#pragma unroll
-                    for (int c = 0; c < NXT; c++) inno = __dsub_rn(inno, __dmul_rn(orow[1 + c], xh[c]));
-                } else {
-                    for (int c = 0; c < nx; c++) inno = __dsub_rn(inno, __dmul_rn(orow[1 + c], xh[c]));
-                }
-                for (int q = 0; q < A.nd; q++) inno = __dsub_rn(inno, __dmul_rn(orow[1 + nx + q], scn_block_at(A.d, i, A.k, q)));
-                if constexpr (NXT > 0) {
-#pragma unroll
-                    for (int c = 0; c < NXT; c++) xn[c] = __dadd_rn(xn[c], __dmul_rn(A.obs_kt[j * NXT + c], inno));
-                } else {
-                    for (int c = 0; c < nx; c++) xn[c] = __dadd_rn(xn[c], __dmul_rn(A.obs_kt[j * nx + c], inno));
-                }
-            }
+            // the innovation against the OBSERVER's model, then the gain
+            if (obs) correct_row<NXT>(A.obs_meas + j * ms, A.obs_kt + j * nx, ym, xh, xn, nx, A.nd, dk);
         }
-        if constexpr (NXT > 0) {
-#pragma unroll
-            for (int c = 0; c < NXT; c++) {
-                if (obs) A.xhat[i * NXT + c] = xn[c];
-                if (A.xhat_out) A.xhat_out[i * NXT + c] = xn[c];
-            }
-#pragma unroll
-            for (int c = 0; c < NXT; c++) scn_lds[threadIdx.x * NXT + c] = xn[c];
-        } else {
-            for (int c = 0; c < nx; c++) {
-                if (obs) A.xhat[i * nx + c] = xn[c];
-                if (A.xhat_out) A.xhat_out[i * nx + c] = xn[c];
-                scn_lds[threadIdx.x * nx + c] = xn[c];
-            }
-        }
-        if (A.d_out) for (int q = 0; q < A.nd; q++) A.d_out[i * A.nd + q] = scn_block_at(A.d, i, A.k, q);
+        for_nx<NXT>(nx, [&](int c) {
+            if (obs) A.xhat[i * nx + c] = xn[c];
+            if (A.xhat_out) A.xhat_out[i * nx + c] = xn[c];
+        });
+        for_nx<NXT>(nx, [&](int c) { scn_lds[threadIdx.x * nx + c] = xn[c]; });
+        if (A.d_out) for (int q = 0; q < A.nd; q++) A.d_out[i * A.nd + q] = dk(q);
     }
     __syncthreads();
     const int nr = A.r.width(), ndw = A.d.width(), npw = A.p.width();
     const int nth = nx + nr + ndw + A.nup + npw;
     const long long left = A.n - base;
     const int rows = left < 256 ? (int)left : 256;
-    auto from_block = [&](const ScnBlock &b, long long s, int q) -> double {
-        return scn_block_at(b, s, b.k0 + q / b.w, q % b.w);
-    };
     for (int idx = threadIdx.x; idx < rows * nth; idx += 256) {
         const int sl = idx / nth;
         int e = idx - sl * nth;
         const long long s = base + sl;
         double v;
         if (e < nx) v = scn_lds[sl * nx + e];
-        else if ((e -= nx) < nr) v = from_block(A.r, s, e);
-        else if ((e -= nr) < ndw) v = from_block(A.d, s, e);
+        else if ((e -= nx) < nr) v = block_entry(A.r, s, e);
+        else if ((e -= nr) < ndw) v = block_entry(A.d, s, e);
         else if ((e -= ndw) < A.nup) v = A.uprev[s * A.nup + e];
-        else v = from_block(A.p, s, e - A.nup);
+        else v = block_entry(A.p, s, e - A.nup);
         A.theta[base * nth + idx] = v;
     }
 }
@@ -253,7 +159,7 @@ struct ScnPost {
     const double *u;                  // N x nu: this step's controls
     const int32_t *flag;              // N: this step's exit flags
     const double *obs_dyn;            // the handle's MPC_PLANT_DYNAMICS (observer model)
-    ScnBlock d, r;                  // d: column k acts on the plant; r: column k enters the cost
+    ThetaBlock d, r;                  // d: column k acts on the plant; r: column k enters the cost
     double *xtraj_next, *utraj;       // this step's slices or nullptr
     int32_t *flag_min;
     double *cost, *viol, *ulast;      // running sums (cost NOT halved until the last step) / previous control for du
@@ -262,8 +168,8 @@ struct ScnPost {
 };
 
 // POST kernel of step k, one lane per scenario: running cost / violation on (x_k, u_k) BEFORE the move,
-// xhat <- predict(xhat, u, d_k) exactly as predict_state_kernel, x <- f_offset + F x + G u + Gd d_k by the same
-// row sums on the true plant's array, uprev <- u, trajectories, smallest exit flag.
+// xhat <- predict(xhat, u, d_k) by dynamics_rows on the observer's model, x <- f_offset + F x + G u + Gd d_k by
+// dynamics_rows on the true plant's array, then step_tail: uprev <- u, trajectories, smallest exit flag.
 template <int NXT, bool COST>
 __global__ __launch_bounds__(256) void scenario_post_kernel(ScnPost A, ScnConst K) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -272,13 +178,9 @@ __global__ __launch_bounds__(256) void scenario_post_kernel(ScnPost A, ScnConst 
     const int nx = NXT > 0 ? NXT : A.nx;
     const int nu = A.nu;
     const double *u = A.u + i * nu;
+    auto dk = [&](int q) { return block_at(A.d, i, A.k, q); };
     double xo[NXA], xn[NXA];
-    if constexpr (NXT > 0) {
-#pragma unroll
-        for (int c = 0; c < NXT; c++) xo[c] = A.x[i * NXT + c];
-    } else {
-        for (int c = 0; c < nx; c++) xo[c] = A.x[i * nx + c];
-    }
+    for_nx<NXT>(nx, [&](int c) { xo[c] = A.x[i * nx + c]; });
     if constexpr (COST) {
         if (A.cost) {
             double ul[64];
@@ -300,49 +202,21 @@ __global__ __launch_bounds__(256) void scenario_post_kernel(ScnPost A, ScnConst 
     }
     if (A.xhat) {
         double ho[NXA], hn[NXA];
-        if constexpr (NXT > 0) {
-#pragma unroll
-            for (int c = 0; c < NXT; c++) ho[c] = A.xhat[i * NXT + c];
-        } else {
-            for (int c = 0; c < nx; c++) ho[c] = A.xhat[i * nx + c];
-        }
-        scn_dynamics<NXT>(A.obs_dyn, ho, hn, nx, nu, A.nd, u, A.d, i, A.k);
-        if constexpr (NXT > 0) {
-#pragma unroll
-            for (int c = 0; c < NXT; c++) A.xhat[i * NXT + c] = hn[c];
-        } else {
-            for (int c = 0; c < nx; c++) A.xhat[i * nx + c] = hn[c];
-        }
+        for_nx<NXT>(nx, [&](int c) { ho[c] = A.xhat[i * nx + c]; });
+        dynamics_rows<NXT>(A.obs_dyn, ho, hn, nx, nu, A.nd, u, dk);
+        for_nx<NXT>(nx, [&](int c) { A.xhat[i * nx + c] = hn[c]; });
     }
-    scn_dynamics<NXT>(K.c + K.plant, xo, xn, nx, nu, A.nd, u, A.d, i, A.k);
-    if constexpr (NXT > 0) {
-#pragma unroll
-        for (int a = 0; a < NXT; a++) A.x[i * NXT + a] = xn[a];
-        if (A.xtraj_next) {
-#pragma unroll
-            for (int a = 0; a < NXT; a++) A.xtraj_next[i * NXT + a] = xn[a];
-        }
-    } else {
-        for (int a = 0; a < nx; a++) {
-            A.x[i * nx + a] = xn[a];
-            if (A.xtraj_next) A.xtraj_next[i * nx + a] = xn[a];
-        }
-    }
-    for (int l = 0; l < nu; l++) {
-        if (l < A.nup) A.uprev[i * A.nup + l] = u[l];
-        if (A.utraj) A.utraj[i * nu + l] = u[l];
-    }
-    if (A.flag_min) {
-        const int32_t f = A.flag[i];
-        A.flag_min[i] = A.first ? f : (f < A.flag_min[i] ? f : A.flag_min[i]);
-    }
+    dynamics_rows<NXT>(K.c + K.plant, xo, xn, nx, nu, A.nd, u, dk);
+    for_nx<NXT>(nx, [&](int a) { A.x[i * nx + a] = xn[a]; });
+    if (A.xtraj_next) for_nx<NXT>(nx, [&](int a) { A.xtraj_next[i * nx + a] = xn[a]; });
+    step_tail(i, u, nu, A.uprev + i * A.nup, (double *)nullptr, A.nup, A.utraj, A.flag, A.flag_min, A.first);
 }
 
 // Stand-alone scoring of stored trajectories, one thread per scenario: X step-major (step k's states at
 // X + k * n * nx, i.e. the first T slices of an X_traj), U step-major (T x n x nu).  The same step functions in the
 // same order over k as the loop's POST kernel.  cost / viol: n doubles; viol_steps: T x n or nullptr.
 __global__ __launch_bounds__(256) void scenario_cost_kernel(ScnConst K, const double *__restrict__ X, const double *__restrict__ U,
-                                                            ScnBlock r, int nx, int nu, int T, double *__restrict__ cost, long long n) {
+                                                            ThetaBlock r, int nx, int nu, int T, double *__restrict__ cost, long long n) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     double x[32], u[64], ul[64];

@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/lmpc_hip.h"
+
 namespace lmpc {
 
 __device__ __forceinline__ double sim_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
@@ -37,11 +39,33 @@ struct ThetaBlock {
     int w, T, k0, H;
     __host__ __device__ int width() const { return w * (H > 0 ? H : 1); }
 };
+// the caller's lmpc_block as the kernels take it; NULL = an absent block
+inline ThetaBlock to_block(const lmpc_block *b) {
+    ThetaBlock t{nullptr, 0, 0, 1, 0, 0};
+    if (b) { t.src = b->src; t.stride = b->stride; t.w = b->w; t.T = b->T > 0 ? b->T : 1; t.k0 = b->k0; t.H = b->H; }
+    return t;
+}
+
+// entry q of column `col` of a block for scenario i; the column clamped to the trajectory ("hold last"), NULL = 0
+__device__ __forceinline__ double block_at(const ThetaBlock &b, long long i, int col, int q) {
+    if (b.src == nullptr) return 0.0;
+    col = col < b.T ? col : b.T - 1;
+    col = col > 0 ? col : 0;
+    return b.src[i * b.stride + (long long)col * b.w + q];
+}
+// entry q (< width()) of the block as it enters theta: the columns from k0 on, one after the other
+__device__ __forceinline__ double block_entry(const ThetaBlock &b, long long i, int q) {
+    return block_at(b, i, b.k0 + q / b.w, q % b.w);
+}
+
+// (The kernels that are not templates are `inline`: this header is part of two translation units.  The compiler takes
+// the linkage from it and says that it ignores the inlining hint.)
+#pragma clang diagnostic ignored "-Wcuda-compat"
 
 // theta_i = [x_i ; r-block ; d-block ; uprev_i ; p-block]   (reference explicit.jl:54-63 form_parameter
 // after format_reference / format_disturbance / format_affine_parameters, utils.jl:78-261);
 // one thread per entry of theta, consecutive threads write consecutive addresses.
-__global__ __launch_bounds__(256) void form_parameter_kernel(
+inline __global__ __launch_bounds__(256) void form_parameter_kernel(
     double *__restrict__ theta, const double *__restrict__ x, int nx, ThetaBlock r, ThetaBlock d,
     const double *__restrict__ uprev, int nup, ThetaBlock p, long long n) {
     const int nr = r.width(), nd = d.width(), npp = p.width();
@@ -50,19 +74,12 @@ __global__ __launch_bounds__(256) void form_parameter_kernel(
     if (idx >= n * nth) return;
     const long long i = idx / nth;
     int e = (int)(idx - i * nth);
-    auto from_block = [&](const ThetaBlock &b, int q) -> double {
-        if (b.src == nullptr) return 0.0;
-        int col = b.k0 + q / b.w;
-        col = col < b.T ? col : b.T - 1;
-        col = col > 0 ? col : 0;
-        return b.src[i * b.stride + (long long)col * b.w + (q % b.w)];
-    };
     double v;
     if (e < nx) v = x[i * nx + e];
-    else if ((e -= nx) < nr) v = from_block(r, e);
-    else if ((e -= nr) < nd) v = from_block(d, e);
+    else if ((e -= nx) < nr) v = block_entry(r, i, e);
+    else if ((e -= nr) < nd) v = block_entry(d, i, e);
     else if ((e -= nd) < nup) v = uprev ? uprev[i * nup + e] : 0.0;
-    else v = from_block(p, e - nup);
+    else v = block_entry(p, i, e - nup);
     theta[idx] = v;
 }
 
@@ -73,7 +90,7 @@ __global__ __launch_bounds__(256) void form_parameter_kernel(
 // by column) and entry j of the block is sum_i reference_i[i] * t2s[i*nr + j], accumulated in index
 // order with separate multiply and add exactly as the C loop does (mpc_update_parameter.c:10-16).
 // One thread per entry of theta.
-__global__ __launch_bounds__(256) void update_parameter_kernel(
+inline __global__ __launch_bounds__(256) void update_parameter_kernel(
     double *__restrict__ theta, const double *__restrict__ control, int ncontrol,
     const double *__restrict__ state, int nx, const double *__restrict__ reference, int nr, int nph,
     const double *__restrict__ t2s, const double *__restrict__ disturbance, int nd, int nup,
@@ -98,9 +115,54 @@ __global__ __launch_bounds__(256) void update_parameter_kernel(
     theta[idx] = v;
 }
 
-// x_i <- F x_i + G u_i (sums in index order, F then G), uprev_i <- u_i, bookkeeping of the run.
-// NXT > 0: compile-time state count (<= 8), the state record read and written with wide accesses
-// (element by element from run-time loops a 32-byte record moved at a quarter of the rate); 0: run-time nx.
+// f(c) for every state index c.  NXT > 0: the state count is the compile-time constant NXT (<= 8) and the loop is
+// unrolled, so every index into a scenario's record is static and the record is read and written with wide accesses
+// (element by element from run-time loops a 32-byte record moved at a quarter of the rate); NXT == 0: run-time nx (<= 32).
+template <int NXT, class F>
+__device__ __forceinline__ void for_nx(int nx, F &&f) {
+    if constexpr (NXT > 0) {
+#pragma unroll
+        for (int c = 0; c < NXT; c++) f(c);
+    } else {
+        for (int c = 0; c < nx; c++) f(c);
+    }
+}
+
+// xn = F xo + G u, FUSED multiply-adds from 0 in index order, F then G: the plant step of plant_kernel and
+// plant_theta_kernel (the observer and the scenario loop do not fuse: dynamics_rows below)
+template <int NXT, typename R>
+__device__ __forceinline__ void plant_rows(const R *__restrict__ F, const R *__restrict__ G, const R *xo, R *xn, int nx, int nu,
+                                           const R *__restrict__ u) {
+    for_nx<NXT>(nx, [&](int a) {
+        R acc = (R)0;
+        for_nx<NXT>(nx, [&](int c) { acc = sim_fma(F[a * nx + c], xo[c], acc); });
+        for (int l = 0; l < nu; l++) acc = sim_fma(G[a * nu + l], u[l], acc);
+        xn[a] = acc;
+    });
+}
+
+// The tail of a step for scenario i.  `u`, `uprev`: the scenario's own records; `uprev2`, `utraj`, `flag`, `flag_min`:
+// whole arrays, one record per scenario (uprev2 / utraj / flag_min may be NULL).  uprev <- u[0:nup] (into uprev2 as
+// well), u into the step's slice of the input trajectory, and the smallest exit flag so far.
+template <typename R>
+__device__ __forceinline__ void step_tail(long long i, const R *__restrict__ u, int nu, R *uprev, R *uprev2, int nup, R *utraj,
+                                          const int32_t *__restrict__ flag, int32_t *__restrict__ flag_min, int first) {
+    for (int l = 0; l < nu; l++) {
+        const R ul = u[l];
+        if (l < nup) {
+            uprev[l] = ul;
+            if (uprev2) uprev2[i * nup + l] = ul;
+        }
+        if (utraj) utraj[i * nu + l] = ul;
+    }
+    if (flag_min) {
+        const int32_t f = flag[i];
+        flag_min[i] = first ? f : (f < flag_min[i] ? f : flag_min[i]);
+    }
+}
+
+// x_i <- F x_i + G u_i (plant_rows), uprev_i <- u_i, bookkeeping of the run (step_tail).
+// NXT: the state count at compile time (for_nx), 0 = run-time nx.
 template <int NXT>
 __global__ __launch_bounds__(256) void plant_kernel(
     double *__restrict__ x, double *__restrict__ uprev, const double *__restrict__ u,
@@ -111,54 +173,20 @@ __global__ __launch_bounds__(256) void plant_kernel(
     if (i >= n) return;
     constexpr int NXA = NXT > 0 ? NXT : 32;
     const int nx = NXT > 0 ? NXT : nx_rt;
-    const double *F = FG, *G = FG + nx * nx;
     double xo[NXA], xn[NXA];
-    if constexpr (NXT > 0) {
-#pragma unroll
-        for (int c = 0; c < NXT; c++) xo[c] = x[i * NXT + c];
-#pragma unroll
-        for (int a = 0; a < NXT; a++) {
-            double acc = 0.0;
-#pragma unroll
-            for (int c = 0; c < NXT; c++) acc = __builtin_fma(F[a * NXT + c], xo[c], acc);
-            for (int l = 0; l < nu; l++) acc = __builtin_fma(G[a * nu + l], u[i * nu + l], acc);
-            xn[a] = acc;
-        }
-#pragma unroll
-        for (int a = 0; a < NXT; a++) x[i * NXT + a] = xn[a];
-        if (xtraj_next) {
-#pragma unroll
-            for (int a = 0; a < NXT; a++) xtraj_next[i * NXT + a] = xn[a];
-        }
-    } else {
-        for (int c = 0; c < nx; c++) xo[c] = x[i * nx + c];
-        for (int a = 0; a < nx; a++) {
-            double acc = 0.0;
-            for (int c = 0; c < nx; c++) acc = __builtin_fma(F[a * nx + c], xo[c], acc);
-            for (int l = 0; l < nu; l++) acc = __builtin_fma(G[a * nu + l], u[i * nu + l], acc);
-            xn[a] = acc;
-        }
-        for (int a = 0; a < nx; a++) {
-            x[i * nx + a] = xn[a];
-            if (xtraj_next) xtraj_next[i * nx + a] = xn[a];
-        }
-    }
-    for (int l = 0; l < nu; l++) {
-        if (l < nup) uprev[i * nup + l] = u[i * nu + l];
-        if (utraj) utraj[i * nu + l] = u[i * nu + l];
-    }
-    if (flag_min) {
-        const int32_t f = flag[i];
-        flag_min[i] = first ? f : (f < flag_min[i] ? f : flag_min[i]);
-    }
+    for_nx<NXT>(nx, [&](int c) { xo[c] = x[i * nx + c]; });
+    plant_rows<NXT>(FG, FG + nx * nx, xo, xn, nx, nu, u + i * nu);
+    for_nx<NXT>(nx, [&](int a) { x[i * nx + a] = xn[a]; });
+    if (xtraj_next) for_nx<NXT>(nx, [&](int a) { xtraj_next[i * nx + a] = xn[a]; });
+    step_tail(i, u + i * nu, nu, uprev + i * nup, (double *)nullptr, nup, utraj, flag, flag_min, first);
 }
 
 // The same plant step with the scenario's state kept INSIDE its theta record (theta = [x; r; uprev]):
 // x <- F x + G u is written back into theta[0:nx], u into theta[nx+nr : nx+nr+nup], so the next
 // step's solve reads the record as it stands and no theta has to be formed again (the closed loop
 // with a constant reference then moves 2 x 8 nth + 8 nu bytes per scenario and step instead of
-// re-reading x and re-writing the whole record in a separate kernel).  Same sums in the same order
-// as plant_kernel.  x_out / uprev_out (last step): the caller's arrays.
+// re-reading x and re-writing the whole record in a separate kernel).  x_out / uprev_out (last step):
+// the caller's arrays.
 template <typename R>
 __global__ __launch_bounds__(256) void plant_theta_kernel(
     R *__restrict__ theta, int nth, int nr, const R *__restrict__ u,
@@ -167,42 +195,54 @@ __global__ __launch_bounds__(256) void plant_theta_kernel(
     int first, R *__restrict__ x_out, R *__restrict__ uprev_out, long long n) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const R *F = FG, *G = FG + nx * nx;
     R *t = theta + i * nth;
     R xo[32], xn[32];
     for (int c = 0; c < nx; c++) xo[c] = t[c];
-    for (int a = 0; a < nx; a++) {
-        R acc = (R)0;
-        for (int c = 0; c < nx; c++) acc = sim_fma(F[a * nx + c], xo[c], acc);
-        for (int l = 0; l < nu; l++) acc = sim_fma(G[a * nu + l], u[i * nu + l], acc);
-        xn[a] = acc;
-    }
+    plant_rows<0>(FG, FG + nx * nx, xo, xn, nx, nu, u + i * nu);
     for (int a = 0; a < nx; a++) {
         t[a] = xn[a];
         if (xtraj_next) xtraj_next[i * nx + a] = xn[a];
         if (x_out) x_out[i * nx + a] = xn[a];
     }
-    for (int l = 0; l < nu; l++) {
-        const R ul = u[i * nu + l];
-        if (l < nup) {
-            t[nx + nr + l] = ul;
-            if (uprev_out) uprev_out[i * nup + l] = ul;
-        }
-        if (utraj) utraj[i * nu + l] = ul;
-    }
-    if (flag_min) {
-        const int32_t f = flag[i];
-        flag_min[i] = first ? f : (f < flag_min[i] ? f : flag_min[i]);
-    }
+    step_tail(i, u + i * nu, nu, t + nx + nr, uprev_out, nup, utraj, flag, flag_min, first);
 }
 
 // The reference's generated state observer for N scenarios (codegen/mpc_observer.c:1-28; arrays as
 // src/observer.jl:136-138 writes them): `dyn` = MPC_PLANT_DYNAMICS, one row [f_offset_i, F_i, G_i, Gd_i]
 // per state; `meas` = MPC_MEASUREMENT_FUNCTION, one row [h_offset_j, C_j, Dd_j] per measurement;
 // `kt` = K_TRANSPOSE_OBSERVER (ny x nx).  Sums in the C code's order with separate multiply and add
-// (the reference compiles it with gcc -O3 -msse3: no fused multiply-add).  One thread per scenario.
-// NXT > 0: the state count is the compile-time constant NXT (<= 8): the record is read and written with
-// wide accesses (every index static); NXT == 0: run-time nx (<= 32).
+// (the reference compiles it with gcc -O3 -msse3: no fused multiply-add).  The two device functions are the only
+// copy of these sums: the stand-alone kernels below and the scenario loop (lmpc_scenario_kernels.hpp) call them, which
+// is what makes the loop's observer and plant steps equal the stand-alone ones bit for bit.  `dist(q)`: the caller's
+// disturbance entry q (a flat array that may be absent here, column k of a block in the scenario loop).
+
+// xn = the rows of `dyn` applied to (xo, u, dist): f_offset + F xo + G u + Gd dist, term by term in that order
+template <int NXT, class D>
+__device__ __forceinline__ void dynamics_rows(const double *__restrict__ dyn, const double *xo, double *xn, int nx, int nu, int nd,
+                                              const double *__restrict__ u, D &&dist) {
+    const int stride = 1 + nx + nu + nd;
+    for_nx<NXT>(nx, [&](int a) {
+        const double *d = dyn + a * stride;
+        double acc = d[0];
+        for_nx<NXT>(nx, [&](int c) { acc = __dadd_rn(acc, __dmul_rn(d[1 + c], xo[c])); });
+        for (int l = 0; l < nu; l++) acc = __dadd_rn(acc, __dmul_rn(d[1 + nx + l], u[l]));
+        for (int q = 0; q < nd; q++) acc = __dadd_rn(acc, __dmul_rn(d[1 + nx + nu + q], dist(q)));
+        xn[a] = acc;
+    });
+}
+
+// one measurement of the correction: the innovation y - h_j - C_j xo - Dd_j dist against row `mr` of `meas`, then
+// xn += K'_j * innovation with row `ktj` of `kt`
+template <int NXT, class D>
+__device__ __forceinline__ void correct_row(const double *__restrict__ mr, const double *__restrict__ ktj, double y, const double *xo,
+                                            double *xn, int nx, int nd, D &&dist) {
+    double inno = __dsub_rn(y, mr[0]);
+    for_nx<NXT>(nx, [&](int c) { inno = __dsub_rn(inno, __dmul_rn(mr[1 + c], xo[c])); });
+    for (int q = 0; q < nd; q++) inno = __dsub_rn(inno, __dmul_rn(mr[1 + nx + q], dist(q)));
+    for_nx<NXT>(nx, [&](int c) { xn[c] = __dadd_rn(xn[c], __dmul_rn(ktj[c], inno)); });
+}
+
+// One thread per scenario; NXT as in plant_kernel.
 template <int NXT>
 __global__ __launch_bounds__(256) void predict_state_kernel(
     double *__restrict__ state, const double *__restrict__ control, const double *__restrict__ disturbance,
@@ -212,36 +252,10 @@ __global__ __launch_bounds__(256) void predict_state_kernel(
     constexpr int NXA = NXT > 0 ? NXT : 32;
     const int nx = NXT > 0 ? NXT : nx_rt;
     double xo[NXA], xn[NXA];
-    if constexpr (NXT > 0) {
-#pragma unroll
-        for (int c = 0; c < NXT; c++) xo[c] = state[i * NXT + c];
-    } else {
-        for (int c = 0; c < nx; c++) xo[c] = state[i * nx + c];
-    }
-    const int stride = 1 + nx + nu + nd;
-    auto row = [&](int a) -> double {
-        const double *d = dyn + a * stride;
-        double acc = d[0];
-        if constexpr (NXT > 0) {
-#pragma unroll
-            for (int c = 0; c < NXT; c++) acc = __dadd_rn(acc, __dmul_rn(d[1 + c], xo[c]));
-        } else {
-            for (int c = 0; c < nx; c++) acc = __dadd_rn(acc, __dmul_rn(d[1 + c], xo[c]));
-        }
-        for (int l = 0; l < nu; l++) acc = __dadd_rn(acc, __dmul_rn(d[1 + nx + l], control[i * nu + l]));
-        for (int q = 0; q < nd; q++)
-            acc = __dadd_rn(acc, __dmul_rn(d[1 + nx + nu + q], disturbance ? disturbance[i * nd + q] : 0.0));
-        return acc;
-    };
-    if constexpr (NXT > 0) {
-#pragma unroll
-        for (int a = 0; a < NXT; a++) xn[a] = row(a);
-#pragma unroll
-        for (int a = 0; a < NXT; a++) state[i * NXT + a] = xn[a];
-    } else {
-        for (int a = 0; a < nx; a++) xn[a] = row(a);
-        for (int a = 0; a < nx; a++) state[i * nx + a] = xn[a];
-    }
+    for_nx<NXT>(nx, [&](int c) { xo[c] = state[i * nx + c]; });
+    dynamics_rows<NXT>(dyn, xo, xn, nx, nu, nd, control + i * nu,
+                       [&](int q) { return disturbance ? disturbance[i * nd + q] : 0.0; });
+    for_nx<NXT>(nx, [&](int a) { state[i * nx + a] = xn[a]; });
 }
 
 template <int NXT>
@@ -253,41 +267,15 @@ __global__ __launch_bounds__(256) void correct_state_kernel(
     constexpr int NXA = NXT > 0 ? NXT : 32;
     const int nx = NXT > 0 ? NXT : nx_rt;
     double xo[NXA], xn[NXA];
-    if constexpr (NXT > 0) {
-#pragma unroll
-        for (int c = 0; c < NXT; c++) { xo[c] = state[i * NXT + c]; xn[c] = xo[c]; }
-    } else {
-        for (int c = 0; c < nx; c++) { xo[c] = state[i * nx + c]; xn[c] = xo[c]; }
-    }
-    const int stride = 1 + nx + nd;
-    for (int j = 0; j < ny; j++) {
-        const double *mr = meas + j * stride;
-        double inno = __dsub_rn(measurement[i * ny + j], mr[0]);
-        if constexpr (NXT > 0) {
-#pragma unroll
-            for (int c = 0; c < NXT; c++) inno = __dsub_rn(inno, __dmul_rn(mr[1 + c], xo[c]));
-        } else {
-            for (int c = 0; c < nx; c++) inno = __dsub_rn(inno, __dmul_rn(mr[1 + c], xo[c]));
-        }
-        for (int q = 0; q < nd; q++)
-            inno = __dsub_rn(inno, __dmul_rn(mr[1 + nx + q], disturbance ? disturbance[i * nd + q] : 0.0));
-        if constexpr (NXT > 0) {
-#pragma unroll
-            for (int c = 0; c < NXT; c++) xn[c] = __dadd_rn(xn[c], __dmul_rn(kt[j * NXT + c], inno));
-        } else {
-            for (int c = 0; c < nx; c++) xn[c] = __dadd_rn(xn[c], __dmul_rn(kt[j * nx + c], inno));
-        }
-    }
-    if constexpr (NXT > 0) {
-#pragma unroll
-        for (int c = 0; c < NXT; c++) state[i * NXT + c] = xn[c];
-    } else {
-        for (int c = 0; c < nx; c++) state[i * nx + c] = xn[c];
-    }
+    for_nx<NXT>(nx, [&](int c) { xo[c] = state[i * nx + c]; xn[c] = xo[c]; });
+    for (int j = 0; j < ny; j++)
+        correct_row<NXT>(meas + j * (1 + nx + nd), kt + j * nx, measurement[i * ny + j], xo, xn, nx, nd,
+                         [&](int q) { return disturbance ? disturbance[i * nd + q] : 0.0; });
+    for_nx<NXT>(nx, [&](int c) { state[i * nx + c] = xn[c]; });
 }
 
 // theta = [x; r; uprev] records -> the caller's x and uprev arrays (end of a fused closed loop)
-__global__ __launch_bounds__(256) void unpack_theta_kernel(
+inline __global__ __launch_bounds__(256) void unpack_theta_kernel(
     const double *__restrict__ theta, double *__restrict__ x, double *__restrict__ uprev, int nx, int nr, int nup,
     long long n) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -300,7 +288,7 @@ __global__ __launch_bounds__(256) void unpack_theta_kernel(
 // mpc_get_estimated_state + mpc_get_estimated_disturbance of the generated offset-free observer code
 // (reference src/observer.jl:163-175) for N scenarios: state = observer_state[0:nx], disturbance =
 // [measured_disturbance (or zeros); observer_state[nx : nx+ndo]].  One thread per output entry.
-__global__ __launch_bounds__(256) void split_observer_state_kernel(
+inline __global__ __launch_bounds__(256) void split_observer_state_kernel(
     double *__restrict__ state, double *__restrict__ disturbance, const double *__restrict__ observer_state,
     const double *__restrict__ measured, int nx, int ndm, int ndo, long long n) {
     const int w = nx + ndm + ndo, nobs = nx + ndo;
