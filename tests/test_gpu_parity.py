@@ -448,9 +448,10 @@ def test_closed_loop_simulation_matches_oracle(lmpc, warm):
     ref = oldp.simulate(L, x0, T, prob.F, prob.G, r=r, warm=warm)
     out = qp.simulate(x0, T, prob.F, prob.G, r=r, warm=warm)
     assert np.array_equal(out["flag_min"], ref["flag_min"]) and np.all(out["flag_min"] >= 1)
-    assert np.abs(out["U"] - ref["U"]).max() <= TOL
-    assert np.abs(out["X"] - ref["X"]).max() <= TOL
-    assert np.abs(out["x"] - ref["x"]).max() <= TOL and np.abs(out["uprev"] - ref["uprev"]).max() <= TOL
+    # the plant step is specified operation by operation (fused multiply-adds from 0, F then G) and the oracle's loop
+    # does exactly that: identical bits, not merely close ones (tests/loop_reference.py restates it a third time)
+    for key in ("U", "X", "x", "uprev"):
+        assert np.array_equal(out[key], ref[key]), (key, np.abs(out[key] - ref[key]).max())
     assert abs(out["U"][0, 0, 0] - 1.7612519326) < 1e-6
 
 
@@ -477,7 +478,8 @@ def test_closed_loop_execution_modes_agree_bit_for_bit(lmpc, warm):
             outs.append(qp.simulate(x0, T, prob.F, prob.G, r=r, warm=warm))
         ref = oldp.simulate(oracle_ldp_from(qp.ldp()), x0, T, prob.F, prob.G, r=r, warm=warm)
         assert np.array_equal(outs[0]["flag_min"], ref["flag_min"])
-        assert np.abs(outs[0]["U"] - ref["U"]).max() <= TOL and np.abs(outs[0]["X"] - ref["X"]).max() <= TOL
+        for key in ("U", "X", "x", "uprev"):
+            assert np.array_equal(outs[0][key], ref[key]), (N, T, key, np.abs(outs[0][key] - ref[key]).max())
         for o in outs[1:]:
             for key in ("U", "X", "x", "uprev", "flag_min"):
                 assert np.array_equal(o[key], outs[0][key]), (N, T, key)
@@ -513,7 +515,8 @@ def test_closed_loop_random_shapes_all_execution_modes(lmpc):
                     qp.set_option(k, v)
                 out = qp.simulate(x0, T, Fm, Gm, r=r, warm=warm)
                 assert np.array_equal(out["flag_min"], ref["flag_min"]), (nx, nu, nr, nup, opts)
-                assert np.abs(out["U"] - ref["U"]).max() <= TOL and np.abs(out["X"] - ref["X"]).max() <= TOL
+                for key in ("U", "X", "x") + (("uprev",) if nup else ()):
+                    assert np.array_equal(out[key], ref[key]), (nx, nu, nr, nup, opts, key, np.abs(out[key] - ref[key]).max())
                 if first is None:
                     first = out
                     assert (out["U"] != 0).any()
@@ -989,7 +992,8 @@ def test_K5_closed_loops_on_the_gpu(lmpc):
 def test_reference_preview_simulation_on_the_gpu(lmpc):
     # /root/reference/test/runtests.jl:276-327 through lmpc_simulate_ref_device (preview window
     # k+1 .. k+Np / column k), soft output bounds -> wavefront kernel; same four assertions, and the
-    # trajectories of the oracle's closed loop
+    # trajectories of the closed loop restated on the host (tests/loop_reference.py), bit for bit
+    import loop_reference as lr
     from oracle import mpc2mpqp as omm
     from test_oracle import _preview_sim
     N = 20
@@ -999,8 +1003,13 @@ def test_reference_preview_simulation_on_the_gpu(lmpc):
         q = omm.mpc2mpqp(p)
         qp = lmpc.BatchedQP.from_mpqp(q.H, q.f, q.f_theta, q.A, q.bu, q.bl, q.W, q.senses, nout=1)
         us_o, ys_o, rt = _preview_sim(prev, N)
-        out = qp.simulate_ref(np.tile([1.0, 0.0], (5, 1)), N, p.F, p.G, rt, preview=p.Np if prev else 0)
+        x0 = np.tile([1.0, 0.0], (5, 1))
+        out = qp.simulate_ref(x0, N, p.F, p.G, rt, preview=p.Np if prev else 0)
         assert np.all(out["flag_min"] >= 1)
+        ref = lr.simulate_ref_reference(oracle_ldp_from(qp.ldp()), x0, N, p.F, p.G, rt, preview=p.Np if prev else 0)
+        for key in ("U", "X", "x", "flag_min"):
+            assert np.array_equal(out[key], ref[key]), (prev, key)
+        assert out["uprev"] is None and ref["uprev"].size == 0
         assert np.abs(out["U"][:, 0, 0] - us_o[0]).max() < 1e-6 and np.abs(out["X"][:N, 0].T - ys_o).max() < 1e-6
         outs[prev] = (out["U"][:, 0].T, out["X"][:N, 0].T, rt)
     (up, yp, rt), (un, yn, _) = outs[True], outs[False]
@@ -1118,7 +1127,7 @@ def test_generated_observer_entry_points(lmpc):
     # lmpc_predict_state / lmpc_correct_state == the generated mpc_predict_state / mpc_correct_state
     # (codegen/mpc_observer.c) for N scenarios; the reference checks them against predict!/correct! to
     # 1e-9 (runtests.jl:936-947, with a disturbance :977-987); here also against the C loops restated
-    # term by term (same order, no fused multiply-add: identical bits expected, 1e-12 asserted)
+    # term by term (same order, no fused multiply-add: identical bits asserted)
     import torch
     from oracle import observer as oobs
     g = load_golden("pendulum")
@@ -1134,19 +1143,19 @@ def test_generated_observer_entry_points(lmpc):
     xp = x0.copy()
     qp.predict_state(xp, u, d)
     ref = np.array([oobs.c_predict(dyn, x0[i], u[i], d[i], nx, nu, nd) for i in range(N)])
-    assert np.abs(xp - ref).max() <= 1e-12
+    assert np.array_equal(xp, ref)
     assert np.abs(xp - np.array([kd.predict(x0[i], u[i], d[i]) for i in range(N)])).max() < 1e-9
     xc = xp.copy()
     qp.correct_state(xc, y, d)
     ref = np.array([oobs.c_correct(meas, kt, xp[i], y[i], d[i], nx, ny, nd) for i in range(N)])
-    assert np.abs(xc - ref).max() <= 1e-12
+    assert np.array_equal(xc, ref)
     assert np.abs(xc - np.array([kd.correct(xp[i], y[i], d[i]) for i in range(N)])).max() < 1e-9
     # NULL disturbance = zeros (runtests.jl:942-946 passes C_NULL), device tensors in place
     xd = torch.from_numpy(x0).cuda()
     qp.predict_state(xd, torch.from_numpy(u).cuda(), None)
     torch.cuda.synchronize()
     ref0 = np.array([oobs.c_predict(dyn, x0[i], u[i], np.zeros(nd), nx, nu, nd) for i in range(N)])
-    assert np.abs(xd.cpu().numpy() - ref0).max() <= 1e-12
+    assert np.array_equal(xd.cpu().numpy(), ref0)
     with pytest.raises(lmpc.LmpcError):
         _qp_from_golden(lmpc, g, 1).predict_state(x0.copy(), u)        # no observer set
 
