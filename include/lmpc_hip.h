@@ -807,6 +807,36 @@ int lmpc_constraint_violation_device(lmpc_handle *h, int64_t N, int T, int nx, i
                                      const double *X, const double *U, double *violation_out, double *violation_steps,
                                      void *stream);
 
+/*
+ * Scenario loop with an explicit controller: the loop above with compute_control(empc, x) (reference src/utils.jl:53-60)
+ * in place of the solve -- Simulation(empc, scenario) of src/simulation.jl:37.  A step whose theta lies in a kept region
+ * takes that region's law and flag 1 / 2 (lmpc_explicit_eval_device's rule); every other step is solved COLD by the
+ * controller's handle, so that step's numbers are those of lmpc_simulate_scenario_device with warm == 0.  PRE and POST
+ * arithmetic are those of the loop above, bit for bit; the observer is the one lmpc_set_observer put on that handle.
+ *   mode 1  run-ahead: one kernel runs every scenario forward through the steps it can locate (no launch and no theta
+ *           record in memory per located step); the scenarios it could not locate wait in a dense batch, which the
+ *           handle solves; the kernel resumes them through the list; at most T + 1 launches of that kernel (T
+ *           solves), one stream synchronisation (the count of waiting scenarios) per launch.
+ *   mode 0  lock-step, from the older entry points' kernels alone: per step the PRE kernel, lmpc_explicit_eval_device
+ *           on the formed theta, the POST kernel; one synchronisation per step.  Same numbers.
+ * region_traj  T x N (step-major) or NULL: the region of every scenario-step, -1 = solved by the handle.
+ * stats        HOST, 4 values or NULL: launches of the run-ahead kernel (all located: 1; every step solved by the
+ *              handle: T + 1; mode 0: the steps), scenario-steps solved by the handle, scenario-steps located, largest
+ *              batch handed to the handle.
+ * Refused (LMPC_ERR_BADARG, text in lmpc_explicit_last_error, the field's name first, before the GPU is touched): all
+ * that lmpc_scenario_check refuses, warm != 0, nth > LMPC_EXPLICIT_MAX_NTH, a controller built without a handle, a
+ * mode other than 0 / 1.  lmpc_explicit_scenario_check asks the descriptor's part of that without a controller (text
+ * in lmpc_last_error(NULL)).  Scratch lives in the controller and is freed with it: one controller serves one
+ * stream at a time.  Other arguments as lmpc_simulate_scenario_device / lmpc_simulate_scenario (HOST twin).
+ */
+int lmpc_explicit_scenario_check(int nth, int nout, const lmpc_observer *observer, const lmpc_scenario_sim *s, int mode);
+int lmpc_explicit_simulate_scenario_device(lmpc_explicit *e, int64_t N, int T, const lmpc_scenario_sim *s, double *x,
+                                           double *xhat, double *uprev, double *U_traj, double *X_traj, int32_t *flag_min,
+                                           int32_t *region_traj, int mode, int64_t *stats, void *stream);
+int lmpc_explicit_simulate_scenario(lmpc_explicit *e, int64_t N, int T, const lmpc_scenario_sim *s, double *x, double *xhat,
+                                    double *uprev, double *U_traj, double *X_traj, int32_t *flag_min, int32_t *region_traj,
+                                    int mode, int64_t *stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,6 +38,7 @@ SYMBOLS = (
     "lmpc_explicit_eval_device", "lmpc_explicit_eval", "lmpc_explicit_last_error", "lmpc_explicit_free",
     "lmpc_scenario_check", "lmpc_simulate_scenario_device", "lmpc_simulate_scenario", "lmpc_evaluate_cost_device",
     "lmpc_constraint_violation_device",
+    "lmpc_explicit_scenario_check", "lmpc_explicit_simulate_scenario_device", "lmpc_explicit_simulate_scenario",
 )
 
 
@@ -232,6 +233,8 @@ def lib():
     L.lmpc_evaluate_cost_device.restype = i32
     L.lmpc_constraint_violation_device.argtypes = [vp, i64, i32, i32, i32, ctypes.POINTER(SimCost), vp, vp, vp, vp, vp]
     L.lmpc_constraint_violation_device.restype = i32
+    L.lmpc_explicit_scenario_check.argtypes = [i32, i32, ctypes.POINTER(Observer), sp, i32]
+    L.lmpc_explicit_scenario_check.restype = i32
     _lib = L
     return L
 

@@ -13,17 +13,6 @@ namespace {
 
 constexpr int kBlock = 256;
 
-int efail(lmpc_explicit *e, int code, const std::string &msg) {
-    e->err = msg;
-    return code;
-}
-
-#define EXP_TRY(e, call)                                                                              \
-    do {                                                                                              \
-        hipError_t e__ = (call);                                                                      \
-        if (e__ != hipSuccess) return efail(e, LMPC_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
-    } while (0)
-
 void release_scratch(lmpc_explicit *e) {
     (void)hipFree(e->dList); (void)hipFree(e->dTheta); (void)hipFree(e->dX); (void)hipFree(e->dFlag);
     e->dList = nullptr; e->dTheta = nullptr; e->dX = nullptr; e->dFlag = nullptr;
@@ -56,6 +45,10 @@ void launch_eval(const lmpc::ExplicitView &v, int64_t N, const double *theta, do
 }
 
 }  // namespace
+
+namespace lmpc {
+int explicit_reserve(lmpc_explicit *e, int64_t N) { return reserve(e, N); }
+}  // namespace lmpc
 
 extern "C" {
 
@@ -168,6 +161,8 @@ void lmpc_explicit_free(lmpc_explicit *e) {
         release_scratch(e);
         (void)hipFree(e->dBlob);
         (void)hipFree(e->dCount);
+        (void)hipFree(e->simStep); (void)hipFree(e->simList2); (void)hipFree(e->simFlag);
+        (void)hipFree(e->simTheta); (void)hipFree(e->simU); (void)hipFree(e->simScr);
         (void)hipHostFree(e->hCount);
     }
     delete e;

@@ -24,11 +24,31 @@ struct lmpc_explicit {
     int32_t *dList = nullptr, *dCount = nullptr, *dFlag = nullptr, *hCount = nullptr;
     double *dTheta = nullptr, *dX = nullptr;
     int64_t cap = 0;
+    // scenario loop (lmpc_explicit_sim.hip): per-scenario step counters, the second work list, the lock-step form's
+    // theta / u / flag, and [xhat | ulast] when the caller keeps none
+    int32_t *simStep = nullptr, *simList2 = nullptr, *simFlag = nullptr;
+    double *simTheta = nullptr, *simU = nullptr, *simScr = nullptr;
+    int64_t simCap = 0, simLockCap = 0;
+    size_t simScrCap = 0;
 };
+
+// the text into the controller's error slot, the code handed back
+inline int efail(lmpc_explicit *e, int code, const std::string &msg) {
+    e->err = msg;
+    return code;
+}
+
+#define EXP_TRY(e, call)                                                                              \
+    do {                                                                                              \
+        hipError_t e__ = (call);                                                                      \
+        if (e__ != hipSuccess) return efail(e, LMPC_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
+    } while (0)
 
 namespace lmpc {
 int explicit_build_pack(lmpc_explicit *e, int n, int m, int ms, int nth, int nout, const double *M, const double *du,
                         const double *dl, const double *Dth, const double *Rout, const double *x0, const double *Xth,
                         const int32_t *sense, const lmpc_settings &s, int is_avi, int64_t N, const double *theta,
                         const uint64_t *active, const int32_t *exitflag, const lmpc_explicit_opts &o);
+// the fallback scratch (dList, dTheta, dX, dFlag, the count words) sized for N points (lmpc_explicit.hip)
+int explicit_reserve(lmpc_explicit *e, int64_t N);
 }  // namespace lmpc

@@ -215,7 +215,8 @@ __global__ __launch_bounds__(256) void scenario_post_kernel(ScnPost A, ScnConst 
 // Stand-alone scoring of stored trajectories, one thread per scenario: X step-major (step k's states at
 // X + k * n * nx, i.e. the first T slices of an X_traj), U step-major (T x n x nu).  The same step functions in the
 // same order over k as the loop's POST kernel.  cost / viol: n doubles; viol_steps: T x n or nullptr.
-__global__ __launch_bounds__(256) void scenario_cost_kernel(ScnConst K, const double *__restrict__ X, const double *__restrict__ U,
+// (`inline`: this header is part of two translation units, as lmpc_sim_kernels.hpp is.)
+inline __global__ __launch_bounds__(256) void scenario_cost_kernel(ScnConst K, const double *__restrict__ X, const double *__restrict__ U,
                                                             ThetaBlock r, int nx, int nu, int T, double *__restrict__ cost, long long n) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -231,7 +232,7 @@ __global__ __launch_bounds__(256) void scenario_cost_kernel(ScnConst K, const do
     cost[i] = __dmul_rn(0.5, run);
 }
 
-__global__ __launch_bounds__(256) void scenario_violation_kernel(ScnConst K, const double *__restrict__ X, const double *__restrict__ U,
+inline __global__ __launch_bounds__(256) void scenario_violation_kernel(ScnConst K, const double *__restrict__ X, const double *__restrict__ U,
                                                                  int nx, int nu, int T, double *__restrict__ viol,
                                                                  double *__restrict__ viol_steps, long long n) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;

@@ -332,6 +332,7 @@ _OPTS = None
 def _bind():
     """argtypes of the explicit-controller entry points (bound once, on first use)."""
     import ctypes
+    from . import _cabi
     from ._cabi import lib
     global _OPTS
     L = lib()
@@ -349,7 +350,11 @@ def _bind():
         L.lmpc_explicit_locate_host.argtypes = [vp, i64] + [vp] * 5
         L.lmpc_explicit_eval_device.argtypes = [vp, i64] + [vp] * 5
         L.lmpc_explicit_eval.argtypes = [vp, i64] + [vp] * 4
-        for f in ("build_ldp", "build", "info", "region", "blob", "training", "locate_host", "eval_device", "eval"):
+        sp = ctypes.POINTER(_cabi.ScenarioSim)
+        L.lmpc_explicit_simulate_scenario_device.argtypes = [vp, i64, i32, sp] + [vp] * 7 + [i32, vp, vp]
+        L.lmpc_explicit_simulate_scenario.argtypes = [vp, i64, i32, sp] + [vp] * 7 + [i32, vp]
+        for f in ("build_ldp", "build", "info", "region", "blob", "training", "locate_host", "eval_device", "eval",
+                  "simulate_scenario_device", "simulate_scenario"):
             getattr(L, "lmpc_explicit_" + f).restype = i32
         L.lmpc_explicit_last_error.argtypes = [vp]
         L.lmpc_explicit_last_error.restype = ctypes.c_char_p
@@ -564,6 +569,30 @@ class ExplicitController:
             _dev_arg(exitflag, "exitflag", torch.int32, N, dev, False), _dev_arg(region, "region", torch.int32, N, dev, False),
             ctypes.c_void_p(st)))
         return x, exitflag, region
+
+    def simulate_scenario_device(self, x, T, plant, measurement=None, *, mode=0, **kw):
+        """The scenario loop with this controller in place of the solve (`lmpc_explicit_simulate_scenario_device`):
+        arguments and result as `BatchedQP.simulate_scenario` on the controller's handle (warm must stay False), plus
+        `regions` (T, N) int32, -1 = solved by the handle, and `stats` = dict(rounds, fallback_steps, located_steps,
+        largest_batch).  mode 0 (default: the faster one where both were measured): lock-step from the older
+        kernels; mode 1: run-ahead kernel with the fallback in rounds.  Synchronises the stream once per round (mode 0: per step); the last launches are still enqueued
+        when it returns."""
+        import ctypes
+        import torch
+        L = _bind()
+        N = int(x.shape[0])
+        regions = torch.empty((int(T), N), dtype=torch.int32, device=x.device)
+        stats = np.zeros(4, np.int64)
+
+        def launch(desc, n, t, *args):
+            self._check(L.lmpc_explicit_simulate_scenario_device(
+                self._e, n, t, ctypes.byref(desc), *args[:6], ctypes.c_void_p(regions.data_ptr()) if regions.numel() else None,
+                int(mode), ctypes.c_void_p(stats.ctypes.data), args[6]))
+
+        out = self.qp.simulate_scenario(x, T, plant, measurement, launch=launch, **kw)
+        out["regions"] = regions
+        out["stats"] = dict(zip(("rounds", "fallback_steps", "located_steps", "largest_batch"), (int(v) for v in stats)))
+        return out
 
     def _check(self, rc):
         if rc != 1:

@@ -121,15 +121,26 @@ class Simulation:
     """`Simulation(mpc, scenario)` of the reference for every scenario at once.  mpc: an `MPC` of this package;
     plant: the true `Plant`; observer: None, an object with `codegen_arrays()` or the triple (MPC_PLANT_DYNAMICS,
     MPC_MEASUREMENT_FUNCTION, K_TRANSPOSE_OBSERVER) of the generated observer (src/observer.jl:124-141).
+    An `ExplicitMPC` runs the loop with its piecewise-affine law (`mode` 0, the default: lock-step, the faster form
+    where both were measured; 1: run-ahead kernel; warm must be False) and adds `regions` (N_scen, N) int32, -1 = solved by the implicit path, and `stats`.
     Fields as in the reference, one leading scenario axis unless x0 was a single vector: xs, xhats (nx, N), us
     (nu, N), ys, yms (ny, N), rs, ds, ts, and flag_min (smallest exit flag per scenario)."""
 
-    def __init__(self, mpc, scenario, plant, observer=None, warm=False, cost=None):
+    def __init__(self, mpc, scenario, plant, observer=None, warm=False, cost=None, mode=0):
         import torch
         from .mpc import ExplicitMPC
-        if isinstance(mpc, ExplicitMPC):
-            raise NotImplementedError("the scenario loop runs the implicit controller (see DESIGN.md)")
-        model: BatchedQP = mpc.control_model()
+        empc = mpc if isinstance(mpc, ExplicitMPC) else None
+        if empc is not None:                      # simulation.jl:37 with compute_control(empc, x), utils.jl:53-60
+            if empc.controller is None:
+                raise RuntimeError("Need to build a binary search tree to evaluate control law")
+            if warm:
+                raise ValueError("an explicit controller has no warm start")
+            mpc = empc.mpc
+            uprev0 = empc.uprev
+        else:
+            uprev0 = mpc.uprev
+        # an explicit controller runs on the handle it was built on (its fallback solves and its observer live there)
+        model: BatchedQP = mpc.control_model() if empc is None else empc.controller.qp
         self.mpc, self.scenario, self.plant, self.model = mpc, scenario, plant, model
         dev = torch.device("cuda", model.device)
         T, S = scenario.N, scenario.n_scen
@@ -145,8 +156,10 @@ class Simulation:
         x = torch.from_numpy(scenario.x0.copy()).to(dev)
         uprev = None
         if mpc.nuprev:
-            uprev = torch.from_numpy(np.tile(np.asarray(mpc.uprev, float)[:mpc.nuprev], (S, 1))).to(dev)
-        out = model.simulate_scenario(
+            uprev = torch.from_numpy(np.tile(np.asarray(uprev0, float)[:mpc.nuprev], (S, 1))).to(dev)
+        run = model.simulate_scenario if empc is None else \
+            (lambda *a, **kw: empc.controller.simulate_scenario_device(*a, mode=mode, **kw))
+        out = run(
             x, T, plant.dynamics_rows(), plant.measurement_rows(), nd=plant.nd, ny=plant.ny,
             r=up(specs["r"]), d=up(specs["d"]), p=up(specs["p"]), noise=up(specs["noise"]),
             r_preview=specs["r"]["H"], d_preview=specs["d"]["H"], p_preview=specs["p"]["H"],
@@ -167,6 +180,9 @@ class Simulation:
         self.cost = out["cost"].cpu().numpy() if "cost" in out else None
         self.violation = out["violation"].cpu().numpy() if "violation" in out else None
         self.ts = np.arange(T, dtype=float)
+        if empc is not None:                      # per scenario and step: the region, -1 = solved by the implicit path
+            self.regions = np.ascontiguousarray(out["regions"].cpu().numpy().T)
+            self.stats = out["stats"]
         if scenario.single:
             for k in ("xs", "us", "ys", "yms", "xhats", "ds", "rs"):
                 setattr(self, k, getattr(self, k)[0])

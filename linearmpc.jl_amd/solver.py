@@ -548,9 +548,11 @@ class BatchedQP:
     def simulate_scenario(self, x, T, plant, measurement=None, nd=0, ny=0, r=None, d=None, p=None, noise=None,
                           r_preview=0, d_preview=0, p_preview=0, r_width=0, d_width=None, p_width=0, xhat=None,
                           uprev=None, use_observer=False, warm=False, cost=None, want=("U", "X"), want_cost=False,
-                          want_violation=False, stream=None):
+                          want_violation=False, stream=None, launch=None):
         """The scenario loop (`lmpc_simulate_scenario_device`): torch CUDA tensors in and out, enqueued on `stream`
-        (default: torch's current stream), not synchronised.
+        (default: torch's current stream), not synchronised.  `launch(desc, N, T, x, xhat, uprev, U, X, flag_min,
+        stream)`, all but desc, N, T as ctypes pointers: another entry point taking the same descriptor and arrays
+        (ExplicitController.simulate_scenario_device).
 
         x (N, nx) float64: true states, advanced in place; xhat (N, nx) or None; uprev (N, nuprev) or None (zeros
         when the handle's theta has a uprev block).  plant: nx rows [f_offset, F, G, Gd]; measurement: ny rows
@@ -598,10 +600,12 @@ class BatchedQP:
             out["violation"] = torch.empty(N, dtype=f64, device=dev)
             desc.violation_out = out["violation"].data_ptr()
         st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-        check(lib().lmpc_simulate_scenario_device(
-            self._h, N, T, ctypes.byref(desc), _vp(x.data_ptr()), _dev_arg(xhat, "xhat", f64, N * nx, dv),
-            _dev_arg(uprev, "uprev", f64, N * nup, dv), _vp(ptr(out.get("U"))), _vp(ptr(out.get("X"))),
-            _vp(out["flag_min"].data_ptr()), _vp(st)), self._h)
+        args = (_vp(x.data_ptr()), _dev_arg(xhat, "xhat", f64, N * nx, dv), _dev_arg(uprev, "uprev", f64, N * nup, dv),
+                _vp(ptr(out.get("U"))), _vp(ptr(out.get("X"))), _vp(out["flag_min"].data_ptr()), _vp(st))
+        if launch is not None:
+            launch(desc, N, T, *args)
+        else:
+            check(lib().lmpc_simulate_scenario_device(self._h, N, T, ctypes.byref(desc), *args), self._h)
         out["_keep"] = keep                      # the launches are asynchronous: keep the sources alive
         return out
 
