@@ -724,8 +724,9 @@ void lmpc_explicit_free(lmpc_explicit *e);
  * kernel, all enqueued on `stream`; no host synchronisation inside (the once-per-handle probe that
  * lmpc_solve_batch_device documents is the one exception, as everywhere).  Binary64.  Every handle the plain solve
  * accepts works (is_avi, hybrid / branch and bound, proximal-point), because the solve is the handle's own.  The
- * scenario-asynchronous machinery ("sim_async", run-ahead, "sim_keep_factor") does not apply to this loop, and the
- * offset-free observer (lmpc_compute_control_observer_device) is not part of it.
+ * scenario-asynchronous machinery ("sim_async", run-ahead, "sim_keep_factor") does not apply to this loop.  The
+ * offset-free observer runs in a loop of its own, lmpc_simulate_scenario_offset_free_device below, which takes the same
+ * descriptor.
  *
  * Step k (0-based), per scenario:
  *   PRE   d_k = column k of d;  ym_j = h_offset_j + sum_i C_ji x_i + sum_q Dd_jq d_q (+ noise_j of column k), summed in
@@ -796,6 +797,52 @@ int lmpc_simulate_scenario_device(lmpc_handle *h, int64_t N, int T, const lmpc_s
                                   double *uprev, double *U_traj, double *X_traj, int32_t *flag_min, void *stream);
 int lmpc_simulate_scenario(lmpc_handle *h, int64_t N, int T, const lmpc_scenario_sim *s, double *x, double *xhat,
                            double *uprev, double *U_traj, double *X_traj, int32_t *flag_min);
+/*
+ * The scenario loop with the reference's OFFSET-FREE observer (set_offset_free_observer!, src/setup.jl:392-487,
+ * src/observer.jl:13-122, 203-225): a Kalman filter on the state augmented with n_offset_free constant disturbance
+ * channels, whose estimate is fed into the controller's d block -- the closed loop of lmpc_correct_state_device ->
+ * lmpc_compute_control_observer_device -> lmpc_predict_state_device, plus the true plant, in one call and with a
+ * disturbance preview.  Dimensions: nx = plant and controller state; s->nd = ndm, the MEASURED disturbances (the
+ * plant's Gd / Dd and the trajectory d have ndm rows); ndo = n_offset_free; na = nx + ndo = the observer's state; the
+ * controller's model.nd = ndm + ndo.  The handle's lmpc_set_observer arrays are those of the AUGMENTED filter:
+ * n_state = na, n_control = nu, n_disturbance = ndm, n_measurement = ny.
+ *
+ * Step k (0-based), per scenario; everything not said here is the loop above, sum for sum:
+ *   PRE   ym, y from the TRUE state (nx wide) and d_k (ndm wide) through `measurement`, as above;
+ *         xaug <- mpc_correct_state(xaug, ym, d_k) on the augmented arrays: lmpc_correct_state_device on this handle,
+ *         bit for bit;  xhat = xaug[0:nx], dhat = xaug[nx:na], both read AFTER the correction (observer.jl:119-122);
+ *         theta = [xhat; r-block; d-block; uprev; p-block];  the d-block is max(d.H, 1) columns of width ndm + ndo,
+ *         column c = [d column k + c, held at the last; dhat]: the measured rows first, dhat repeated in every column
+ *         (get_control_disturbance, observer.jl:203-222; format_disturbance, utils.jl:155-205).  d.w == 0 (no
+ *         trajectory, or ndm == 0): the measured rows are zeros (absent with ndm == 0), dhat is repeated all the same.
+ *   solve as above.
+ *   POST  cost and violation on the TRUE (x_k, u_k);  xaug <- mpc_predict_state(xaug, u, d_k) on the augmented arrays
+ *         (lmpc_predict_state_device bit for bit);  x <- the row sums of `plant` (nx rows of 1 + nx + nu + ndm);  uprev
+ *         <- u, trajectories, flag_min last.
+ *   xaug  N records of na, in/out; NULL = it starts at [x; 0] (set_state!, observer.jl:74-90) in the handle's scratch.
+ * Outputs: Xhat_traj T x N x nx = the first nx entries of the corrected estimate, D_traj T x N x ndm, and Dhat_traj
+ * T x N x ndo (DEVICE, or NULL) = the disturbance estimate the controller saw.  na <= 8: kernels with both counts at
+ * compile time; larger, up to na = 32: run-time loops.
+ * Refused (LMPC_ERR_BADARG, the field's name first, before the GPU is touched): of NULL, n_offset_free <= 0,
+ * nx + n_offset_free > 32, use_observer == 0, no observer set or one set with other dimensions than (nx + ndo, nu, nd,
+ * ny), d.w neither 0 nor nd, widths with nx + width(r) + (nd + n_offset_free) * max(d.H, 1) + nuprev + width(p) != nth,
+ * xaug given to a handle without an observer, and all that lmpc_scenario_check refuses.
+ * lmpc_scenario_offset_free_check asks that without a handle.  lmpc_simulate_scenario_offset_free: the HOST twin
+ * (Dhat_traj HOST as well).  The explicit controller's loop (lmpc_explicit_simulate_scenario*) is NOT extended: given a
+ * descriptor of this kind it refuses through its own dimension check ("nth").
+ */
+typedef struct lmpc_offset_free {
+    int32_t n_offset_free;               /* ndo: estimated disturbance channels                                   */
+    double *Dhat_traj;                   /* T x N x ndo, optional output, or NULL                                 */
+} lmpc_offset_free;
+int lmpc_scenario_offset_free_check(int nth, int nout, const lmpc_observer *observer, const lmpc_scenario_sim *s,
+                                    const lmpc_offset_free *of);
+int lmpc_simulate_scenario_offset_free_device(lmpc_handle *h, int64_t N, int T, const lmpc_scenario_sim *s,
+                                              const lmpc_offset_free *of, double *x, double *xaug, double *uprev,
+                                              double *U_traj, double *X_traj, int32_t *flag_min, void *stream);
+int lmpc_simulate_scenario_offset_free(lmpc_handle *h, int64_t N, int T, const lmpc_scenario_sim *s,
+                                       const lmpc_offset_free *of, double *x, double *xaug, double *uprev, double *U_traj,
+                                       double *X_traj, int32_t *flag_min);
 /* Scoring of a stored run, one thread per scenario: X = the states x_0 .. x_{T-1}, step-major (the first T slices of an
  * X_traj), U = T x N x nu as U_traj.  r: the reference trajectory as in the loop (column k at step k; NULL = zeros).
  * cost_out: N doubles.  violation_out: N doubles (maximum over the steps) and / or violation_steps: T x N, the

@@ -149,6 +149,68 @@ end
 #   lay = LmpcParamLayout(nx, nr, nd, nuprev, np, cond ? mpc.Np : 0, cond ? pointer(mpc.traj2setpoint) : C_NULL)
 #   ccall((:lmpc_set_parameter_layout, liblmpc), Cint, (Ptr{Cvoid}, Ref{LmpcParamLayout}), bm.h, lay)
 
+# ---- Simulation(mpc, scenario) with an OffsetFreeObserver for N scenarios (include/lmpc_hip.h,
+# lmpc_simulate_scenario_offset_free).  NOT executed in this repository's tests: there is no Julia here.
+struct LmpcBlock
+    src::Ptr{Cdouble}; stride::Int64; w::Cint; T::Cint; k0::Cint; H::Cint
+end
+LmpcBlock() = LmpcBlock(C_NULL, 0, 0, 1, 0, 0)
+LmpcBlock(A::Array{Float64,3}, H) = LmpcBlock(pointer(A), size(A,1)*size(A,2), size(A,1), size(A,2), 0, H)   # w × T × N
+struct LmpcScenarioSim
+    nx::Cint; nu::Cint; nd::Cint; ny::Cint
+    plant::Ptr{Cdouble}; measurement::Ptr{Cdouble}
+    r::LmpcBlock; d::LmpcBlock; p::LmpcBlock; noise::LmpcBlock
+    nuprev::Cint; use_observer::Cint; warm::Cint
+    Y_traj::Ptr{Cdouble}; Ym_traj::Ptr{Cdouble}; Xhat_traj::Ptr{Cdouble}; D_traj::Ptr{Cdouble}
+    cost::Ptr{Cvoid}; cost_out::Ptr{Cdouble}; violation_out::Ptr{Cdouble}
+end
+struct LmpcOffsetFree
+    n_offset_free::Cint; Dhat_traj::Ptr{Cdouble}
+end
+struct LmpcObserver
+    n_state::Cint; n_control::Cint; n_disturbance::Cint; n_measurement::Cint
+    plant_dynamics::Ptr{Cdouble}; measurement_function::Ptr{Cdouble}; k_transpose::Ptr{Cdouble}
+end
+"the augmented filter of mpc.state_observer::OffsetFreeObserver onto the handle (observer.jl:139-141's arrays)"
+function set_offset_free_observer!(bm::BatchedModel, obs)
+    kf = obs.estimator
+    dyn = collect([kf.f_offset kf.F kf.G kf.Gd]')[:]; meas = collect([kf.h_offset kf.C kf.Dd]')[:]; kt = kf.K[:]
+    GC.@preserve dyn meas kt begin
+        o = LmpcObserver(size(kf.F,1), size(kf.G,2), size(kf.Gd,2), size(kf.C,1), pointer(dyn), pointer(meas), pointer(kt))
+        rc = ccall((:lmpc_set_observer, liblmpc), Cint, (Ptr{Cvoid}, Ref{LmpcObserver}), bm.h, o)
+    end
+    rc == 1 || error("lmpc_set_observer failed ($rc)")
+end
+"X0 nx × N true initial states; R ny × T × N, D ndm × T × N (or nothing); plant: the TRUE model (F, G, Gd, f_offset, C, Dd, h_offset
+with the MEASURED columns).  Returns us (nu × N × T), xs (nx × N × T+1), xhats, dhats (ndo × N × T), flag_min."
+function simulate_offset_free!(mpc::LinearMPC.MPC, bm::BatchedModel, plant, X0::Matrix{Float64}, T::Integer;
+                               R=nothing, D=nothing, warm=false)
+    obs = mpc.state_observer
+    set_offset_free_observer!(bm, obs)
+    nx, nu, ny, ndm, ndo = obs.nx, mpc.model.nu, size(obs.C,1), obs.nd_measured, obs.nd_offsetfree
+    N = size(X0,2)
+    dyn = collect([plant.f_offset plant.F plant.G plant.Gd[:,1:ndm]]')[:]
+    meas = collect([plant.h_offset plant.C plant.Dd[:,1:ndm]]')[:]
+    H = mpc.settings.disturbance_preview ? mpc.Np : 0
+    nr, _, nuprev, _ = LinearMPC.get_parameter_dims(mpc)[2:5]
+    rb = isnothing(R) ? LmpcBlock(C_NULL, 0, nr, 1, 0, 0) : LmpcBlock(R, 0)
+    db = isnothing(D) ? LmpcBlock(C_NULL, 0, 0, 1, 0, H) : LmpcBlock(D, H)
+    U = Array{Float64}(undef, nu, N, T); X = Array{Float64}(undef, nx, N, T+1)
+    Xh = Array{Float64}(undef, nx, N, T); Dh = Array{Float64}(undef, ndo, N, T); fm = Vector{Cint}(undef, N)
+    x = copy(X0); up = zeros(max(nuprev,1), N)
+    GC.@preserve dyn meas R D Xh Dh begin
+        s = LmpcScenarioSim(nx, nu, ndm, ny, pointer(dyn), pointer(meas), rb, db, LmpcBlock(), LmpcBlock(), nuprev, 1, warm,
+                            C_NULL, C_NULL, pointer(Xh), C_NULL, C_NULL, C_NULL, C_NULL)
+        rc = ccall((:lmpc_simulate_scenario_offset_free, liblmpc), Cint,
+            (Ptr{Cvoid}, Int64, Cint, Ref{LmpcScenarioSim}, Ref{LmpcOffsetFree}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+             Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+            bm.h, N, T, s, LmpcOffsetFree(ndo, pointer(Dh)), x, C_NULL, up, U, X, fm)
+    end
+    rc == 1 || error("lmpc_simulate_scenario_offset_free failed ($rc): ",
+                     unsafe_string(ccall((:lmpc_last_error, liblmpc), Cstring, (Ptr{Cvoid},), bm.h)))
+    return U, X, Xh, Dh, fm
+end
+
 "compute_control for N scenarios at once (utils.jl:43-51 without the mutable mpc.uprev)"
 function compute_control_batch(mpc, bm::BatchedModel, X0::Matrix; R=nothing, Uprev=nothing, check=true)
     N = size(X0,2)

@@ -39,6 +39,7 @@ SYMBOLS = (
     "lmpc_scenario_check", "lmpc_simulate_scenario_device", "lmpc_simulate_scenario", "lmpc_evaluate_cost_device",
     "lmpc_constraint_violation_device",
     "lmpc_explicit_scenario_check", "lmpc_explicit_simulate_scenario_device", "lmpc_explicit_simulate_scenario",
+    "lmpc_scenario_offset_free_check", "lmpc_simulate_scenario_offset_free_device", "lmpc_simulate_scenario_offset_free",
 )
 
 
@@ -93,6 +94,11 @@ class ScenarioSim(ctypes.Structure):
                 ("Y_traj", ctypes.c_void_p), ("Ym_traj", ctypes.c_void_p), ("Xhat_traj", ctypes.c_void_p),
                 ("D_traj", ctypes.c_void_p), ("cost", ctypes.POINTER(SimCost)),
                 ("cost_out", ctypes.c_void_p), ("violation_out", ctypes.c_void_p)]
+
+
+class OffsetFree(ctypes.Structure):
+    """`lmpc_offset_free`: the offset-free part of a scenario run (lmpc_simulate_scenario_offset_free*)."""
+    _fields_ = [("n_offset_free", ctypes.c_int32), ("Dhat_traj", ctypes.c_void_p)]
 
 
 _lib = None
@@ -235,6 +241,13 @@ def lib():
     L.lmpc_constraint_violation_device.restype = i32
     L.lmpc_explicit_scenario_check.argtypes = [i32, i32, ctypes.POINTER(Observer), sp, i32]
     L.lmpc_explicit_scenario_check.restype = i32
+    op = ctypes.POINTER(OffsetFree)
+    L.lmpc_scenario_offset_free_check.argtypes = [i32, i32, ctypes.POINTER(Observer), sp, op]
+    L.lmpc_scenario_offset_free_check.restype = i32
+    L.lmpc_simulate_scenario_offset_free_device.argtypes = [vp, i64, i32, sp, op] + [vp] * 7
+    L.lmpc_simulate_scenario_offset_free_device.restype = i32
+    L.lmpc_simulate_scenario_offset_free.argtypes = [vp, i64, i32, sp, op] + [vp] * 6
+    L.lmpc_simulate_scenario_offset_free.restype = i32
     _lib = L
     return L
 

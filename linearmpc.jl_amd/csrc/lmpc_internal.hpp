@@ -368,6 +368,7 @@ int api_launch_wave_f32(lmpc_handle *h, const float *dC, int64_t nprob, const fl
                         uint64_t *active, const uint64_t *warm, hipStream_t st);
 void loop_preload();
 void scenario_preload();
+void offset_free_preload();
 
 // four problems per wavefront (lmpc_row_inst.hip): capacity the batch would run at on that kernel (0: it does not take
 // the batch), and its launch as the only pass (pass 0) or the first of two (pass 1) of a wavefront-kernel call

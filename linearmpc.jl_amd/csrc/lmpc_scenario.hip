@@ -20,6 +20,7 @@ void scenario_preload() {
     hipFuncAttributes fa;
     (void)hipFuncGetAttributes(&fa, (const void *)scenario_pre_kernel<0>);
     (void)hipGetLastError();
+    offset_free_preload();                             // ... and the offset-free loop's unit
 }
 }  // namespace lmpc
 

@@ -14,11 +14,19 @@ namespace lmpc {
 inline int bwidth(const lmpc_block &b) { return b.w * (b.H > 0 ? b.H : 1); }
 
 // every check that needs no device; `obs`: the dimensions lmpc_set_observer was given, or nullptr.  "" = fine,
-// otherwise the text, which starts with the offending field's name
-inline std::string scenario_problem(int nth, int nout, const lmpc_observer *obs, const lmpc_scenario_sim *s) {
+// otherwise the text, which starts with the offending field's name.  `offset_free`: the check of the offset-free loop
+// (lmpc_scenario_offset_free_check) -- the observer is required and na = nx + of->n_offset_free wide, nd counts the
+// MEASURED disturbances and every column of theta's d block carries the n_offset_free estimates behind them
+inline std::string scenario_problem(int nth, int nout, const lmpc_observer *obs, const lmpc_scenario_sim *s,
+                                    const lmpc_offset_free *of = nullptr, bool offset_free = false) {
     if (!s) return "s: NULL descriptor";
     auto bad = [](const char *f, const std::string &why) { return std::string(f) + ": " + why; };
+    if (offset_free && !of) return "of: NULL descriptor";
+    if (offset_free && of->n_offset_free <= 0) return bad("n_offset_free", "must be >= 1, got " + std::to_string(of->n_offset_free));
+    const int ndo = offset_free ? of->n_offset_free : 0;
     if (s->nx < 1 || s->nx > 32) return bad("nx", "1 <= nx <= 32, got " + std::to_string(s->nx));
+    if (offset_free && s->nx + ndo > 32)
+        return bad("n_offset_free", "nx + n_offset_free <= 32, got " + std::to_string(s->nx) + " + " + std::to_string(ndo));
     if (s->nu != nout || s->nu < 0 || s->nu > 64)
         return bad("nu", "must equal the handle's nout = " + std::to_string(nout) + " (and be <= 64), got " + std::to_string(s->nu));
     if (s->nd < 0 || s->nd > 32) return bad("nd", "0 <= nd <= 32, got " + std::to_string(s->nd));
@@ -37,16 +45,24 @@ inline std::string scenario_problem(int nth, int nout, const lmpc_observer *obs,
     if (s->noise.w != 0 && s->noise.w != s->ny) return bad("noise.w", "must be ny = " + std::to_string(s->ny) + " (or 0: no noise), got " + std::to_string(s->noise.w));
     if (s->noise.H != 0) return bad("noise.H", "the noise block has no preview");
     if (s->nuprev < 0 || s->nuprev > s->nu) return bad("nuprev", "0 <= nuprev <= nu, got " + std::to_string(s->nuprev));
+    if (offset_free && !s->use_observer) return bad("use_observer", "must be non-zero: the offset-free loop runs the handle's observer");
     if (s->use_observer) {
         if (!obs) return bad("use_observer", "lmpc_set_observer has not been called on this handle");
         if (s->ny < 1) return bad("ny", "an observer needs a measurement (ny >= 1)");
-        if (obs->n_state != s->nx) return bad("nx", "the observer was set with n_state = " + std::to_string(obs->n_state) + ", the descriptor says " + std::to_string(s->nx));
+        if (offset_free && obs->n_state != s->nx + ndo)
+            return bad("n_offset_free", "the observer was set with n_state = " + std::to_string(obs->n_state) + ", the descriptor says nx + n_offset_free = " + std::to_string(s->nx + ndo));
+        if (!offset_free && obs->n_state != s->nx) return bad("nx", "the observer was set with n_state = " + std::to_string(obs->n_state) + ", the descriptor says " + std::to_string(s->nx));
         if (obs->n_control != s->nu) return bad("nu", "the observer was set with n_control = " + std::to_string(obs->n_control) + ", the descriptor says " + std::to_string(s->nu));
         if (obs->n_disturbance != s->nd) return bad("nd", "the observer was set with n_disturbance = " + std::to_string(obs->n_disturbance) + ", the descriptor says " + std::to_string(s->nd));
         if (obs->n_measurement != s->ny) return bad("ny", "the observer was set with n_measurement = " + std::to_string(obs->n_measurement) + ", the descriptor says " + std::to_string(s->ny));
     }
+    if (offset_free) {
+        const int osum = s->nx + bwidth(s->r) + (s->nd + ndo) * (s->d.H > 0 ? s->d.H : 1) + s->nuprev + bwidth(s->p);
+        if (osum != nth)
+            return bad("nth", "nx + width(r) + (nd + n_offset_free) * max(d.H, 1) + nuprev + width(p) = " + std::to_string(osum) + " must equal the handle's nth = " + std::to_string(nth));
+    }
     const int sum = s->nx + bwidth(s->r) + bwidth(s->d) + s->nuprev + bwidth(s->p);
-    if (sum != nth)
+    if (!offset_free && sum != nth)
         return bad("nth", "nx + width(r) + width(d) + nuprev + width(p) = " + std::to_string(sum) + " must equal the handle's nth = " + std::to_string(nth));
     if ((s->Y_traj || s->Ym_traj) && s->ny == 0) return bad(s->Y_traj ? "Y_traj" : "Ym_traj", "asked for with ny = 0");
     if (s->D_traj && s->nd == 0) return bad("D_traj", "asked for with nd = 0");

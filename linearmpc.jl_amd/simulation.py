@@ -5,6 +5,8 @@ at once, on the scenario loop of the library (`lmpc_simulate_scenario_device`, i
     Scenario(x0, N, r, d, p, noise)               simulation.jl:13-35; x0 (nx,) or (N_scen, nx); r, d, p, noise
                                                   (w, T) shared by all scenarios or (N_scen, w, T)
     Simulation(mpc, scenario, plant, observer)    simulation.jl:37-116 -> ts, ys, us, xs, rs, ds, xhats, yms, flag_min
+    offset_free_observer(F, G, C, ...)            setup.jl:392-448: the augmented filter of set_offset_free_observer!
+                                                  from given gains; as `observer=` it adds dhats
     evaluate_cost / constraint_violation          utils.jl:397-425, on the device
 
 Callbacks and nonlinear dynamics (`scenario.callback`, `scenario.dynamics`) have no counterpart: the plant is the
@@ -16,7 +18,8 @@ import numpy as np
 
 from .solver import BatchedQP
 
-__all__ = ["Plant", "Scenario", "Simulation", "evaluate_cost", "constraint_violation"]
+__all__ = ["Plant", "Scenario", "Simulation", "evaluate_cost", "constraint_violation", "OffsetFreeObserver",
+           "offset_free_observer"]
 
 
 class Plant:
@@ -88,24 +91,115 @@ class Scenario:
                     w=int(w_), T=int(Tc), H=int(H))
 
 
-def scenario_blocks(mpc, scenario):
+def scenario_blocks(mpc, scenario, ndo=0):
     """The four block specs of a run: column or preview follows the MPC's settings as simulation.jl:74,81,89 (and
-    the widths of theta) have it."""
+    the widths of theta) have it.  ndo: the last ndo of the controller's disturbances are an offset-free observer's
+    estimates, the scenario's d holds the measured ones alone."""
     if mpc.reference_condensation:
         raise ValueError("reference condensation is not available in the scenario loop")
     Np = mpc.Np
     specs = {
         "r": scenario.block_spec("r", Np if (mpc.reference_preview and mpc.nr > 0) else 0, mpc.ny if mpc.nr > 0 else 0),
-        "d": scenario.block_spec("d", Np if (mpc.disturbance_preview and mpc.nd > 0) else 0, mpc.nd_base),
+        "d": scenario.block_spec("d", Np if (mpc.disturbance_preview and mpc.nd > 0) else 0, mpc.nd_base - ndo),
         "p": scenario.block_spec("p", Np if (mpc.parameter_preview and mpc.np > 0) else 0, mpc.np_base),
         "noise": scenario.block_spec("noise", 0, 0),
     }
     if mpc.nr == 0:                          # no reference in theta: the trajectory only serves the cost
         specs["r"] = dict(data=None, stride=0, w=0, T=1, H=0)
-    for k, w in (("r", mpc.ny if mpc.nr > 0 else 0), ("d", mpc.nd_base), ("p", mpc.np_base)):
+    for k, w in (("r", mpc.ny if mpc.nr > 0 else 0), ("d", mpc.nd_base - ndo), ("p", mpc.np_base)):
         if specs[k]["data"] is not None and specs[k]["w"] != w:
             raise ValueError(f"{k} trajectory must have {w} rows, got {specs[k]['w']}")
     return specs
+
+
+_OFFSET_FREE_METHODS = {"state": "state_disturbance", "state_disturbance": "state_disturbance", "velocity": "velocity",
+                        "output": "output_disturbance", "output_disturbance": "output_disturbance", "general": "general"}
+
+
+class OffsetFreeObserver:
+    """The reference's OffsetFreeObserver (src/observer.jl:13-22) as arrays: the filter on [x; dhat] with
+    Faug = [F Bd; 0 I], Gaug = [G; 0], Gdaug = [Gd; 0], Caug = [C Cd], gain Kaug (nx + ndo, ny)."""
+
+    def __init__(self, Faug, Gaug, Gdaug, faug, Caug, Dd, h_offset, Kaug, nx, nd_measured, nd_offsetfree, Bd, Cd,
+                 formulation):
+        self.F, self.G, self.Gd, self.f_offset = Faug, Gaug, Gdaug, faug
+        self.C, self.Dd, self.h_offset, self.K = Caug, Dd, h_offset, Kaug
+        self.nx, self.nd_measured, self.nd_offsetfree = int(nx), int(nd_measured), int(nd_offsetfree)
+        self.Bd, self.Cd, self.formulation = Bd, Cd, formulation
+
+    def codegen_arrays(self):
+        """MPC_PLANT_DYNAMICS, MPC_MEASUREMENT_FUNCTION, K_TRANSPOSE_OBSERVER of the augmented filter
+        (src/observer.jl:139-141), flat."""
+        dyn = np.hstack([self.f_offset[:, None], self.F, self.G, self.Gd])
+        meas = np.hstack([self.h_offset[:, None], self.C, self.Dd])
+        return np.ascontiguousarray(dyn).reshape(-1), np.ascontiguousarray(meas).reshape(-1), \
+            np.ascontiguousarray(self.K.T).reshape(-1)
+
+
+def offset_free_observer(F, G, C, Gd=None, Dd=None, f_offset=None, h_offset=None, method="state_disturbance", K=None,
+                         Bd=None, Cd=None, Kx=None, Kd=None, Kaug=None):
+    """`build_offset_free_observer` (reference src/setup.jl:392-448) WITHOUT its Riccati solve: the gains are given.
+    Gd / Dd: the MEASURED disturbances' columns.  method (aliases of setup.jl:342-353): "state_disturbance" /
+    "state" and "velocity" take the nominal gain K (nx, ny) and set Bd = K, Cd = I - C K, Kx = K, Kd = I;
+    "output_disturbance" / "output" (Bd = 0, Cd = I) and "general" (Bd, Cd given) take Kx (nx, ny) and / or Kd (ndo, ny),
+    or the whole gain Kaug (nx + ndo, ny).  Refuses a disturbance model with rank([F - I Bd; C Cd]) != nx + ndo
+    (setup.jl:382-390)."""
+    if method not in _OFFSET_FREE_METHODS:
+        raise ValueError(f"Unknown offset-free method {method}")
+    method = _OFFSET_FREE_METHODS[method]
+    F = np.atleast_2d(np.asarray(F, float))
+    nx = F.shape[0]
+    G = np.asarray(G, float).reshape(nx, -1)
+    C = np.asarray(C, float).reshape(-1, nx)
+    ny = C.shape[0]
+    Gd = np.zeros((nx, 0)) if Gd is None else np.asarray(Gd, float).reshape(nx, -1)
+    ndm = Gd.shape[1]
+    Dd = np.zeros((ny, ndm)) if Dd is None else np.asarray(Dd, float).reshape(ny, ndm)
+    f_offset = np.zeros(nx) if f_offset is None else np.asarray(f_offset, float).reshape(nx)
+    h_offset = np.zeros(ny) if h_offset is None else np.asarray(h_offset, float).reshape(ny)
+    if method in ("state_disturbance", "velocity"):
+        if K is None:
+            raise ValueError(f"method {method} needs the nominal observer gain K ({nx}, {ny})")
+        K = np.asarray(K, float)
+        if K.shape != (nx, ny):
+            raise ValueError(f"K must have size ({nx}, {ny})")
+        Bd, Cd, Kx, Kd = K, np.eye(ny) - C @ K, K, np.eye(ny)
+    elif method == "output_disturbance":
+        Bd, Cd = np.zeros((nx, ny)), np.eye(ny)
+    else:
+        if Bd is None:
+            raise ValueError("Method general requires Bd")
+        if Cd is None:
+            raise ValueError("Method general requires Cd")
+    Bd, Cd = np.asarray(Bd, float), np.asarray(Cd, float)
+    if Bd.ndim != 2 or Bd.shape[0] != nx:
+        raise ValueError(f"Bd must have {nx} rows")
+    ndo = Bd.shape[1]
+    if Cd.shape != (ny, ndo):
+        raise ValueError(f"Cd must have size ({ny}, {ndo})")
+    if np.linalg.matrix_rank(np.block([[F - np.eye(nx), Bd], [C, Cd]])) != nx + ndo:
+        raise ValueError("Offset-free disturbance model violates rank([F-I Bd; C Cd]) = nx + nd")
+    if Kaug is not None:
+        Kaug = np.asarray(Kaug, float)
+        if Kaug.shape != (nx + ndo, ny):
+            raise ValueError(f"Kaug must have size ({nx + ndo}, {ny})")
+    elif Kx is not None or Kd is not None:
+        Kx = np.zeros((nx, ny)) if Kx is None else np.asarray(Kx, float)
+        Kd = np.zeros((ndo, ny)) if Kd is None else np.asarray(Kd, float)
+        if Kx.shape != (nx, ny):
+            raise ValueError(f"Kx must have size ({nx}, {ny})")
+        if Kd.shape != (ndo, ny):
+            raise ValueError(f"Kd must have size ({ndo}, {ny})")
+        Kaug = np.vstack([Kx, Kd])
+    else:
+        raise ValueError(f"method {method} needs the gains Kx / Kd or Kaug (this package solves no Riccati equation)")
+    nu = G.shape[1]
+    Faug = np.block([[F, Bd], [np.zeros((ndo, nx)), np.eye(ndo)]])
+    Gaug = np.vstack([G, np.zeros((ndo, nu))])
+    Gdaug = np.vstack([Gd, np.zeros((ndo, ndm))])
+    Caug = np.hstack([C, Cd])
+    faug = np.concatenate([f_offset, np.zeros(ndo)])
+    return OffsetFreeObserver(Faug, Gaug, Gdaug, faug, Caug, Dd, h_offset, Kaug, nx, ndm, ndo, Bd, Cd, method)
 
 
 def _observer_arrays(observer):
@@ -124,12 +218,17 @@ class Simulation:
     An `ExplicitMPC` runs the loop with its piecewise-affine law (`mode` 0, the default: lock-step, the faster form
     where both were measured; 1: run-ahead kernel; warm must be False) and adds `regions` (N_scen, N) int32, -1 = solved by the implicit path, and `stats`.
     Fields as in the reference, one leading scenario axis unless x0 was a single vector: xs, xhats (nx, N), us
-    (nu, N), ys, yms (ny, N), rs, ds, ts, and flag_min (smallest exit flag per scenario)."""
+    (nu, N), ys, yms (ny, N), rs, ds, ts, and flag_min (smallest exit flag per scenario).
+    observer = `offset_free_observer(...)`: the offset-free loop (`lmpc_simulate_scenario_offset_free_device`); the plant
+    and the scenario's d then carry the MEASURED disturbances alone (plant.nd == mpc.nd_base - ndo) and `dhats`
+    (N_scen, ndo, N), the estimate the controller saw, is added.  Not available with an `ExplicitMPC`."""
 
     def __init__(self, mpc, scenario, plant, observer=None, warm=False, cost=None, mode=0):
         import torch
         from .mpc import ExplicitMPC
         empc = mpc if isinstance(mpc, ExplicitMPC) else None
+        if empc is not None and isinstance(observer, OffsetFreeObserver):
+            raise ValueError("the offset-free observer is not available in the explicit controller's loop")
         if empc is not None:                      # simulation.jl:37 with compute_control(empc, x), utils.jl:53-60
             if empc.controller is None:
                 raise RuntimeError("Need to build a binary search tree to evaluate control law")
@@ -146,12 +245,17 @@ class Simulation:
         T, S = scenario.N, scenario.n_scen
         if plant.nx != mpc.nx or plant.nu != mpc.nu:
             raise ValueError("plant and controller disagree on nx / nu")
-        if plant.nd != mpc.nd_base:
-            raise ValueError(f"the plant has {plant.nd} disturbances, the controller's theta {mpc.nd_base}")
+        off = observer if isinstance(observer, OffsetFreeObserver) else None
+        ndo = 0 if off is None else off.nd_offsetfree
+        if off is not None and off.nx != plant.nx:
+            raise ValueError("plant and offset-free observer disagree on nx")
+        if plant.nd != mpc.nd_base - ndo:
+            raise ValueError(f"the plant has {plant.nd} disturbances, the controller's theta {mpc.nd_base}"
+                             + (f" of which {ndo} are estimated" if ndo else ""))
         obs = _observer_arrays(observer)
         if obs is not None:
-            model.set_observer(*obs, plant.nx, plant.nu, plant.nd, plant.ny)
-        specs = scenario_blocks(mpc, scenario)
+            model.set_observer(*obs, plant.nx + ndo, plant.nu, plant.nd, plant.ny)
+        specs = scenario_blocks(mpc, scenario, ndo)
         up = lambda sp: None if sp["data"] is None else torch.from_numpy(np.swapaxes(sp["data"], -1, -2).copy()).to(dev)
         x = torch.from_numpy(scenario.x0.copy()).to(dev)
         uprev = None
@@ -159,20 +263,31 @@ class Simulation:
             uprev = torch.from_numpy(np.tile(np.asarray(uprev0, float)[:mpc.nuprev], (S, 1))).to(dev)
         run = model.simulate_scenario if empc is None else \
             (lambda *a, **kw: empc.controller.simulate_scenario_device(*a, mode=mode, **kw))
-        out = run(
-            x, T, plant.dynamics_rows(), plant.measurement_rows(), nd=plant.nd, ny=plant.ny,
-            r=up(specs["r"]), d=up(specs["d"]), p=up(specs["p"]), noise=up(specs["noise"]),
-            r_preview=specs["r"]["H"], d_preview=specs["d"]["H"], p_preview=specs["p"]["H"],
-            r_width=specs["r"]["w"], d_width=specs["d"]["w"], p_width=specs["p"]["w"], uprev=uprev,
-            use_observer=obs is not None, warm=warm, cost=cost,
-            want=("U", "X", "Y", "Ym", "Xhat") + (("D",) if plant.nd else ()),
-            want_cost=cost is not None, want_violation=cost is not None and cost[0].nc > 0)
+        want = ("U", "X", "Y", "Ym", "Xhat") + (("D",) if plant.nd else ())
+        if off is not None:                       # simulation.jl:37-116 with an OffsetFreeObserver (observer.jl:203-225)
+            out = model.simulate_scenario_offset_free(
+                x, T, plant.dynamics_rows(), plant.measurement_rows(), ndo, nd=plant.nd, ny=plant.ny,
+                r=up(specs["r"]), d=up(specs["d"]), p=up(specs["p"]), noise=up(specs["noise"]),
+                r_preview=specs["r"]["H"], d_preview=specs["d"]["H"], p_preview=specs["p"]["H"],
+                r_width=specs["r"]["w"], p_width=specs["p"]["w"], uprev=uprev, warm=warm, cost=cost,
+                want=want + ("Dhat",), want_cost=cost is not None, want_violation=cost is not None and cost[0].nc > 0)
+        else:
+            out = run(
+                x, T, plant.dynamics_rows(), plant.measurement_rows(), nd=plant.nd, ny=plant.ny,
+                r=up(specs["r"]), d=up(specs["d"]), p=up(specs["p"]), noise=up(specs["noise"]),
+                r_preview=specs["r"]["H"], d_preview=specs["d"]["H"], p_preview=specs["p"]["H"],
+                r_width=specs["r"]["w"], d_width=specs["d"]["w"], p_width=specs["p"]["w"], uprev=uprev,
+                use_observer=obs is not None, warm=warm, cost=cost, want=want,
+                want_cost=cost is not None, want_violation=cost is not None and cost[0].nc > 0)
         torch.cuda.synchronize(dev)
         model.check()
         per = lambda t: np.ascontiguousarray(t.cpu().numpy().transpose(1, 2, 0))      # (T, S, w) -> (S, w, T)
         self.xs, self.us = per(out["X"][:T]), per(out["U"])
         self.ys, self.yms, self.xhats = per(out["Y"]), per(out["Ym"]), per(out["Xhat"])
         self.ds = per(out["D"]) if plant.nd else np.zeros((S, 0, T))
+        if off is not None:
+            self.dhats = per(out["Dhat"])
+            self.xaug_final = out["xaug"].cpu().numpy() if out["xaug"] is not None else None
         rs = scenario.trajectory("r", mpc.ny)
         self.rs = np.broadcast_to(rs, (S,) + rs.shape[-2:]).copy()
         self.x_final = out["x"].cpu().numpy()
@@ -184,7 +299,7 @@ class Simulation:
             self.regions = np.ascontiguousarray(out["regions"].cpu().numpy().T)
             self.stats = out["stats"]
         if scenario.single:
-            for k in ("xs", "us", "ys", "yms", "xhats", "ds", "rs"):
+            for k in ("xs", "us", "ys", "yms", "xhats", "ds", "rs") + (("dhats",) if off is not None else ()):
                 setattr(self, k, getattr(self, k)[0])
 
 

@@ -609,6 +609,71 @@ class BatchedQP:
         out["_keep"] = keep                      # the launches are asynchronous: keep the sources alive
         return out
 
+    def offset_free_check(self, desc, n_offset_free, observer_dims="handle"):
+        """`lmpc_scenario_offset_free_check` of a descriptor against this handle's dimensions (host only)."""
+        od = getattr(self, "_obs", None) if observer_dims == "handle" else observer_dims
+        o = None if od is None else ctypes.byref(Observer(*[int(v) for v in od], None, None, None))
+        of = _cabi.OffsetFree(int(n_offset_free), None)
+        check(lib().lmpc_scenario_offset_free_check(self.nth, self.nout, o, ctypes.byref(desc), ctypes.byref(of)))
+
+    def simulate_scenario_offset_free(self, x, T, plant, measurement, n_offset_free, nd=0, ny=0, r=None, d=None, p=None,
+                                      noise=None, r_preview=0, d_preview=0, p_preview=0, r_width=0, p_width=0, xaug=None,
+                                      uprev=None, warm=False, cost=None, want=("U", "X"), want_cost=False,
+                                      want_violation=False, stream=None):
+        """The scenario loop with the offset-free observer (`lmpc_simulate_scenario_offset_free_device`): as
+        `simulate_scenario`, with the handle's observer (`set_observer`, the AUGMENTED filter of nx + n_offset_free
+        states) always in the loop.  nd: the MEASURED disturbances (rows of d, columns of the plant's Gd / Dd); the
+        d block of theta is max(d_preview, 1) columns [d; dhat].  xaug (N, nx + n_offset_free) or None = [x; 0].
+        want: any of "U", "X", "Y", "Ym", "Xhat", "D", "Dhat".  Returns the dict of `simulate_scenario` plus xaug."""
+        import torch
+        f64, dv = torch.float64, self.device
+        if not (x.is_cuda and x.dtype == f64 and x.is_contiguous() and x.dim() == 2 and x.device.index == dv):
+            raise ValueError("x must be a contiguous float64 CUDA tensor of shape (N, nx) on this handle's GPU")
+        N, nx = int(x.shape[0]), int(x.shape[1])
+        dev, nu, T, ndo = x.device, self.nout, int(T), int(n_offset_free)
+        keep = []
+
+        def block(t, w0, H):
+            if t is None:
+                return Block(None, 0, int(w0), 1, 0, int(H)) if (w0 or H) else None
+            if t.dim() == 3 and t.shape[0] != N:
+                raise ValueError("a per-scenario trajectory must have shape (N, w, T)")
+            b, k = self._block(t.to(dev), H, 0)
+            keep.append(k)
+            return b
+
+        br, bd = block(r, r_width, r_preview), block(d, 0, d_preview)       # no d: width 0, the preview length kept
+        bp, bn = block(p, p_width, p_preview), block(noise, 0, 0)
+        wid = lambda b: 0 if b is None else b.w * (b.H if b.H > 0 else 1)
+        nup = self.nth - nx - wid(br) - (int(nd) + ndo) * max(int(d_preview), 1) - wid(bp)
+        if uprev is None and 0 < nup <= nu:
+            uprev = torch.zeros((N, nup), dtype=f64, device=dev)
+        nup = 0 if uprev is None else int(uprev.shape[1])
+        out = dict(x=x, xaug=xaug, uprev=uprev, flag_min=torch.empty(N, dtype=torch.int32, device=dev))
+        shapes = dict(U=(T, N, nu), X=(T + 1, N, nx), Y=(T, N, ny), Ym=(T, N, ny), Xhat=(T, N, nx), D=(T, N, nd),
+                      Dhat=(T, N, ndo))
+        for k in want:
+            out[k] = torch.empty(shapes[k], dtype=f64, device=dev)
+        desc, hk = self.scenario_descriptor(plant, nx, nd, measurement, ny, br, bd, bp, bn, nup, True, warm, cost)
+        keep.append(hk)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        desc.Y_traj, desc.Ym_traj = ptr(out.get("Y")), ptr(out.get("Ym"))
+        desc.Xhat_traj, desc.D_traj = ptr(out.get("Xhat")), ptr(out.get("D"))
+        of = _cabi.OffsetFree(ndo, ptr(out.get("Dhat")))
+        if want_cost:
+            out["cost"] = torch.empty(N, dtype=f64, device=dev)
+            desc.cost_out = out["cost"].data_ptr()
+        if want_violation:
+            out["violation"] = torch.empty(N, dtype=f64, device=dev)
+            desc.violation_out = out["violation"].data_ptr()
+        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        check(lib().lmpc_simulate_scenario_offset_free_device(
+            self._h, N, T, ctypes.byref(desc), ctypes.byref(of), _vp(x.data_ptr()),
+            _dev_arg(xaug, "xaug", f64, N * (nx + ndo), dv), _dev_arg(uprev, "uprev", f64, N * nup, dv),
+            _vp(ptr(out.get("U"))), _vp(ptr(out.get("X"))), _vp(out["flag_min"].data_ptr()), _vp(st)), self._h)
+        out["_keep"] = keep                      # the launches are asynchronous: keep the sources alive
+        return out
+
     def evaluate_cost_device(self, X, U, cost, r=None, stream=None):
         """`lmpc_evaluate_cost_device`: X (>= T, N, nx) and U (T, N, nu) step-major CUDA tensors, cost =
         `sim_cost(...)`, r as in `simulate_scenario`.  Returns the (N,) cost tensor (not synchronised)."""
