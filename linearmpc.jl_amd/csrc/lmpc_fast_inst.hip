@@ -54,6 +54,14 @@ static int launch_fast_t(lmpc_handle *h, int64_t nprob, const double *theta, dou
     // (tools/hot_ab.py, same box) -- the tickets' device-scope atomics cost what the levelling saves.
     int D = GATHER ? 0 : (h->fastDyn >= 0 ? h->fastDyn : 0);
     if (R < 12 || nprob >= (int64_t)0x7fffff00 || D >= R) D = 0;
+    // A ticket of counter c stands for tile nstat + ticket * kFastCtrs + c, and streaming wavefront w of the grid draws
+    // from counter w mod kFastCtrs only: a grid of fewer than kFastCtrs streaming wavefronts leaves the counters nobody
+    // draws from -- and their tiles -- unvisited (one workgroup, 12 tiles, "fast_dyn" 4: tile 11 was never screened, its
+    // outputs never written).  Such a grid keeps the tail only if the tail is no longer than its wavefronts are many.
+    if (D) {
+        const long long nstat = (long long)grid * (R - D) < ntiles ? (long long)grid * (R - D) : ntiles;
+        if ((long long)grid * nstr < kFastCtrs && ntiles - nstat > (long long)grid * nstr) D = 0;
+    }
     const int Rs = R - D, Dcap = 3 * D, Rq = D ? Rs + Dcap + 1 : R;      // (+ 1: the batch's partial tile, first workgroup)
     // streaming wavefronts take their records by LDS-DMA into a ring of dk tile slots each ("fast_dma": 0 = through
     // registers, 2 / 3 = ring depth; default LMPC_FAST_DMA_DEPTH); the generated controller's gather stays on registers
