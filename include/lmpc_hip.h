@@ -843,6 +843,76 @@ int lmpc_simulate_scenario_offset_free_device(lmpc_handle *h, int64_t N, int T, 
 int lmpc_simulate_scenario_offset_free(lmpc_handle *h, int64_t N, int T, const lmpc_scenario_sim *s,
                                        const lmpc_offset_free *of, double *x, double *xaug, double *uprev, double *U_traj,
                                        double *X_traj, int32_t *flag_min);
+/*
+ * The scenario loop UNDER UNCERTAINTY: what the reference's users put into the plant hook of its Simulation
+ * (`Simulation(dynamics, mpc)`, `scenario.dynamics`, src/simulation.jl:40,110,118-126) wherever its manual, examples and
+ * tests use it -- additive process noise on the state (docs/src/manual/robust.md:17,78, example/robust.jl:5,25,
+ * example/observer.jl:11) and a plant that is not the controller's model (test/runtests.jl:992,1081) -- for N scenarios
+ * in one call, with the draws made on the device.  A side struct next to the unchanged lmpc_scenario_sim.
+ *
+ * Step k (0-based), per scenario i; everything not said here is lmpc_simulate_scenario_device, sum for sum:
+ *   PRE   ym as there; then ym_j <- ym_j + v_j as the LAST addition (the place s->noise has, with which `measurement`
+ *         is exclusive).
+ *   POST  cost, violation and the observer's predict as there: the observer predicts with the handle's model and sees
+ *         no w.  x <- the row sums of THIS SCENARIO's plant array; then for each row a, onto the finished row sum and in
+ *         index order, x_a <- x_a + Gw_a0 * e_0 + Gw_a1 * e_1 + ... with separate multiply and add (Gw == NULL:
+ *         x_a <- x_a + e_a).
+ *   W_traj T x N x nx (DEVICE, optional): row a holds 0 + Gw_a0 * e_0 + ... in the same order (Gw == NULL: e_a).
+ * A source (process e_k with process.w components, measurement v_k with ny) is one of
+ *   supplied  lo == NULL: column k of the block `src` (w rows, H must be 0, per scenario or shared, held at its last
+ *             column; k counts from THIS call's first step); src.src == NULL gives zeros;
+ *   drawn     lo, hi (HOST, w each): uniform in [lo_q, hi_q] from Philox4x32-10 (Salmon, Moraes, Dror, Shaw, SC'11;
+ *             multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85) with
+ *             key (seed & 0xffffffff, seed >> 32) and counter (g & 0xffffffff, g >> 32, step_offset + k,
+ *             (stream << 16) | j), g = scenario_offset + i, stream 0 = process and 1 = measurement, j the PAIR index:
+ *             components 2j and 2j + 1 come from the output words (0, 1) and (2, 3).  From a word pair (a, b):
+ *             u = (double)(((uint64_t)a << 21) | (b >> 11)) * 2^-53, exact and in [0, 1);  e_q = min(hi_q, lo_q + u *
+ *             span_q), span_q = hi_q - lo_q formed once on the host in binary64, one multiply and one add.
+ * A draw depends on (seed, global scenario, global step, stream, component) and on nothing of the launch: a run split
+ * over calls by scenario (scenario_offset) or by time (step_offset, with x / xhat / uprev carried over and the
+ * trajectories shifted by the caller) reproduces the unsplit one bit for bit.  GAUSSIAN draws are deliberately not
+ * made on the device: log, cos and sqrt of the device library cannot be restated bit for bit on a host, and a closed
+ * loop turns a last-bit difference into another active set; Gaussian noise (example/observer.jl) goes through the
+ * supplied block, drawn by the caller, with Gw = B.
+ * Plant ensemble: n_plants > 0 arrays in the layout of s->plant, one after the other (HOST), staged once per call;
+ * scenario i steps array plant_index[i] (DEVICE, N entries), or (scenario_offset + i) mod n_plants with plant_index
+ * NULL.  An entry is taken as UNSIGNED, modulo n_plants: no entry addresses outside the staged table.  n_plants == 0:
+ * s->plant for every scenario.  The ensemble shares ONE measurement (s->measurement).
+ * Every source absent and n_plants == 0 runs and is lmpc_simulate_scenario_device bit for bit.
+ * Refused (LMPC_ERR_BADARG, the field's name first, before the GPU is touched): all that lmpc_scenario_check refuses; un
+ * NULL; a negative w; lo without hi or the reverse; lo_q > hi_q or a non-finite bound; src.H != 0; process.w not in
+ * {0, nx} with Gw NULL; measurement.w not in {0, ny}; measurement.w > 0 with s->noise.w > 0; n_plants < 0; n_plants > 0
+ * with plants NULL; plant_index with n_plants == 0; W_traj with process.w == 0; step_offset < 0, or step_offset + T
+ * beyond 2^31 - 1 (the call alone knows T).  lmpc_scenario_uncertain_check asks that without a handle.
+ * lmpc_simulate_scenario_uncertain: the HOST twin (the sources' blocks, plant_index and W_traj HOST as well).
+ * NOT extended: the offset-free loop and the explicit controller's loop.
+ */
+typedef struct lmpc_noise {              /* one noise source                                                      */
+    int32_t w;                           /* components; 0 = absent                                                */
+    lmpc_block src;                      /* DEVICE, supplied draws: w rows, column k at step k, H must be 0; read
+                                          * when lo == NULL (src.src == NULL then gives zeros)                    */
+    const double *lo, *hi;               /* HOST, w each: drawn on the device, uniform in [lo_q, hi_q]; both or none */
+} lmpc_noise;
+typedef struct lmpc_uncertainty {
+    lmpc_noise process;                  /* e_k, nw = process.w components                                        */
+    const double *Gw;                    /* HOST nx x nw row-major: w_k = Gw e_k; NULL = identity, then nw == nx   */
+    lmpc_noise measurement;              /* v_k, ny components, added to ym; exclusive with s->noise              */
+    uint64_t seed;
+    int64_t scenario_offset;             /* global index of scenario 0 of this call (sharded runs)                */
+    int32_t step_offset;                 /* global index of step 0 of this call (continued runs)                  */
+    int32_t n_plants;                    /* 0 = the descriptor's `plant` for every scenario                       */
+    const double *plants;                /* HOST, n_plants arrays in the layout of s->plant, one after the other  */
+    const int32_t *plant_index;          /* DEVICE, N entries, or NULL = (scenario_offset + i) mod n_plants       */
+    double *W_traj;                      /* DEVICE T x N x nx, optional: the w_k that acted                       */
+} lmpc_uncertainty;
+int lmpc_scenario_uncertain_check(int nth, int nout, const lmpc_observer *observer, const lmpc_scenario_sim *s,
+                                  const lmpc_uncertainty *un);
+int lmpc_simulate_scenario_uncertain_device(lmpc_handle *h, int64_t N, int T, const lmpc_scenario_sim *s,
+                                            const lmpc_uncertainty *un, double *x, double *xhat, double *uprev,
+                                            double *U_traj, double *X_traj, int32_t *flag_min, void *stream);
+int lmpc_simulate_scenario_uncertain(lmpc_handle *h, int64_t N, int T, const lmpc_scenario_sim *s,
+                                     const lmpc_uncertainty *un, double *x, double *xhat, double *uprev, double *U_traj,
+                                     double *X_traj, int32_t *flag_min);
 /* Scoring of a stored run, one thread per scenario: X = the states x_0 .. x_{T-1}, step-major (the first T slices of an
  * X_traj), U = T x N x nu as U_traj.  r: the reference trajectory as in the loop (column k at step k; NULL = zeros).
  * cost_out: N doubles.  violation_out: N doubles (maximum over the steps) and / or violation_steps: T x N, the

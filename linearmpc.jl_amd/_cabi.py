@@ -40,6 +40,7 @@ SYMBOLS = (
     "lmpc_constraint_violation_device",
     "lmpc_explicit_scenario_check", "lmpc_explicit_simulate_scenario_device", "lmpc_explicit_simulate_scenario",
     "lmpc_scenario_offset_free_check", "lmpc_simulate_scenario_offset_free_device", "lmpc_simulate_scenario_offset_free",
+    "lmpc_scenario_uncertain_check", "lmpc_simulate_scenario_uncertain_device", "lmpc_simulate_scenario_uncertain",
 )
 
 
@@ -99,6 +100,18 @@ class ScenarioSim(ctypes.Structure):
 class OffsetFree(ctypes.Structure):
     """`lmpc_offset_free`: the offset-free part of a scenario run (lmpc_simulate_scenario_offset_free*)."""
     _fields_ = [("n_offset_free", ctypes.c_int32), ("Dhat_traj", ctypes.c_void_p)]
+
+
+class Noise(ctypes.Structure):
+    """`lmpc_noise`: one noise source of the uncertain scenario loop, supplied (`src`) or drawn in the box [lo, hi]."""
+    _fields_ = [("w", ctypes.c_int32), ("src", Block), ("lo", ctypes.c_void_p), ("hi", ctypes.c_void_p)]
+
+
+class Uncertainty(ctypes.Structure):
+    """`lmpc_uncertainty`: process / measurement noise and the plant table (lmpc_simulate_scenario_uncertain*)."""
+    _fields_ = [("process", Noise), ("Gw", ctypes.c_void_p), ("measurement", Noise), ("seed", ctypes.c_uint64),
+                ("scenario_offset", ctypes.c_int64), ("step_offset", ctypes.c_int32), ("n_plants", ctypes.c_int32),
+                ("plants", ctypes.c_void_p), ("plant_index", ctypes.c_void_p), ("W_traj", ctypes.c_void_p)]
 
 
 _lib = None
@@ -248,6 +261,13 @@ def lib():
     L.lmpc_simulate_scenario_offset_free_device.restype = i32
     L.lmpc_simulate_scenario_offset_free.argtypes = [vp, i64, i32, sp, op] + [vp] * 6
     L.lmpc_simulate_scenario_offset_free.restype = i32
+    up = ctypes.POINTER(Uncertainty)
+    L.lmpc_scenario_uncertain_check.argtypes = [i32, i32, ctypes.POINTER(Observer), sp, up]
+    L.lmpc_scenario_uncertain_check.restype = i32
+    L.lmpc_simulate_scenario_uncertain_device.argtypes = [vp, i64, i32, sp, up] + [vp] * 7
+    L.lmpc_simulate_scenario_uncertain_device.restype = i32
+    L.lmpc_simulate_scenario_uncertain.argtypes = [vp, i64, i32, sp, up] + [vp] * 6
+    L.lmpc_simulate_scenario_uncertain.restype = i32
     _lib = L
     return L
 

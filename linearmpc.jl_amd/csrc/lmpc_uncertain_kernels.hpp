@@ -1,0 +1,232 @@
+// Glue kernels of the uncertain scenario loop (lmpc_simulate_scenario_uncertain_device): the scenario loop of
+// lmpc_scenario_kernels.hpp with what the reference's users put into `scenario.dynamics` (reference
+// src/simulation.jl:40,110,118-126; docs/src/manual/robust.md:17,78; example/observer.jl:11) -- additive process noise
+// w_k = Gw e_k on the state, additive measurement noise v_k, and a table of plant variants one of which steps each
+// scenario.  e_k and v_k are either read from a supplied block or drawn here, uniform in a box, from a counter-based
+// generator: a draw depends on (seed, global scenario, global step, stream, component) and on nothing of the launch.
+//
+// The sums are the ones of the scenario loop, called, not restated: correct_row and dynamics_rows, block_at /
+// block_entry, scn_step_cost / scn_step_violation, step_tail.  The measurement sum is inline in scenario_pre_kernel, so
+// uncertain_pre_kernel carries its fourth copy (scenario_pre_kernel, offset_free_pre_kernel, explicit_sim_run_kernel).
+// With every source absent and no plant table both kernels execute the arithmetic of scenario_pre_kernel /
+// scenario_post_kernel operation for operation.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "lmpc_scenario_kernels.hpp"
+
+namespace lmpc {
+
+// Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11), written out: ten
+// rounds of two 32 x 32 -> 64 bit multiplies, the key bumped between rounds.  Counter c[0..3] in, output in place.
+__host__ __device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int round = 0; round < 10; round++) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
+        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0;
+        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
+        c[1] = (uint32_t)p1;
+        c[3] = (uint32_t)p0;
+        c[0] = n0;
+        c[2] = n2;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+}
+
+// a word pair -> [0, 1): the 53 bits (a << 21) | (b >> 11) times 2^-53, exact
+__host__ __device__ __forceinline__ double philox_unit(uint32_t a, uint32_t b) {
+    return (double)(((uint64_t)a << 21) | (uint64_t)(b >> 11)) * 0x1.0p-53;
+}
+
+// one noise source: a supplied block (drawn == 0: column k of src, absent = zeros) or the box [lo, hi] in ScnConst::c
+struct UncSource {
+    ThetaBlock src;
+    int w, drawn;
+    int lo, span, hi;                 // offsets in doubles into ScnConst::c; span = hi - lo formed on the host
+};
+
+// what one step's launches know of the uncertainty
+struct UncStep {
+    UncSource process, meas;
+    int gw;                           // offset of Gw (nx x nw row-major) in ScnConst::c, -1 = identity
+    uint32_t key0, key1;              // seed & 0xffffffff, seed >> 32
+    uint32_t step;                    // step_offset + k
+    unsigned long long goff;          // scenario_offset
+    int n_plants;                     // 0 = ScnConst::plant for everyone; else the table starts at ScnConst::plant
+    const int32_t *plant_index;       // N entries or nullptr = (scenario_offset + i) mod n_plants
+    double *w_out;                    // this step's slice of W_traj or nullptr
+};
+
+// The draws of one (scenario, step, stream), component after component: counter (g lo, g hi, step, stream << 16 | j)
+// gives components 2j (words 0, 1) and 2j + 1 (words 2, 3); a block is computed when its first component is asked
+// for, so an odd count uses half of the last one.  No array: the four words live in registers.
+struct UncDraws {
+    uint32_t g0, g1, step, stream, k0, k1;
+    uint32_t r0, r1, r2, r3;
+    int j;
+    __device__ __forceinline__ UncDraws(const UncStep &U, long long i, uint32_t stream_)
+        : step(U.step), stream(stream_), k0(U.key0), k1(U.key1), r0(0), r1(0), r2(0), r3(0), j(-1) {
+        const unsigned long long g = U.goff + (unsigned long long)i;
+        g0 = (uint32_t)g; g1 = (uint32_t)(g >> 32);
+    }
+    __device__ __forceinline__ double unit(int q) {
+        if ((q >> 1) != j) {
+            j = q >> 1;
+            uint32_t c[4] = {g0, g1, step, (stream << 16) | (uint32_t)j};
+            philox4x32_10(c, k0, k1);
+            r0 = c[0]; r1 = c[1]; r2 = c[2]; r3 = c[3];
+        }
+        return (q & 1) ? philox_unit(r2, r3) : philox_unit(r0, r1);
+    }
+};
+
+// component q of a source at step k for scenario i: e = min(hi, lo + u * span), one multiply and one add
+__device__ __forceinline__ double unc_value(const UncSource &S, const double *__restrict__ c, UncDraws &D, long long i, int k, int q) {
+    if (!S.drawn) return block_at(S.src, i, k, q);
+    const double e = __dadd_rn(c[S.lo + q], __dmul_rn(D.unit(q), c[S.span + q]));
+    const double hi = c[S.hi + q];
+    return e < hi ? e : hi;
+}
+
+// PRE kernel of step k: scenario_pre_kernel with v_j added to ym_j as the last addition (the place the descriptor's
+// noise block has; the two are exclusive).  Same two phases, same 256 * nx doubles of dynamic LDS.
+template <int NXT>
+__global__ __launch_bounds__(256) void uncertain_pre_kernel(ScnPre A, ScnConst K, UncStep U) {
+    extern __shared__ double unc_lds[];
+    constexpr int NXA = NXT > 0 ? NXT : 32;
+    const int nx = NXT > 0 ? NXT : A.nx;
+    const long long base = (long long)blockIdx.x * 256;
+    const long long i = base + threadIdx.x;
+    if (i < A.n) {
+        double xo[NXA], xh[NXA], xn[NXA];
+        auto dk = [&](int q) { return block_at(A.d, i, A.k, q); };
+        for_nx<NXT>(nx, [&](int c) { xo[c] = A.x[i * nx + c]; });
+        const bool obs = A.xhat != nullptr;
+        if (obs) for_nx<NXT>(nx, [&](int c) { xh[c] = A.xhat[i * nx + c]; xn[c] = xh[c]; });
+        else for_nx<NXT>(nx, [&](int c) { xn[c] = xo[c]; });
+        const int ms = 1 + nx + A.nd;
+        UncDraws dv(U, i, 1u);
+        for (int j = 0; j < A.ny; j++) {
+            const double *mr = K.c + K.meas + j * ms;
+            double ym = mr[0], y = 0.0;
+            for_nx<NXT>(nx, [&](int c) {
+                const double t = __dmul_rn(mr[1 + c], xo[c]);
+                ym = __dadd_rn(ym, t); y = __dadd_rn(y, t);
+            });
+            for (int q = 0; q < A.nd; q++) {
+                const double t = __dmul_rn(mr[1 + nx + q], dk(q));
+                ym = __dadd_rn(ym, t); y = __dadd_rn(y, t);
+            }
+            if (A.noise.w > 0) ym = __dadd_rn(ym, block_at(A.noise, i, A.k, j));
+            if (U.meas.w > 0) ym = __dadd_rn(ym, unc_value(U.meas, K.c, dv, i, A.k, j));
+            if (A.ym_out) A.ym_out[i * A.ny + j] = ym;
+            if (A.y_out) A.y_out[i * A.ny + j] = obs ? y : ym;
+            if (obs) correct_row<NXT>(A.obs_meas + j * ms, A.obs_kt + j * nx, ym, xh, xn, nx, A.nd, dk);
+        }
+        for_nx<NXT>(nx, [&](int c) {
+            if (obs) A.xhat[i * nx + c] = xn[c];
+            if (A.xhat_out) A.xhat_out[i * nx + c] = xn[c];
+        });
+        for_nx<NXT>(nx, [&](int c) { unc_lds[threadIdx.x * nx + c] = xn[c]; });
+        if (A.d_out) for (int q = 0; q < A.nd; q++) A.d_out[i * A.nd + q] = dk(q);
+    }
+    __syncthreads();
+    const int nr = A.r.width(), ndw = A.d.width(), npw = A.p.width();
+    const int nth = nx + nr + ndw + A.nup + npw;
+    const long long left = A.n - base;
+    const int rows = left < 256 ? (int)left : 256;
+    for (int idx = threadIdx.x; idx < rows * nth; idx += 256) {
+        const int sl = idx / nth;
+        int e = idx - sl * nth;
+        const long long s = base + sl;
+        double v;
+        if (e < nx) v = unc_lds[sl * nx + e];
+        else if ((e -= nx) < nr) v = block_entry(A.r, s, e);
+        else if ((e -= nr) < ndw) v = block_entry(A.d, s, e);
+        else if ((e -= ndw) < A.nup) v = A.uprev[s * A.nup + e];
+        else v = block_entry(A.p, s, e - A.nup);
+        A.theta[base * nth + idx] = v;
+    }
+}
+
+// POST kernel of step k: scenario_post_kernel with the scenario's own plant rows (table + idx * nx * (1 + nx + nu + nd);
+// a plant_index entry is taken as unsigned, modulo n_plants, so no entry addresses outside the table), and then, onto
+// the finished row sums, x_a <- x_a + Gw_a0 e_0 + Gw_a1 e_1 + ... term by term (x_a <- x_a + e_a without Gw).  W_traj:
+// row a = 0 + Gw_a0 e_0 + ... in the same order, or e_a.  The terms are visited component by component (one draw per
+// component) with the rows' running sums side by side, which is the same order of additions for every row.
+template <int NXT, bool COST>
+__global__ __launch_bounds__(256) void uncertain_post_kernel(ScnPost A, ScnConst K, UncStep U) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= A.n) return;
+    constexpr int NXA = NXT > 0 ? NXT : 32;
+    const int nx = NXT > 0 ? NXT : A.nx;
+    const int nu = A.nu;
+    const double *u = A.u + i * nu;
+    auto dk = [&](int q) { return block_at(A.d, i, A.k, q); };
+    double xo[NXA], xn[NXA];
+    for_nx<NXT>(nx, [&](int c) { xo[c] = A.x[i * nx + c]; });
+    if constexpr (COST) {
+        if (A.cost) {
+            double ul[64];
+            if (K.cRr >= 0) for (int l = 0; l < nu; l++) ul[l] = A.first ? 0.0 : A.ulast[i * nu + l];
+            double us[64];
+            for (int l = 0; l < nu; l++) us[l] = u[l];
+            const double c = scn_step_cost(K, xo, nx, us, ul, nu, A.r, i, A.k);
+            const double run = __dadd_rn(A.first ? 0.0 : A.cost[i], c);
+            A.cost[i] = A.last ? __dmul_rn(0.5, run) : run;
+            if (K.cRr >= 0 && !A.last) for (int l = 0; l < nu; l++) A.ulast[i * nu + l] = us[l];
+        }
+        if (A.viol) {
+            double us[64];
+            for (int l = 0; l < nu; l++) us[l] = u[l];
+            const double w = scn_step_violation(K, xo, nx, us, nu);
+            const double old = A.first ? 0.0 : A.viol[i];
+            A.viol[i] = w > old ? w : old;
+        }
+    }
+    if (A.xhat) {
+        double ho[NXA], hn[NXA];
+        for_nx<NXT>(nx, [&](int c) { ho[c] = A.xhat[i * nx + c]; });
+        dynamics_rows<NXT>(A.obs_dyn, ho, hn, nx, nu, A.nd, u, dk);
+        for_nx<NXT>(nx, [&](int c) { A.xhat[i * nx + c] = hn[c]; });
+    }
+    long long prow = 0;
+    if (U.n_plants > 0) {
+        const unsigned long long g = U.plant_index ? (unsigned long long)(uint32_t)U.plant_index[i] : U.goff + (unsigned long long)i;
+        prow = (long long)(g % (unsigned long long)U.n_plants) * ((long long)nx * (1 + nx + nu + A.nd));
+    }
+    dynamics_rows<NXT>(K.c + K.plant + prow, xo, xn, nx, nu, A.nd, u, dk);
+    const int nw = U.process.w;
+    if (nw > 0) {
+        UncDraws de(U, i, 0u);
+        if (U.gw < 0) {
+            for_nx<NXT>(nx, [&](int a) {
+                const double e = unc_value(U.process, K.c, de, i, A.k, a);
+                xn[a] = __dadd_rn(xn[a], e);
+                if (U.w_out) U.w_out[i * nx + a] = e;
+            });
+        } else {
+            const double *gw = K.c + U.gw;
+            double wv[NXA];
+            for_nx<NXT>(nx, [&](int a) { wv[a] = 0.0; });
+            for (int q = 0; q < nw; q++) {
+                const double e = unc_value(U.process, K.c, de, i, A.k, q);
+                for_nx<NXT>(nx, [&](int a) {
+                    const double t = __dmul_rn(gw[a * nw + q], e);
+                    xn[a] = __dadd_rn(xn[a], t);
+                    wv[a] = __dadd_rn(wv[a], t);
+                });
+            }
+            if (U.w_out) for_nx<NXT>(nx, [&](int a) { U.w_out[i * nx + a] = wv[a]; });
+        }
+    }
+    for_nx<NXT>(nx, [&](int a) { A.x[i * nx + a] = xn[a]; });
+    if (A.xtraj_next) for_nx<NXT>(nx, [&](int a) { A.xtraj_next[i * nx + a] = xn[a]; });
+    step_tail(i, u, nu, A.uprev + i * A.nup, (double *)nullptr, A.nup, A.utraj, A.flag, A.flag_min, A.first);
+}
+
+}  // namespace lmpc

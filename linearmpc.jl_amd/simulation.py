@@ -8,9 +8,16 @@ at once, on the scenario loop of the library (`lmpc_simulate_scenario_device`, i
     offset_free_observer(F, G, C, ...)            setup.jl:392-448: the augmented filter of set_offset_free_observer!
                                                   from given gains; as `observer=` it adds dhats
     evaluate_cost / constraint_violation          utils.jl:397-425, on the device
+    Uniform(lo, hi)                               a noise source drawn on the device, uniform in the box [lo, hi]
 
-Callbacks and nonlinear dynamics (`scenario.callback`, `scenario.dynamics`) have no counterpart: the plant is the
-affine one the kernels step.  An MPC with reference condensation is refused (its theta block is not a cut of r).
+Of the reference's plant hook (`Simulation(dynamics, mpc)`, `scenario.dynamics`) the two uses its manual, examples and
+tests make are covered (`lmpc_simulate_scenario_uncertain_device`): additive process noise on the state --
+`Scenario(process_noise=)` with `Simulation(Gw=, seed=)` -- and plants that are not the controller's model -- a list
+of `Plant`s.  Draws made on the device are uniform (`Uniform`); Gaussian noise (example/observer.jl) is drawn by the
+caller and given as an array, with Gw = B: the device library's log / cos / sqrt cannot be restated bit for bit on a
+host.  Callbacks and nonlinear dynamics (`scenario.callback`, a general `scenario.dynamics`) have no counterpart: the
+plant is the affine one the kernels step.  An MPC with reference condensation is refused (its theta block is not a
+cut of r).
 """
 from __future__ import annotations
 
@@ -19,7 +26,7 @@ import numpy as np
 from .solver import BatchedQP
 
 __all__ = ["Plant", "Scenario", "Simulation", "evaluate_cost", "constraint_violation", "OffsetFreeObserver",
-           "offset_free_observer"]
+           "offset_free_observer", "Uniform"]
 
 
 class Plant:
@@ -47,16 +54,36 @@ class Plant:
         return np.ascontiguousarray(np.hstack([self.h_offset[:, None], self.C, self.Dd]))
 
 
+class Uniform:
+    """A noise source drawn on the device: component q uniform in [lo[q], hi[q]] (lo == hi: the constant), from the
+    counter-based generator include/lmpc_hip.h states -- a draw depends on (seed, scenario, step, stream, component)
+    alone."""
+
+    def __init__(self, lo, hi):
+        self.lo, self.hi = np.atleast_1d(np.asarray(lo, float)), np.atleast_1d(np.asarray(hi, float))
+        if self.lo.shape != self.hi.shape or self.lo.ndim != 1:
+            raise ValueError("lo and hi must be vectors of the same length")
+        if not (np.isfinite(self.lo).all() and np.isfinite(self.hi).all() and (self.lo <= self.hi).all()):
+            raise ValueError("the bounds must be finite with lo <= hi")
+
+
 class Scenario:
     """simulation.jl:13-35 for N_scen scenarios.  Trajectories keep their own length; `trajectory` gives them over
-    the N steps of the run, cut or held at the last column (simulation.jl:69-88)."""
+    the N steps of the run, cut or held at the last column (simulation.jl:69-88).  process_noise (added to the state
+    through Simulation's Gw) and measurement_noise (added to ym, as `noise` is): a `Uniform`, drawn on the device, or
+    an array (w, T) / (N_scen, w, T) of supplied draws."""
 
-    def __init__(self, x0, N=1000, r=None, d=None, p=None, noise=None):
+    def __init__(self, x0, N=1000, r=None, d=None, p=None, noise=None, process_noise=None, measurement_noise=None):
         x0 = np.asarray(x0, float)
         self.single = x0.ndim == 1
         self.x0 = np.ascontiguousarray(np.atleast_2d(x0))
         self.n_scen, self.N = self.x0.shape[0], int(N)
         self.r, self.d, self.p, self.noise = (self._traj(a, k) for a, k in ((r, "r"), (d, "d"), (p, "p"), (noise, "noise")))
+        if self.noise is not None and measurement_noise is not None:
+            raise ValueError("noise and measurement_noise are the same slot: give one of them")
+        self.process_noise, self.measurement_noise = (
+            a if isinstance(a, Uniform) else self._traj(a, k)
+            for a, k in ((process_noise, "process_noise"), (measurement_noise, "measurement_noise")))
 
     def _traj(self, a, name):
         if a is None or np.size(a) == 0:
@@ -221,12 +248,33 @@ class Simulation:
     (nu, N), ys, yms (ny, N), rs, ds, ts, and flag_min (smallest exit flag per scenario).
     observer = `offset_free_observer(...)`: the offset-free loop (`lmpc_simulate_scenario_offset_free_device`); the plant
     and the scenario's d then carry the MEASURED disturbances alone (plant.nd == mpc.nd_base - ndo) and `dhats`
-    (N_scen, ndo, N), the estimate the controller saw, is added.  Not available with an `ExplicitMPC`."""
+    (N_scen, ndo, N), the estimate the controller saw, is added.  Not available with an `ExplicitMPC`.
+    Uncertainty (`lmpc_simulate_scenario_uncertain_device`): the scenario's process_noise e_k acts as w_k = Gw e_k on
+    the state (Gw None: identity) and `ws` (N_scen, nx, N) is added; its measurement_noise is added to ym; plant = a
+    list of `Plant`s of equal nx, nu, nd, ny: scenario i is stepped by plant plant_index[i] (default i mod the list's
+    length) and all share the FIRST one's measurement rows; seed keys the draws of a `Uniform`.  Without any of these
+    the existing path runs unchanged; with an `ExplicitMPC` or an `OffsetFreeObserver` they raise ValueError."""
 
-    def __init__(self, mpc, scenario, plant, observer=None, warm=False, cost=None, mode=0):
+    def __init__(self, mpc, scenario, plant, observer=None, warm=False, cost=None, mode=0, Gw=None, seed=0, plant_index=None):
         import torch
         from .mpc import ExplicitMPC
         empc = mpc if isinstance(mpc, ExplicitMPC) else None
+        plants = list(plant) if isinstance(plant, (list, tuple)) else None
+        if plants is not None:
+            if not plants:
+                raise ValueError("the list of plants is empty")
+            plant = plants[0]
+            if any((q.nx, q.nu, q.nd, q.ny) != (plant.nx, plant.nu, plant.nd, plant.ny) for q in plants):
+                raise ValueError("the plants of a list must agree in nx, nu, nd and ny")
+        e_src, v_src = getattr(scenario, "process_noise", None), getattr(scenario, "measurement_noise", None)
+        uncertain = plants is not None or e_src is not None or v_src is not None or Gw is not None or plant_index is not None
+        if uncertain and (empc is not None or isinstance(observer, OffsetFreeObserver)):
+            raise ValueError("process noise, measurement_noise, Gw, plant lists and plant_index are not available in the "
+                             "explicit controller's loop or with an offset-free observer")
+        if plant_index is not None and plants is None:
+            raise ValueError("plant_index needs a list of plants")
+        if Gw is not None and e_src is None:
+            raise ValueError("Gw needs the scenario's process_noise")
         if empc is not None and isinstance(observer, OffsetFreeObserver):
             raise ValueError("the offset-free observer is not available in the explicit controller's loop")
         if empc is not None:                      # simulation.jl:37 with compute_control(empc, x), utils.jl:53-60
@@ -264,6 +312,14 @@ class Simulation:
         run = model.simulate_scenario if empc is None else \
             (lambda *a, **kw: empc.controller.simulate_scenario_device(*a, mode=mode, **kw))
         want = ("U", "X", "Y", "Ym", "Xhat") + (("D",) if plant.nd else ())
+        if uncertain:
+            src = lambda a: a if (a is None or isinstance(a, Uniform)) else torch.from_numpy(np.ascontiguousarray(a[..., :T])).to(dev)
+            pidx = None if plant_index is None else torch.from_numpy(
+                np.ascontiguousarray(np.asarray(plant_index).reshape(S).astype(np.int32))).to(dev)
+            run = lambda *a, want, **kw: model.simulate_scenario_uncertain(
+                *a, process=src(e_src), measurement_noise=src(v_src), Gw=Gw, seed=seed,
+                plants=None if plants is None else np.stack([q.dynamics_rows() for q in plants]), plant_index=pidx,
+                want=want + (("W",) if e_src is not None else ()), **kw)
         if off is not None:                       # simulation.jl:37-116 with an OffsetFreeObserver (observer.jl:203-225)
             out = model.simulate_scenario_offset_free(
                 x, T, plant.dynamics_rows(), plant.measurement_rows(), ndo, nd=plant.nd, ny=plant.ny,
@@ -285,6 +341,8 @@ class Simulation:
         self.xs, self.us = per(out["X"][:T]), per(out["U"])
         self.ys, self.yms, self.xhats = per(out["Y"]), per(out["Ym"]), per(out["Xhat"])
         self.ds = per(out["D"]) if plant.nd else np.zeros((S, 0, T))
+        if "W" in out:
+            self.ws = per(out["W"])
         if off is not None:
             self.dhats = per(out["Dhat"])
             self.xaug_final = out["xaug"].cpu().numpy() if out["xaug"] is not None else None
@@ -299,7 +357,8 @@ class Simulation:
             self.regions = np.ascontiguousarray(out["regions"].cpu().numpy().T)
             self.stats = out["stats"]
         if scenario.single:
-            for k in ("xs", "us", "ys", "yms", "xhats", "ds", "rs") + (("dhats",) if off is not None else ()):
+            for k in ("xs", "us", "ys", "yms", "xhats", "ds", "rs") + (("dhats",) if off is not None else ()) + \
+                    (("ws",) if hasattr(self, "ws") else ()):
                 setattr(self, k, getattr(self, k)[0])
 
 

@@ -609,6 +609,82 @@ class BatchedQP:
         out["_keep"] = keep                      # the launches are asynchronous: keep the sources alive
         return out
 
+    def uncertainty(self, N, nx, process=None, measurement_noise=None, Gw=None, seed=0, scenario_offset=0, step_offset=0,
+                    plants=None, plant_index=None, W=None):
+        """`lmpc_uncertainty` from its parts.  process / measurement_noise: None, an object with `lo` and `hi` (drawn on
+        the device, uniform in the box) or a CUDA tensor (w, Tc) shared / (N, w, Tc) per scenario (supplied draws).
+        Gw (nx, nw) host array or None.  plants: (n_plants, nx, 1 + nx + nu + nd) host array or None; plant_index: int32
+        CUDA tensor (N,) or None.  W: the (T, N, nx) CUDA tensor that takes W_traj, or None.  Returns (struct, keep-alive)."""
+        un, keep = _cabi.Uncertainty(), []
+
+        def source(dst, a):
+            if a is None:
+                return
+            if hasattr(a, "lo") and hasattr(a, "hi"):
+                lo, hi = _f64(np.asarray(a.lo, float).reshape(-1)), _f64(np.asarray(a.hi, float).reshape(-1))
+                if lo.shape != hi.shape:
+                    raise ValueError("lo and hi of a drawn noise source must have the same length")
+                dst.w, dst.lo, dst.hi = lo.size, lo.ctypes.data, hi.ctypes.data
+                keep.extend([lo, hi])
+                return
+            if a.dim() == 3 and a.shape[0] != N:
+                raise ValueError("a per-scenario noise block must have shape (N, w, T)")
+            b, k = self._block(a, 0, 0)
+            dst.w, dst.src = b.w, b
+            keep.append(k)
+
+        source(un.process, process)
+        source(un.measurement, measurement_noise)
+        if Gw is not None:
+            g = _f64(np.asarray(Gw, float).reshape(nx, -1))
+            if g.shape[1] != un.process.w:
+                raise ValueError(f"Gw must have shape ({nx}, {un.process.w}), got {g.shape}")
+            un.Gw = g.ctypes.data
+            keep.append(g)
+        un.seed, un.scenario_offset, un.step_offset = int(seed), int(scenario_offset), int(step_offset)
+        if plants is not None:
+            tab = _f64(np.asarray(plants, float))
+            if tab.ndim != 3 or tab.shape[1] != nx:
+                raise ValueError("plants must have shape (n_plants, nx, 1 + nx + nu + nd)")
+            un.n_plants, un.plants = tab.shape[0], tab.ctypes.data
+            keep.append(tab)
+        if plant_index is not None:
+            import torch
+            un.plant_index = _dev_arg(plant_index, "plant_index", torch.int32, N, self.device, False).value
+            keep.append(plant_index)
+        if W is not None:
+            un.W_traj = W.data_ptr()
+        return un, keep
+
+    def uncertain_check(self, desc, un, observer_dims="handle"):
+        """`lmpc_scenario_uncertain_check` of a descriptor and an uncertainty against this handle's dimensions (host only)."""
+        od = getattr(self, "_obs", None) if observer_dims == "handle" else observer_dims
+        o = None if od is None else ctypes.byref(Observer(*[int(v) for v in od], None, None, None))
+        check(lib().lmpc_scenario_uncertain_check(self.nth, self.nout, o, ctypes.byref(desc), ctypes.byref(un)))
+
+    def simulate_scenario_uncertain(self, x, T, plant, measurement=None, *, process=None, measurement_noise=None, Gw=None,
+                                    seed=0, scenario_offset=0, step_offset=0, plants=None, plant_index=None,
+                                    want=("U", "X"), **kw):
+        """The scenario loop under uncertainty (`lmpc_simulate_scenario_uncertain_device`): `simulate_scenario` with
+        additive process noise w_k = Gw e_k on the state, additive measurement noise and a table of plant variants
+        (`uncertainty` says how each is given; `plant` stays the descriptor's plant and steps everyone without
+        `plants`).  The draws are uniform in a box: Gaussian noise is drawn by the caller and supplied as a block.
+        want may name "W" (T, N, nx), the w_k that acted.  Everything else, and the dict returned, as `simulate_scenario`."""
+        import torch
+        N, nx = int(x.shape[0]), int(x.shape[1])
+        W = torch.empty((int(T), N, nx), dtype=torch.float64, device=x.device) if "W" in want else None
+        un, keep = self.uncertainty(N, nx, process, measurement_noise, Gw, seed, scenario_offset, step_offset, plants,
+                                    plant_index, W)
+
+        def launch(desc, n, t, *args):
+            check(lib().lmpc_simulate_scenario_uncertain_device(self._h, n, t, ctypes.byref(desc), ctypes.byref(un), *args), self._h)
+
+        out = self.simulate_scenario(x, T, plant, measurement, want=tuple(k for k in want if k != "W"), launch=launch, **kw)
+        if W is not None:
+            out["W"] = W
+        out["_keep"].append(keep)
+        return out
+
     def offset_free_check(self, desc, n_offset_free, observer_dims="handle"):
         """`lmpc_scenario_offset_free_check` of a descriptor against this handle's dimensions (host only)."""
         od = getattr(self, "_obs", None) if observer_dims == "handle" else observer_dims
