@@ -563,7 +563,13 @@ int lmpc_set_option(lmpc_handle *h, const char *name, int value);
  * [0, *n_sets): set_masks[k * words ..] the mask, set_count[k] how many problems ended on it, set_first[k] the
  * smallest problem index that did.  `capacity` = room in the three arrays; more distinct sets than that raise the
  * overflow word (lmpc_distinct_active_sets_overflowed: 0 / nonzero, synchronises the stream) and *n_sets then counts
- * the claims, not the stored sets.  Order of the sets is unspecified (sort on the host).  Asynchronous on `stream`. */
+ * the claims, not the stored sets.  Order of the sets is unspecified (sort on the host).  Asynchronous on `stream`.
+ * Precondition: a ONE-word mask (2 m <= 64 bits) is never all ones -- that value is the empty key of the lock-free
+ * reduction (N >= 65536, option "region_lockfree"); the solver cannot produce it, a row is never active at both bounds.
+ * The overflow word belongs to the LAST call on the handle: 0 if its sets fitted, 1 if there were more than `capacity`
+ * (then *n_sets >= capacity, the first min(*n_sets, capacity) entries hold complete sets, but counts and first indices
+ * are not final), 2 if a table slot was never published.  A call that is not repeated leaves its word standing until
+ * the next call on the handle, which starts from 0 whatever this one reported and whichever kernel either one took. */
 int lmpc_distinct_active_sets_device(lmpc_handle *h, int64_t N, const uint64_t *active, const int32_t *exitflag,
                                      int32_t capacity, uint64_t *set_masks, int64_t *set_count, int64_t *set_first,
                                      int32_t *n_sets, void *stream);

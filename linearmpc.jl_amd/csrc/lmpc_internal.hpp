@@ -87,6 +87,7 @@ struct lmpc_handle {
     unsigned long long *dRegW1 = nullptr;   // one-word masks: key / count / first-index tables of regW1Cap slots each (clean
     int regW1Cap = 0;                       // between calls: the publishing kernel resets what it read)
     int regW1 = 1;                          // tuning: 0 = the ballot-loop kernels also for one-word masks ("region_lockfree")
+    bool regOvStale = false;                // dRegTable[0] may hold the overflow word of a ballot-kernel call: the lock-free path clears it first
     int regBlocks = 0;          // tuning: workgroups per CU of the two-level distinct-mask reduction ("region_blocks", 0 = 1)
     long long *hRegOut = nullptr;   // lmpc_discover_regions_device: result block in mapped host memory ...
     long long *dRegOut = nullptr;   // ... and its device address; regOutWords = its size in 64-bit words

@@ -348,6 +348,10 @@ static int distinct_w1(lmpc_handle *h, int64_t N, const uint64_t *active, const 
         HIP_TRY(h, hipMemsetAsync(h->dRegTable, 0, sizeof(int32_t) * 16, st));
         h->regW1Cap = tcap;
     }
+    if (h->regOvStale) {                                  // an overflowed ballot-kernel call that nobody repeated left its word
+        HIP_TRY(h, hipMemsetAsync(h->dRegTable, 0, sizeof(int32_t) * 16, st));     // behind: publish_w1_kernel would report it as this call's
+        h->regOvStale = false;
+    }
     unsigned long long *gkey = h->dRegW1, *gcnt = h->dRegW1 + tcap;
     long long *gfirst = reinterpret_cast<long long *>(h->dRegW1 + 2 * (size_t)tcap);
     const long long tilesAll = (N + 255) / 256;
@@ -387,6 +391,7 @@ int lmpc_distinct_active_sets_device(lmpc_handle *h, int64_t N, const uint64_t *
     HIP_TRY(h, hipMemsetAsync(h->dRegTable, 0, sizeof(int32_t) * 16, st));
     HIP_TRY(h, hipMemsetAsync(table, 0xff, sizeof(int32_t) * (size_t)tcap, st));
     HIP_TRY(h, hipMemsetAsync(n_sets, 0, sizeof(int32_t), st));
+    h->regOvStale = true;                                 // (word 0 is this call's from here on; the lock-free path starts from 0)
     if (N > 0 && h->P.words() <= kLocalWords && N >= 65536) {
         // two levels: one workgroup per CU ("region_blocks": per CU), each over its share of the tiles
         const long long tilesAll = (N + 255) / 256;
