@@ -489,6 +489,26 @@ const char *lmpc_kernel_name(const lmpc_handle *h);
  * first wavefront-kernel launch). */
 int lmpc_wave_stats(lmpc_handle *h, unsigned long long out[5]);
 
+/* Which wavefront-kernel instantiations the handle last launched, and in which launch shape: the handle keeps a record
+ * of its four most recent wavefront-kernel launches (one call makes up to three: a first pass at a smaller capacity,
+ * the second pass at the full one, and -- once per fresh handle -- the probe in front).  Written on the host when a
+ * launch is enqueued; nothing is read from the device and nothing is waited for.  Copies min(launches so far, 4, max)
+ * entries into out, OLDEST first, LMPC_WAVE_INFO_WORDS words each, and returns how many (< 0: error).  Words of an entry:
+ *    [0] running number of the launch in the handle's life (1, 2, ...): read it before and after a call to tell that
+ *        call's launches from earlier ones
+ *    [1] sizeof(real): 8 / 4      [2] constraint slots MR    [3] staging level LDSC the kernel was built for
+ *    [4] BNB   [5] PACKED   [6] variable slots NU   [7] GRAM   [8] SIM  -- the template arguments of wave_kernel
+ *    [9] wavefronts per workgroup (nwv)   [10] staging level of the launch configuration   [11] workgroups (grid)
+ *   [12] problems per ticket (qchunk)     [13] pass: 0 the only one, 1 / 2 first / second of two
+ *   [14] working-set capacity of this launch   [15] 1 = the slow path (big_kernel) was enqueued behind it
+ *   [16] 1 = problems handed out through the ticket counter, 0 = static split
+ *   [17] 1 = the launch walks a work list (behind a screening / tiers / row pass, or as a second pass)
+ *   [18] dynamic LDS bytes per workgroup  [19] problems of the batch (saturated at 2^31 - 1)
+ * A request the launcher could not honour ("wave_level" 3 where the packed Gram matrix does not fit the LDS, say) shows
+ * here as the configuration that ran instead.  For tests and benchmark reports. */
+#define LMPC_WAVE_INFO_WORDS 20
+int lmpc_wave_launch_info(const lmpc_handle *h, int32_t *out, int max);
+
 /* Device time per lmpc_solve_batch* call, measured with HIP events recorded on the launch
  * stream (switch on with lmpc_profile(h, 1); timing-only events, hipEventDisableSystemFence: a default event's
  * system-scope cache writeback added ~1.7 us to a 24 us call that rocprofv3's kernel trace does not see).  lmpc_profile_read waits for the recorded calls,

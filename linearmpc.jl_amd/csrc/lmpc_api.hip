@@ -1121,6 +1121,15 @@ int lmpc_wave_stats(lmpc_handle *h, unsigned long long out[5]) {
     return LMPC_OK;
 }
 
+int lmpc_wave_launch_info(const lmpc_handle *h, int32_t *out, int max) {
+    if (!h || !out || max < 0) return LMPC_ERR_BADARG;
+    long long k = h->waveRecN < 4 ? h->waveRecN : 4;
+    if (k > max) k = max;
+    for (long long q = 0; q < k; q++)                      // the k most recent entries of the ring, oldest first
+        std::memcpy(out + q * LMPC_WAVE_INFO_WORDS, h->waveRec[(h->waveRecN - k + q) & 3], sizeof(int32_t) * LMPC_WAVE_INFO_WORDS);
+    return (int)k;
+}
+
 const char *lmpc_kernel_name(const lmpc_handle *h) {
     if (!h) return "";
     if (h->avi) return h->kname.c_str();          // "avi" / "avi+prox"

@@ -289,14 +289,21 @@ __global__ __launch_bounds__(64) void big_kernel(
 
         // ---- x = R^-1 u + x0 + Xth theta   (mpc_update_qp.c:14-22), flags, working set
         double xsim[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (int k = 0; k < P.nout; k++) {
+        auto xout = [&](int k) -> R {
             R xs = (R)0, sh = C[P.ox0 + k];
             for (int c = 0; c < n; c++) xs = big_fma<R>(C[P.oRout + (size_t)k * n + c], u[c], xs);
             for (int t = 0; t < nth; t++) sh = big_fma<R>(C[P.oXth + (size_t)k * nth + t], th[t], sh);
             const R xk = xs + sh;
             if (X != nullptr) X[pid * P.nout + k] = xk;
-            if (k < 8) xsim[k] = (double)xk;
-        }
+            return xk;
+        };
+        // The first eight outputs are kept for the plant step below, in a loop of their own: written as ONE loop over
+        // all outputs with `if (k < 8) xsim[k] = xk` inside, the compiler emitted an indexed register write that it
+        // executes for EVERY k, with a select behind it -- outputs 8, 9, ... landed in the registers that follow the
+        // array (pointers among them): an illegal access from nout = 9 on, found by tests/test_gpu_wave.py at nout = 32.
+        const int k8 = P.nout < 8 ? P.nout : 8;
+        for (int k = 0; k < k8; k++) xsim[k] = (double)xout(k);
+        for (int k = k8; k < P.nout; k++) (void)xout(k);
         if constexpr (sizeof(R) == 8) {
             if (sim.FG != nullptr) {             // closed loop with the plant step fused in: advance in place (WaveSim)
                 const int snx = sim.nx, snu = sim.nu, ks = sim.kfix >= 0 ? sim.kfix : sim.kstep[pid];

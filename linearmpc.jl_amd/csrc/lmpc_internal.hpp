@@ -82,6 +82,10 @@ struct lmpc_handle {
     unsigned long long statA[4] = {0, 0, 0, 0}, statB[4] = {0, 0, 0, 0};   // window of the statistics: snapshots of the
                                 // cumulative counters about 2^20 problems apart; decisions use (now - statA)
     int waveCtrSet = 0;         // which of the two (ticket, overflow) counter pairs the next wavefront-kernel launch uses
+    // what launch_wave_cfg last enqueued (lmpc_wave_launch_info): a ring of the four most recent wavefront-kernel
+    // launches, LMPC_WAVE_INFO_WORDS words each, and how many the handle has made in its life (host memory only)
+    int32_t waveRec[4][LMPC_WAVE_INFO_WORDS] = {};
+    long long waveRecN = 0;
     int32_t *dRegTable = nullptr;  // hash table of lmpc_distinct_active_sets_device (lmpc_regions.hip): 16 control words + slots
     int regCap = 0;
     unsigned long long *dRegW1 = nullptr;   // one-word masks: key / count / first-index tables of regW1Cap slots each (clean

@@ -362,6 +362,13 @@ int launch_wave_cfg(lmpc_handle *h, const WaveConfig &cfg, const R *dC, int64_t 
                            active, warm, h->dOvfList, ovfCount, static_cast<R *>(h->dBigR), h->dBigI, bigCap, h->waveSim);
         HIP_TRY(h, hipGetLastError());
     }
+    // what was enqueued, for lmpc_wave_launch_info (include/lmpc_hip.h lists the words)
+    const int32_t rec[LMPC_WAVE_INFO_WORDS] = {
+        (int32_t)((h->waveRecN + 1) & 0x7fffffff), (int32_t)sizeof(R), MR, LDSC, BNB ? 1 : 0, PACKED ? 1 : 0, NU, GRAM ? 1 : 0,
+        SIM ? 1 : 0, cfg.nwv, cfg.level, (int32_t)grid, qchunk, pass, Wl.cap, big ? 1 : 0, queue != nullptr ? 1 : 0,
+        wl.list != nullptr ? 1 : 0, (int32_t)cfg.lds, (int32_t)(nprob < (int64_t)0x7fffffff ? nprob : (int64_t)0x7fffffff)};
+    for (int q = 0; q < LMPC_WAVE_INFO_WORDS; q++) h->waveRec[h->waveRecN & 3][q] = rec[q];
+    h->waveRecN++;
     return LMPC_OK;
 }
 

@@ -188,6 +188,23 @@ class BatchedQP:
         return {"problems": int(out[0]), "within_24": int(out[1]), "within_32": int(out[2]), "within_48": int(out[3]),
                 "first_pass_rows": int(out[4])}
 
+    WAVE_LAUNCH_FIELDS = ("seq", "real_bytes", "MR", "LDSC", "BNB", "PACKED", "NU", "GRAM", "SIM", "nwv", "level", "grid",
+                          "qchunk", "pass", "cap", "big", "queue", "worklist", "lds", "nprob")
+
+    def wave_launch_info(self, since=0):
+        """The handle's most recent wavefront-kernel launches (lmpc_wave_launch_info; at most four are kept), oldest
+        first: one dict per launch with the template arguments of the wave_kernel instantiation that ran (real_bytes,
+        MR, LDSC, BNB, PACKED, NU, GRAM, SIM) and its launch shape (nwv, level, grid, qchunk, pass, cap, big, queue,
+        worklist, lds, nprob).  "seq" numbers the launches of the handle's life from 1; `since` = keep only the
+        launches with a larger number (pass the last "seq" seen before a call to get that call's launches)."""
+        W = len(self.WAVE_LAUNCH_FIELDS)
+        out = (ctypes.c_int32 * (4 * W))()
+        k = lib().lmpc_wave_launch_info(self._h, out, 4)
+        if k < 0:
+            check(k, self._h)
+        recs = [dict(zip(self.WAVE_LAUNCH_FIELDS, (int(v) for v in out[q * W:(q + 1) * W]))) for q in range(k)]
+        return [r for r in recs if r["seq"] > since]
+
     def ldp(self):
         """The constant pack the kernels use (row-major) -- what tests hand to the oracle."""
         out = dict(M=np.empty((self.m, self.n)), du=np.empty(self.m), dl=np.empty(self.m),
