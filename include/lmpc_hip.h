@@ -980,6 +980,117 @@ int lmpc_explicit_simulate_scenario(lmpc_explicit *e, int64_t N, int T, const lm
                                     double *uprev, double *U_traj, double *X_traj, int32_t *flag_min, int32_t *region_traj,
                                     int mode, int64_t *stats);
 
+/*
+ * A NONLINEAR TRUE PLANT in the scenario loop: the reference's Simulation steps mpc.model.true_dynamics
+ * (src/simulation.jl:40,110,126), which for Model(f, h, xo, uo, Ts) is x + Ts * f(x, u, d) (src/model.jl:87,114-118).
+ * Here the plant is a straight-line PROGRAM -- data, not code -- that one kernel interprets, one scenario per lane.
+ *
+ * Inputs of the program: x (nx <= 32), u (nu <= 64), d (nd <= 32: column k of the descriptor's d block) and q (nq <= 32
+ * plant parameters: N x nq on the device, one row per scenario, or nq values shared by all).  The program has a table
+ * of n_consts binary64 constants, n_ins instructions over a file of n_slots binary64 slots, and out_slot[nx]: slot
+ * out_slot[a] holds x+_a after the last instruction.  An instruction is five int32: op, dst, a, b, c.
+ *   op  name     dst <-                              operands
+ *    1  LOADX    x[a]                                a < nx
+ *    2  LOADU    u[a]                                a < nu
+ *    3  LOADD    d[a]                                a < nd
+ *    4  LOADQ    q[a]                                a < nq
+ *    5  CONST    consts[a]                           a < n_consts
+ *    6  ADD      s[a] + s[b]                         a, b slots written earlier (likewise below)
+ *    7  SUB      s[a] - s[b]
+ *    8  MUL      s[a] * s[b]
+ *    9  DIV      s[a] / s[b]
+ *   10  NEG      -s[a]                               (the sign bit flipped)
+ *   11  ABS      |s[a]|                              (the sign bit cleared)
+ *   12  FMA      fma(s[a], s[b], s[c])               one rounding
+ *   13  MIN      s[a] < s[b] ? s[a] : s[b]           (so MIN(NaN, t) = t, MIN(t, NaN) = NaN, MIN(-0, +0) = +0)
+ *   14  MAX      s[a] > s[b] ? s[a] : s[b]
+ *   15  SIN      sin_(s[a])
+ *   16  COS      cos_(s[a])
+ * Unused operand fields must be 0.  Every operation is ONE IEEE-754 binary64 operation, round to nearest even, nothing
+ * fused that is not written as fma; SQRT, EXP, TANH, comparisons and selects are not operations of this version.
+ * sin_ / cos_ are NOT the device library's: they are this sequence, which a host restates bit for bit.
+ *   kd = rint(t * TWO_OVER_PI)                                      (one multiply; rint: to nearest, ties to even)
+ *   r  = fma(-kd, P1, t);  r = fma(-kd, P2, r);  r = fma(-kd, P3, r)      (Cody-Waite, three constants)
+ *   z  = r * r
+ *   ps = S6; ps = fma(ps, z, S5); ps = fma(ps, z, S4); ps = fma(ps, z, S3); ps = fma(ps, z, S2); ps = fma(ps, z, S1)
+ *   sn = fma(r * z, ps, r)
+ *   pc = C6; pc = fma(pc, z, C5); pc = fma(pc, z, C4); pc = fma(pc, z, C3); pc = fma(pc, z, C2); pc = fma(pc, z, C1)
+ *   hz = 0.5 * z;  w = 1 - hz;  cs = w + fma(z * z, pc, (1 - w) - hz)
+ *   m  = kd - 4 * rint(0.25 * kd)                  (exact; m in {-2, -1, 0, 1, 2}: k & 3 with 3 as -1 and 2 as +-2)
+ *   sin_: m == 0: sn;  m == 1: cs;  m == -1: -cs;  otherwise -sn
+ *   cos_: m == 0: cs;  m == 1: -sn; m == -1: sn;   otherwise -cs
+ * with (hexadecimal binary64)
+ *   TWO_OVER_PI 0x3FE45F306DC9C883
+ *   P1 0x3FF921FB54400000 (33 bits of pi/2)   P2 0x3DD0B4611A600000 (the next 33)   P3 0x3BA3198A2E037073 (pi/2 - P1 - P2)
+ *   S1 0xBFC5555555555549  S2 0x3F8111111110F8A6  S3 0xBF2A01A019C161D5  S4 0x3EC71DE357B1FE7D  S5 0xBE5AE5E68A2B9CEB
+ *   S6 0x3DE5D93A5ACFD57C
+ *   C1 0x3FA555555555554C  C2 0xBF56C16C16C15177  C3 0x3EFA01A019CB1590  C4 0xBE927E4F809C52AD  C5 0x3E21EE9EBDB4B1C4
+ *   C6 0xBDA8FAE9BE8838D4
+ * (the polynomials of the classic kernels on [-pi/4, pi/4]).  Both polynomials are always evaluated.  Accuracy (below
+ * 2 ulp against a correctly rounded result) is claimed for |t| <= 2^20 ONLY.  Beyond that the same operations run
+ * unchanged: the result is defined and restated but carries no accuracy (r leaves [-pi/4, pi/4]; for |kd| >= 2^54, m
+ * is 0).  t = +-inf or NaN gives NaN (r is NaN).  t = -0 gives sin_ = +0.
+ * Caps: n_ins <= LMPC_PLANT_MAX_INS, n_slots <= LMPC_PLANT_MAX_SLOTS, n_consts <= LMPC_PLANT_MAX_CONSTS.
+ *
+ * lmpc_plant_program_check (HOST only; every entry point below runs it first): LMPC_OK, or LMPC_ERR_BADARG with the
+ * field's name first in lmpc_last_error(NULL): prog NULL; nx not in 1 .. 32, nu not in 0 .. 64, nd or nq not in 0 .. 32;
+ * a count beyond its cap or negative, n_slots < 1; a NULL array with a non-zero count; an unknown op; dst not a slot; an
+ * input or constant index out of range; a slot operand out of range or read before an instruction wrote it; a non-zero
+ * unused field; an out_slot entry out of range or never written.  A program that passes reads and writes nothing
+ * outside its n_slots slots, its constants and the nx / nu / nd / nq inputs it declares.
+ * lmpc_plant_program_eval_host: xnext[i, :] = program(x[i, :], u[i, :], d[i, :], q) for i < N on the CPU, HOST arrays
+ * (N x nx, N x nu, N x nd, N x nq or nq with q_shared != 0; an array whose width is 0 may be NULL).  Needs no GPU.
+ * lmpc_plant_program_eval_device: the same on the handle's GPU with DEVICE arrays, one kernel, asynchronous on `stream`;
+ * the program itself (HOST) is staged by the call.  The two execute the same source and agree bit for bit (a NaN
+ * result's sign and payload excepted).
+ * lmpc_simulate_scenario_nonlinear_device: lmpc_simulate_scenario_uncertain_device with the plant's row sums replaced by
+ * the program.  PRE is that loop's (the measurement stays the linear s->measurement, the reference's default
+ * get_measurement, simulation.jl:45-50).  POST: cost, violation and the observer's predict (with the handle's LINEAR
+ * model) as there; x+ = the program on (x, u_k, d_k, q_i); then the process noise onto the finished x+ as there.
+ * un may be NULL (no noise); s->plant is ignored and may be NULL; un->n_plants > 0 is refused (q takes its place: DEVICE,
+ * N x nq, or nq values with q_shared != 0; NULL with nq == 0); prog->nx / nu / nd must equal s->nx / nu / nd.
+ * Everything lmpc_scenario_uncertain_check refuses is refused here too.  lmpc_simulate_scenario_nonlinear: the HOST
+ * twin (q HOST as well).  NOT extended: the offset-free loop, the explicit controller's loop, a nonlinear measurement.
+ */
+#define LMPC_PLANT_MAX_INS 1024
+#define LMPC_PLANT_MAX_SLOTS 64
+#define LMPC_PLANT_MAX_CONSTS 256
+#define LMPC_PLANT_LOADX 1
+#define LMPC_PLANT_LOADU 2
+#define LMPC_PLANT_LOADD 3
+#define LMPC_PLANT_LOADQ 4
+#define LMPC_PLANT_CONST 5
+#define LMPC_PLANT_ADD 6
+#define LMPC_PLANT_SUB 7
+#define LMPC_PLANT_MUL 8
+#define LMPC_PLANT_DIV 9
+#define LMPC_PLANT_NEG 10
+#define LMPC_PLANT_ABS 11
+#define LMPC_PLANT_FMA 12
+#define LMPC_PLANT_MIN 13
+#define LMPC_PLANT_MAX 14
+#define LMPC_PLANT_SIN 15
+#define LMPC_PLANT_COS 16
+typedef struct lmpc_plant_program {
+    int32_t nx, nu, nd, nq;              /* widths of the inputs                                                  */
+    int32_t n_slots, n_consts, n_ins;
+    const double *consts;                /* HOST, n_consts                                                        */
+    const int32_t *ins;                  /* HOST, n_ins x 5: op, dst, a, b, c                                     */
+    const int32_t *out_slot;             /* HOST, nx: the slots that hold x+ after the last instruction           */
+} lmpc_plant_program;
+int lmpc_plant_program_check(const lmpc_plant_program *prog);
+int lmpc_plant_program_eval_host(const lmpc_plant_program *prog, int64_t N, const double *x, const double *u, const double *d,
+                                 const double *q, int q_shared, double *xnext);
+int lmpc_plant_program_eval_device(lmpc_handle *h, const lmpc_plant_program *prog, int64_t N, const double *x, const double *u,
+                                   const double *d, const double *q, int q_shared, double *xnext, void *stream);
+int lmpc_simulate_scenario_nonlinear_device(lmpc_handle *h, int64_t N, int T, const lmpc_scenario_sim *s,
+                                            const lmpc_uncertainty *un, const lmpc_plant_program *prog, const double *q,
+                                            int q_shared, double *x, double *xhat, double *uprev, double *U_traj,
+                                            double *X_traj, int32_t *flag_min, void *stream);
+int lmpc_simulate_scenario_nonlinear(lmpc_handle *h, int64_t N, int T, const lmpc_scenario_sim *s, const lmpc_uncertainty *un,
+                                     const lmpc_plant_program *prog, const double *q, int q_shared, double *x, double *xhat,
+                                     double *uprev, double *U_traj, double *X_traj, int32_t *flag_min);
+
 #ifdef __cplusplus
 }
 #endif

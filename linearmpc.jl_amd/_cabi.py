@@ -41,6 +41,8 @@ SYMBOLS = (
     "lmpc_explicit_scenario_check", "lmpc_explicit_simulate_scenario_device", "lmpc_explicit_simulate_scenario",
     "lmpc_scenario_offset_free_check", "lmpc_simulate_scenario_offset_free_device", "lmpc_simulate_scenario_offset_free",
     "lmpc_scenario_uncertain_check", "lmpc_simulate_scenario_uncertain_device", "lmpc_simulate_scenario_uncertain",
+    "lmpc_plant_program_check", "lmpc_plant_program_eval_host", "lmpc_plant_program_eval_device",
+    "lmpc_simulate_scenario_nonlinear_device", "lmpc_simulate_scenario_nonlinear",
 )
 
 
@@ -112,6 +114,12 @@ class Uncertainty(ctypes.Structure):
     _fields_ = [("process", Noise), ("Gw", ctypes.c_void_p), ("measurement", Noise), ("seed", ctypes.c_uint64),
                 ("scenario_offset", ctypes.c_int64), ("step_offset", ctypes.c_int32), ("n_plants", ctypes.c_int32),
                 ("plants", ctypes.c_void_p), ("plant_index", ctypes.c_void_p), ("W_traj", ctypes.c_void_p)]
+
+
+class PlantProgram(ctypes.Structure):
+    """`lmpc_plant_program`: a nonlinear plant as a straight-line program (lmpc_simulate_scenario_nonlinear*)."""
+    _fields_ = [(k, ctypes.c_int32) for k in ("nx", "nu", "nd", "nq", "n_slots", "n_consts", "n_ins")] + \
+               [("consts", ctypes.c_void_p), ("ins", ctypes.c_void_p), ("out_slot", ctypes.c_void_p)]
 
 
 _lib = None
@@ -271,6 +279,17 @@ def lib():
     L.lmpc_simulate_scenario_uncertain_device.restype = i32
     L.lmpc_simulate_scenario_uncertain.argtypes = [vp, i64, i32, sp, up] + [vp] * 6
     L.lmpc_simulate_scenario_uncertain.restype = i32
+    pp = ctypes.POINTER(PlantProgram)
+    L.lmpc_plant_program_check.argtypes = [pp]
+    L.lmpc_plant_program_check.restype = i32
+    L.lmpc_plant_program_eval_host.argtypes = [pp, i64, vp, vp, vp, vp, i32, vp]
+    L.lmpc_plant_program_eval_host.restype = i32
+    L.lmpc_plant_program_eval_device.argtypes = [vp, pp, i64, vp, vp, vp, vp, i32, vp, vp]
+    L.lmpc_plant_program_eval_device.restype = i32
+    L.lmpc_simulate_scenario_nonlinear_device.argtypes = [vp, i64, i32, sp, up, pp, vp, i32] + [vp] * 7
+    L.lmpc_simulate_scenario_nonlinear_device.restype = i32
+    L.lmpc_simulate_scenario_nonlinear.argtypes = [vp, i64, i32, sp, up, pp, vp, i32] + [vp] * 6
+    L.lmpc_simulate_scenario_nonlinear.restype = i32
     _lib = L
     return L
 

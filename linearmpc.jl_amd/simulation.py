@@ -15,9 +15,11 @@ tests make are covered (`lmpc_simulate_scenario_uncertain_device`): additive pro
 `Scenario(process_noise=)` with `Simulation(Gw=, seed=)` -- and plants that are not the controller's model -- a list
 of `Plant`s.  Draws made on the device are uniform (`Uniform`); Gaussian noise (example/observer.jl) is drawn by the
 caller and given as an array, with Gw = B: the device library's log / cos / sqrt cannot be restated bit for bit on a
-host.  Callbacks and nonlinear dynamics (`scenario.callback`, a general `scenario.dynamics`) have no counterpart: the
-plant is the affine one the kernels step.  An MPC with reference condensation is refused (its theta block is not a
-cut of r).
+host.  A NONLINEAR true plant -- the `true_dynamics` x + Ts f(x, u, d) of a controller built from `Model(f, h, xo, uo, Ts)`
+(simulation.jl:40,110,126, model.jl:87) -- is a `NonlinearPlant` (nonlinear.py): a Python function traced into a plant
+program that `lmpc_simulate_scenario_nonlinear_device` interprets, with `params=` as its per-scenario parameters.
+Callbacks (`scenario.callback`) and a nonlinear measurement have no counterpart.  An MPC with reference condensation
+is refused (its theta block is not a cut of r).
 """
 from __future__ import annotations
 
@@ -253,13 +255,29 @@ class Simulation:
     the state (Gw None: identity) and `ws` (N_scen, nx, N) is added; its measurement_noise is added to ym; plant = a
     list of `Plant`s of equal nx, nu, nd, ny: scenario i is stepped by plant plant_index[i] (default i mod the list's
     length) and all share the FIRST one's measurement rows; seed keys the draws of a `Uniform`.  Without any of these
-    the existing path runs unchanged; with an `ExplicitMPC` or an `OffsetFreeObserver` they raise ValueError."""
+    the existing path runs unchanged; with an `ExplicitMPC` or an `OffsetFreeObserver` they raise ValueError.
+    plant = a `NonlinearPlant` (`lmpc_simulate_scenario_nonlinear_device`): the true plant is its traced program, stepped
+    on the device; params (nq,) or (N_scen, nq) are its q; process_noise, measurement_noise, Gw, seed and observer= as
+    above; the measurement is its linear C, Dd, h_offset.  A list of plants, an `ExplicitMPC` or an `OffsetFreeObserver`
+    raises ValueError."""
 
-    def __init__(self, mpc, scenario, plant, observer=None, warm=False, cost=None, mode=0, Gw=None, seed=0, plant_index=None):
+    def __init__(self, mpc, scenario, plant, observer=None, warm=False, cost=None, mode=0, Gw=None, seed=0, plant_index=None,
+                 params=None):
         import torch
         from .mpc import ExplicitMPC
+        from .nonlinear import NonlinearPlant
         empc = mpc if isinstance(mpc, ExplicitMPC) else None
         plants = list(plant) if isinstance(plant, (list, tuple)) else None
+        nonlinear = isinstance(plant, NonlinearPlant)
+        if plants is not None and any(isinstance(q, NonlinearPlant) for q in plants):
+            raise ValueError("a NonlinearPlant cannot be part of a list of plants: its params (per scenario) take the "
+                             "ensemble's place")
+        if nonlinear and empc is not None:
+            raise ValueError("a NonlinearPlant is not available in the explicit controller's loop")
+        if nonlinear and isinstance(observer, OffsetFreeObserver):
+            raise ValueError("a NonlinearPlant is not available with an offset-free observer")
+        if params is not None and not nonlinear:
+            raise ValueError("params needs a NonlinearPlant")
         if plants is not None:
             if not plants:
                 raise ValueError("the list of plants is empty")
@@ -268,6 +286,8 @@ class Simulation:
                 raise ValueError("the plants of a list must agree in nx, nu, nd and ny")
         e_src, v_src = getattr(scenario, "process_noise", None), getattr(scenario, "measurement_noise", None)
         uncertain = plants is not None or e_src is not None or v_src is not None or Gw is not None or plant_index is not None
+        if nonlinear and plant_index is not None:
+            raise ValueError("plant_index needs a list of plants")
         if uncertain and (empc is not None or isinstance(observer, OffsetFreeObserver)):
             raise ValueError("process noise, measurement_noise, Gw, plant lists and plant_index are not available in the "
                              "explicit controller's loop or with an offset-free observer")
@@ -312,13 +332,17 @@ class Simulation:
         run = model.simulate_scenario if empc is None else \
             (lambda *a, **kw: empc.controller.simulate_scenario_device(*a, mode=mode, **kw))
         want = ("U", "X", "Y", "Ym", "Xhat") + (("D",) if plant.nd else ())
-        if uncertain:
+        if uncertain or nonlinear:
             src = lambda a: a if (a is None or isinstance(a, Uniform)) else torch.from_numpy(np.ascontiguousarray(a[..., :T])).to(dev)
             pidx = None if plant_index is None else torch.from_numpy(
                 np.ascontiguousarray(np.asarray(plant_index).reshape(S).astype(np.int32))).to(dev)
             run = lambda *a, want, **kw: model.simulate_scenario_uncertain(
                 *a, process=src(e_src), measurement_noise=src(v_src), Gw=Gw, seed=seed,
                 plants=None if plants is None else np.stack([q.dynamics_rows() for q in plants]), plant_index=pidx,
+                want=want + (("W",) if e_src is not None else ()), **kw)
+        if nonlinear:                             # simulation.jl:40,110,126 with true_dynamics = x + Ts f(x, u, d) (model.jl:87)
+            run = lambda x_, T_, rows, meas, want, **kw: model.simulate_scenario_nonlinear(
+                x_, T_, plant, params=params, process=src(e_src), measurement_noise=src(v_src), Gw=Gw, seed=seed,
                 want=want + (("W",) if e_src is not None else ()), **kw)
         if off is not None:                       # simulation.jl:37-116 with an OffsetFreeObserver (observer.jl:203-225)
             out = model.simulate_scenario_offset_free(
@@ -329,7 +353,7 @@ class Simulation:
                 want=want + ("Dhat",), want_cost=cost is not None, want_violation=cost is not None and cost[0].nc > 0)
         else:
             out = run(
-                x, T, plant.dynamics_rows(), plant.measurement_rows(), nd=plant.nd, ny=plant.ny,
+                x, T, None if nonlinear else plant.dynamics_rows(), plant.measurement_rows(), nd=plant.nd, ny=plant.ny,
                 r=up(specs["r"]), d=up(specs["d"]), p=up(specs["p"]), noise=up(specs["noise"]),
                 r_preview=specs["r"]["H"], d_preview=specs["d"]["H"], p_preview=specs["p"]["H"],
                 r_width=specs["r"]["w"], d_width=specs["d"]["w"], p_width=specs["p"]["w"], uprev=uprev,

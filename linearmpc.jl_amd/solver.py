@@ -702,6 +702,65 @@ class BatchedQP:
         out["_keep"].append(keep)
         return out
 
+    def _plant_params(self, plant, params, N, dev):
+        """q of a `NonlinearPlant` run as (CUDA tensor or None, q_shared): (nq,) shared by all, (N, nq) per scenario"""
+        import torch
+        if plant.nq == 0:
+            return None, 1
+        if params is None:
+            raise ValueError(f"the plant has nq = {plant.nq} parameters: params is required")
+        q = params if isinstance(params, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(params, float)))
+        q = q.to(dev, torch.float64).contiguous()
+        if tuple(q.shape) not in ((plant.nq,), (N, plant.nq)):
+            raise ValueError(f"params must have shape ({plant.nq},) or ({N}, {plant.nq}), got {tuple(q.shape)}")
+        return q, int(q.dim() == 1)
+
+    def plant_program_eval_device(self, plant, x, u=None, d=None, params=None, stream=None):
+        """`lmpc_plant_program_eval_device`: one step of a `NonlinearPlant` on CUDA tensors x (N, nx), u (N, nu),
+        d (N, nd); returns x+ (N, nx), enqueued on `stream` (default: torch's current stream), not synchronised."""
+        import torch
+        f64, dv = torch.float64, self.device
+        N, dev = int(x.shape[0]), x.device
+        q, shared = self._plant_params(plant, params, N, dev)
+        out = torch.empty((N, plant.nx), dtype=f64, device=dev)
+        p, keep = plant.program()
+        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        check(lib().lmpc_plant_program_eval_device(
+            self._h, ctypes.byref(p), N, _dev_arg(x, "x", f64, N * plant.nx, dv, False), _dev_arg(u, "u", f64, N * plant.nu, dv),
+            _dev_arg(d, "d", f64, N * plant.nd, dv), _dev_arg(q, "params", f64, q.numel() if q is not None else 0, dv), shared,
+            _vp(out.data_ptr()), _vp(st)), self._h)
+        return out
+
+    def simulate_scenario_nonlinear(self, x, T, plant, *, params=None, process=None, measurement_noise=None, Gw=None,
+                                    seed=0, scenario_offset=0, step_offset=0, want=("U", "X"), **kw):
+        """The scenario loop with a nonlinear true plant (`lmpc_simulate_scenario_nonlinear_device`):
+        `simulate_scenario_uncertain` with the plant's row sums replaced by the program of `plant`, a `NonlinearPlant`
+        (its linear measurement rows are the descriptor's).  params: its q, (nq,) shared or (N, nq) per scenario, a
+        host array or a CUDA tensor.  No plant table.  Everything else as `simulate_scenario_uncertain`."""
+        import torch
+        N, nx = int(x.shape[0]), int(x.shape[1])
+        if nx != plant.nx:
+            raise ValueError(f"x has {nx} columns, the plant nx = {plant.nx}")
+        W = torch.empty((int(T), N, nx), dtype=torch.float64, device=x.device) if "W" in want else None
+        un, keep = self.uncertainty(N, nx, process, measurement_noise, Gw, seed, scenario_offset, step_offset, None, None, W)
+        q, shared = self._plant_params(plant, params, N, x.device)
+        p, pkeep = plant.program()
+
+        def launch(desc, n, t, *args):
+            desc.plant = None                         # ignored by this loop
+            check(lib().lmpc_simulate_scenario_nonlinear_device(
+                self._h, n, t, ctypes.byref(desc), ctypes.byref(un), ctypes.byref(p), _vp(q.data_ptr() if q is not None else None),
+                shared, *args), self._h)
+
+        kw.setdefault("nd", plant.nd)
+        kw.setdefault("ny", plant.ny)
+        out = self.simulate_scenario(x, T, np.zeros(1), plant.measurement_rows(), want=tuple(k for k in want if k != "W"),
+                                     launch=launch, **kw)
+        if W is not None:
+            out["W"] = W
+        out["_keep"].append([keep, pkeep, q])
+        return out
+
     def offset_free_check(self, desc, n_offset_free, observer_dims="handle"):
         """`lmpc_scenario_offset_free_check` of a descriptor against this handle's dimensions (host only)."""
         od = getattr(self, "_obs", None) if observer_dims == "handle" else observer_dims
