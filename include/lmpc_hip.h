@@ -896,28 +896,68 @@ int lmpc_simulate_scenario_offset_free(lmpc_handle *h, int64_t N, int T, const l
  *             span_q), span_q = hi_q - lo_q formed once on the host in binary64, one multiply and one add.
  * A draw depends on (seed, global scenario, global step, stream, component) and on nothing of the launch: a run split
  * over calls by scenario (scenario_offset) or by time (step_offset, with x / xhat / uprev carried over and the
- * trajectories shifted by the caller) reproduces the unsplit one bit for bit.  GAUSSIAN draws are deliberately not
- * made on the device: log, cos and sqrt of the device library cannot be restated bit for bit on a host, and a closed
- * loop turns a last-bit difference into another active set; Gaussian noise (example/observer.jl) goes through the
- * supplied block, drawn by the caller, with Gw = B.
+ * trajectories shifted by the caller) reproduces the unsplit one bit for bit.
+ * GAUSSIAN draws (dist == LMPC_NOISE_GAUSSIAN; example/observer.jl:11-12, test/runtests.jl:958,1082): lo holds the means
+ * and hi the standard deviations (HOST, w each).  The same block, key and counter as above; one block gives the
+ * standard normal PAIR (z_2j, z_2j+1) by Box-Muller, through stated operations alone -- never the device library's
+ * log, sin, cos -- so that a host restates a draw bit for bit (a closed loop turns a last-bit difference into another
+ * active set).  With (a, b, c, d) the block's words and unit(a, b) the u above:
+ *   u1  = 1 - unit(a, b)                                   exact, a multiple of 2^-53 in (0, 1]
+ *   u2  = unit(c, d)
+ *   t   = TWO_PI * u2                                      one multiply
+ *   rho = sqrt(-2 * log_(u1))                              one multiply; sqrt: THE correctly rounded binary64 root
+ *   (sn, cs, m) of t as in sin_ / cos_ below (lmpc_plant_program), with their quadrant selection
+ *   z_2j = rho * cos_(t),  z_2j+1 = rho * sin_(t)           an odd count uses half of the last pair
+ *   e_q = mean_q + std_q * z_q                             separate multiply and add, NO clamp
+ * log_(t), for t a multiple of 2^-53 in [2^-53, 1] (all that occurs), on the bits B of t (hi = B >> 32, 32 bits):
+ *   hi = hi + 0x00095F62;  k = (hi >> 20) - 0x3FF;  hi = (hi & 0x000FFFFF) + 0x3FE6A09E
+ *   m  = the binary64 with high word hi and the low word of B        (t = 2^k * m, m in [sqrt(2)/2, sqrt(2)); exact)
+ *   f  = m - 1 (exact);  s = f / (2 + f);  z = s * s
+ *   p  = L7; p = fma(p, z, L6); p = fma(p, z, L5); p = fma(p, z, L4); p = fma(p, z, L3); p = fma(p, z, L2);
+ *   p  = fma(p, z, L1);  R = p * z;  hf = (0.5 * f) * f;  dk = (double)k
+ *   lo = s * (hf + R) + dk * LN2_LO                        (multiply, add, multiply, add: nothing fused)
+ *   log_ = dk * LN2_HI - ((hf - lo) - f)                   (dk * LN2_HI is exact)
+ * with (hexadecimal binary64)
+ *   TWO_PI 0x401921FB54442D18   LN2_HI 0x3FE62E42FEE00000   LN2_LO 0x3DEA39EF35793C76
+ *   L1 0x3FE5555555555593  L2 0x3FD999999997FA04  L3 0x3FD2492494229359  L4 0x3FCC71C51D8E78AF  L5 0x3FC7466496CB03DE
+ *   L6 0x3FC39A09D078C69F  L7 0x3FC2F112DF3E5244
+ * (the classic kernel on [sqrt(2)/2, sqrt(2)), its polynomial by Horner in z).  log_(1) is exactly +0.  Accuracy: below
+ * 2 ulp against a correctly rounded logarithm on the stated domain.  |z| <= sqrt(106 ln 2) = 8.5717..., reached only by
+ * u1 = 2^-53.  std_q == 0 gives the mean.  Correlated process noise goes through Gw (a Cholesky factor of the
+ * covariance); measurement components are independent.
+ * lmpc_noise_draw_host / lmpc_noise_draw_device return the e a DRAWN source (either dist) gives the loop, for N
+ * scenarios from scenario_offset and T steps from step_offset, stream 0 = process or 1 = measurement: out[i * w * T +
+ * k * w + q] -- laid out to be handed back as the per-scenario supplied block {src = out, stride = w * T, w, T}.  The
+ * host one needs no GPU and no handle; the device one is one kernel, one (scenario, step) per lane, asynchronous on
+ * hip_stream, out DEVICE.  Both refuse (LMPC_ERR_BADARG, text in lmpc_last_error(NULL) / (h)): noise NULL, what the
+ * loop refuses of a source, a source without lo / hi, stream not 0 or 1, negative N, T or step_offset, step_offset + T
+ * beyond 2^31 - 1, out NULL.
  * Plant ensemble: n_plants > 0 arrays in the layout of s->plant, one after the other (HOST), staged once per call;
  * scenario i steps array plant_index[i] (DEVICE, N entries), or (scenario_offset + i) mod n_plants with plant_index
  * NULL.  An entry is taken as UNSIGNED, modulo n_plants: no entry addresses outside the staged table.  n_plants == 0:
  * s->plant for every scenario.  The ensemble shares ONE measurement (s->measurement).
  * Every source absent and n_plants == 0 runs and is lmpc_simulate_scenario_device bit for bit.
  * Refused (LMPC_ERR_BADARG, the field's name first, before the GPU is touched): all that lmpc_scenario_check refuses; un
- * NULL; a negative w; lo without hi or the reverse; lo_q > hi_q or a non-finite bound; src.H != 0; process.w not in
+ * NULL; a negative w; dist neither 0 nor 1; with dist == 1: lo (the means) or hi (the standard deviations) NULL, a
+ * non-finite mean, a standard deviation that is negative or not finite; lo without hi or the reverse; lo_q > hi_q or a
+ * non-finite bound; src.H != 0; process.w not in
  * {0, nx} with Gw NULL; measurement.w not in {0, ny}; measurement.w > 0 with s->noise.w > 0; n_plants < 0; n_plants > 0
  * with plants NULL; plant_index with n_plants == 0; W_traj with process.w == 0; step_offset < 0, or step_offset + T
  * beyond 2^31 - 1 (the call alone knows T).  lmpc_scenario_uncertain_check asks that without a handle.
  * lmpc_simulate_scenario_uncertain: the HOST twin (the sources' blocks, plant_index and W_traj HOST as well).
- * NOT extended: the offset-free loop and the explicit controller's loop.
+ * NOT extended: the offset-free loop and the explicit controller's loop, for drawn noise of either distribution; and
+ * the plant program gets no new opcode from this (opcode 17 stays unknown, there is no SQRT or LOG operation).
  */
+#define LMPC_NOISE_UNIFORM 0
+#define LMPC_NOISE_GAUSSIAN 1
 typedef struct lmpc_noise {              /* one noise source                                                      */
     int32_t w;                           /* components; 0 = absent                                                */
+    int32_t dist;                        /* LMPC_NOISE_UNIFORM (0, what a zeroed struct says) or LMPC_NOISE_GAUSSIAN;
+                                          * in the four bytes that were padding: no size or offset moved           */
     lmpc_block src;                      /* DEVICE, supplied draws: w rows, column k at step k, H must be 0; read
                                           * when lo == NULL (src.src == NULL then gives zeros)                    */
-    const double *lo, *hi;               /* HOST, w each: drawn on the device, uniform in [lo_q, hi_q]; both or none */
+    const double *lo, *hi;               /* HOST, w each: drawn on the device, uniform in [lo_q, hi_q]; both or none.
+                                          * dist == LMPC_NOISE_GAUSSIAN: lo = the means, hi = the standard deviations */
 } lmpc_noise;
 typedef struct lmpc_uncertainty {
     lmpc_noise process;                  /* e_k, nw = process.w components                                        */
@@ -939,6 +979,10 @@ int lmpc_simulate_scenario_uncertain_device(lmpc_handle *h, int64_t N, int T, co
 int lmpc_simulate_scenario_uncertain(lmpc_handle *h, int64_t N, int T, const lmpc_scenario_sim *s,
                                      const lmpc_uncertainty *un, double *x, double *xhat, double *uprev, double *U_traj,
                                      double *X_traj, int32_t *flag_min);
+int lmpc_noise_draw_host(const lmpc_noise *noise, uint64_t seed, int stream, int64_t scenario_offset, int64_t N,
+                         int32_t step_offset, int T, double *out);
+int lmpc_noise_draw_device(lmpc_handle *h, const lmpc_noise *noise, uint64_t seed, int stream, int64_t scenario_offset,
+                           int64_t N, int32_t step_offset, int T, double *out, void *hip_stream);
 /* Scoring of a stored run, one thread per scenario: X = the states x_0 .. x_{T-1}, step-major (the first T slices of an
  * X_traj), U = T x N x nu as U_traj.  r: the reference trajectory as in the loop (column k at step k; NULL = zeros).
  * cost_out: N doubles.  violation_out: N doubles (maximum over the steps) and / or violation_steps: T x N, the

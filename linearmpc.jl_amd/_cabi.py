@@ -43,6 +43,7 @@ SYMBOLS = (
     "lmpc_scenario_uncertain_check", "lmpc_simulate_scenario_uncertain_device", "lmpc_simulate_scenario_uncertain",
     "lmpc_plant_program_check", "lmpc_plant_program_eval_host", "lmpc_plant_program_eval_device",
     "lmpc_simulate_scenario_nonlinear_device", "lmpc_simulate_scenario_nonlinear",
+    "lmpc_noise_draw_host", "lmpc_noise_draw_device",
 )
 
 
@@ -105,8 +106,9 @@ class OffsetFree(ctypes.Structure):
 
 
 class Noise(ctypes.Structure):
-    """`lmpc_noise`: one noise source of the uncertain scenario loop, supplied (`src`) or drawn in the box [lo, hi]."""
-    _fields_ = [("w", ctypes.c_int32), ("src", Block), ("lo", ctypes.c_void_p), ("hi", ctypes.c_void_p)]
+    """`lmpc_noise`: one noise source of the uncertain scenario loop, supplied (`src`) or drawn: uniform in the box
+    [lo, hi] (dist 0) or Gaussian with means lo and standard deviations hi (dist 1)."""
+    _fields_ = [("w", ctypes.c_int32), ("dist", ctypes.c_int32), ("src", Block), ("lo", ctypes.c_void_p), ("hi", ctypes.c_void_p)]
 
 
 class Uncertainty(ctypes.Structure):
@@ -290,6 +292,12 @@ def lib():
     L.lmpc_simulate_scenario_nonlinear_device.restype = i32
     L.lmpc_simulate_scenario_nonlinear.argtypes = [vp, i64, i32, sp, up, pp, vp, i32] + [vp] * 6
     L.lmpc_simulate_scenario_nonlinear.restype = i32
+    if hasattr(L, "lmpc_noise_draw_host"):    # (an older build selected with LMPC_HIP_LIB for an A/B lacks them)
+        npn = ctypes.POINTER(Noise)
+        L.lmpc_noise_draw_host.argtypes = [npn, ctypes.c_uint64, i32, i64, i64, ctypes.c_int32, i32, vp]
+        L.lmpc_noise_draw_host.restype = i32
+        L.lmpc_noise_draw_device.argtypes = [vp, npn, ctypes.c_uint64, i32, i64, i64, ctypes.c_int32, i32, vp, vp]
+        L.lmpc_noise_draw_device.restype = i32
     _lib = L
     return L
 

@@ -161,7 +161,11 @@ UncSource pack_source(std::vector<double> &v, const lmpc_noise &n) {
     S.src = to_block(nullptr);
     S.w = n.w; S.drawn = n.lo != nullptr && n.w > 0;
     S.lo = S.span = S.hi = -1;
-    if (S.drawn) {
+    if (S.drawn && n.dist == LMPC_NOISE_GAUSSIAN) {        // the means, then the standard deviations
+        S.drawn = UNC_GAUSSIAN;
+        S.lo = (int)v.size(); v.insert(v.end(), n.lo, n.lo + n.w);
+        S.span = S.hi = (int)v.size(); v.insert(v.end(), n.hi, n.hi + n.w);
+    } else if (S.drawn) {
         S.lo = (int)v.size(); v.insert(v.end(), n.lo, n.lo + n.w);
         S.span = (int)v.size();
         for (int q = 0; q < n.w; q++) v.push_back(n.hi[q] - n.lo[q]);
@@ -252,6 +256,8 @@ int lmpc_simulate_scenario_nonlinear_device(lmpc_handle *h, int64_t N, int T, co
     { const int rcu = upload_constants(h, hostC, K, st); if (rcu != LMPC_OK) return rcu; }
     PlantProg P{}; NlPlant Q{};
     device_program(K.c, po, prog, q, q_shared, P, Q);
+    // the instantiations that hold the Gaussian sequence serve a run with such a source, and no other
+    const bool gauss = U.process.drawn == UNC_GAUSSIAN || U.meas.drawn == UNC_GAUSSIAN;
     const bool obs = s->use_observer != 0;
     const bool wantCost = s->cost && (s->cost_out || s->violation_out);
     const bool needUlast = wantCost && s->cost_out && s->cost->Rr;
@@ -295,7 +301,8 @@ int lmpc_simulate_scenario_nonlinear_device(lmpc_handle *h, int64_t N, int T, co
         U.step = (uint32_t)(un->step_offset + k);
         U.w_out = un->W_traj ? un->W_traj + (size_t)k * N * nx : nullptr;
         dispatch_nx(nx, [&](auto NX) {
-            hipLaunchKernelGGL(uncertain_pre_kernel<decltype(NX)::value>, dim3(grid), dim3(256), sizeof(double) * 256 * (size_t)nx, st, A, K, U);
+            if (gauss) hipLaunchKernelGGL((uncertain_pre_kernel<decltype(NX)::value, true>), dim3(grid), dim3(256), sizeof(double) * 256 * (size_t)nx, st, A, K, U);
+            else hipLaunchKernelGGL(uncertain_pre_kernel<decltype(NX)::value>, dim3(grid), dim3(256), sizeof(double) * 256 * (size_t)nx, st, A, K, U);
         });
         HIP_TRY(h, hipGetLastError());
         const uint64_t *wm = (s->warm && k > 0) ? h->simAct : nullptr;
@@ -305,7 +312,9 @@ int lmpc_simulate_scenario_nonlinear_device(lmpc_handle *h, int64_t N, int T, co
         B.xtraj_next = X_traj ? X_traj + (size_t)(k + 1) * N * nx : nullptr;
         B.utraj = U_traj ? U_traj + (size_t)k * N * nu : nullptr;
         dispatch_nx(nx, [&](auto NX) {
-            if (wantCost) hipLaunchKernelGGL((nonlinear_post_kernel<decltype(NX)::value, true>), dim3(gridPost), dim3(NL_LANES), lds, st, B, K, U, P, Q);
+            if (gauss && wantCost) hipLaunchKernelGGL((nonlinear_post_kernel<decltype(NX)::value, true, true>), dim3(gridPost), dim3(NL_LANES), lds, st, B, K, U, P, Q);
+            else if (gauss) hipLaunchKernelGGL((nonlinear_post_kernel<decltype(NX)::value, false, true>), dim3(gridPost), dim3(NL_LANES), lds, st, B, K, U, P, Q);
+            else if (wantCost) hipLaunchKernelGGL((nonlinear_post_kernel<decltype(NX)::value, true>), dim3(gridPost), dim3(NL_LANES), lds, st, B, K, U, P, Q);
             else hipLaunchKernelGGL((nonlinear_post_kernel<decltype(NX)::value, false>), dim3(gridPost), dim3(NL_LANES), lds, st, B, K, U, P, Q);
         });
         HIP_TRY(h, hipGetLastError());

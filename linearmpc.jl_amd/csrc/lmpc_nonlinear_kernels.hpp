@@ -58,7 +58,7 @@ inline __global__ __launch_bounds__(NL_LANES) void plant_program_eval_kernel(Pla
 }
 
 // POST kernel of step k of the nonlinear loop
-template <int NXT, bool COST>
+template <int NXT, bool COST, bool GAUSS = false>
 __global__ __launch_bounds__(NL_LANES) void nonlinear_post_kernel(ScnPost A, ScnConst K, UncStep U, PlantProg P, NlPlant Q) {
     extern __shared__ double nl_lds[];
     const long long i = (long long)blockIdx.x * NL_LANES + threadIdx.x;
@@ -101,7 +101,7 @@ __global__ __launch_bounds__(NL_LANES) void nonlinear_post_kernel(ScnPost A, Scn
     for_nx<NXT>(nx, [&](int a) { xn[a] = E.slot(Q.out_slot[a]); });
     const int nw = U.process.w;
     if (nw > 0) {
-        UncDraws de(U, i, 0u);
+        typename std::conditional<GAUSS, UncDrawsGauss, UncDraws>::type de(U, i, 0u);
         if (U.gw < 0) {
             for_nx<NXT>(nx, [&](int a) {
                 const double e = unc_value(U.process, K.c, de, i, A.k, a);

@@ -16,9 +16,28 @@ using namespace lmpc;
 
 namespace {
 
+// a Gaussian source: lo = the means, hi = the standard deviations, both required
+std::string gaussian_problem(const char *name, const lmpc_noise &n) {
+    auto bad = [&](const char *f, const std::string &why) { return std::string(name) + "." + f + ": " + why; };
+    if (!n.lo) return bad("lo", "NULL with dist == LMPC_NOISE_GAUSSIAN (the means)");
+    if (!n.hi) return bad("hi", "NULL with dist == LMPC_NOISE_GAUSSIAN (the standard deviations)");
+    for (int q = 0; q < n.w; q++) {
+        if (!std::isfinite(n.lo[q])) return bad("lo", "non-finite mean at component " + std::to_string(q));
+        if (!std::isfinite(n.hi[q])) return bad("hi", "non-finite standard deviation at component " + std::to_string(q));
+        if (n.hi[q] < 0.0) return bad("hi", "negative standard deviation at component " + std::to_string(q));
+    }
+    if (n.src.H != 0) return bad("src.H", "a noise block has no preview");
+    if (n.src.w < 0) return bad("src.w", "negative width");
+    if (n.src.stride < 0) return bad("src.stride", "negative stride");
+    return "";
+}
+
 std::string noise_problem(const char *name, const lmpc_noise &n) {
     auto bad = [&](const char *f, const std::string &why) { return std::string(name) + "." + f + ": " + why; };
     if (n.w < 0) return bad("w", "negative count");
+    if (n.dist != LMPC_NOISE_UNIFORM && n.dist != LMPC_NOISE_GAUSSIAN)
+        return bad("dist", "must be LMPC_NOISE_UNIFORM (0) or LMPC_NOISE_GAUSSIAN (1), got " + std::to_string(n.dist));
+    if (n.dist == LMPC_NOISE_GAUSSIAN) return gaussian_problem(name, n);
     if (n.lo && !n.hi) return bad("hi", "NULL with lo given (both or none)");
     if (n.hi && !n.lo) return bad("lo", "NULL with hi given (both or none)");
     if (n.lo) {
@@ -81,7 +100,11 @@ UncSource pack_source(std::vector<double> &v, const lmpc_noise &n) {
     S.src = to_block(nullptr);
     S.w = n.w; S.drawn = n.lo != nullptr && n.w > 0;
     S.lo = S.span = S.hi = -1;
-    if (S.drawn) {
+    if (S.drawn && n.dist == LMPC_NOISE_GAUSSIAN) {        // the means, then the standard deviations
+        S.drawn = UNC_GAUSSIAN;
+        S.lo = (int)v.size(); v.insert(v.end(), n.lo, n.lo + n.w);
+        S.span = S.hi = (int)v.size(); v.insert(v.end(), n.hi, n.hi + n.w);
+    } else if (S.drawn) {
         S.lo = (int)v.size(); v.insert(v.end(), n.lo, n.lo + n.w);
         S.span = (int)v.size();
         for (int q = 0; q < n.w; q++) v.push_back(n.hi[q] - n.lo[q]);
@@ -93,9 +116,108 @@ UncSource pack_source(std::vector<double> &v, const lmpc_noise &n) {
     return S;
 }
 
+// ---- lmpc_noise_draw_*: the e of one (global scenario, global step, stream), all w components, as UncDraws and
+// unc_value give them to the loop: one source for the CPU and the GPU.  c = [lo | span | hi] (uniform) or [mean | std].
+__host__ __device__ __forceinline__ void noise_draw_record(const double *__restrict__ c, int w, int gaussian, uint32_t k0,
+                                                           uint32_t k1, unsigned long long g, uint32_t step, uint32_t stream,
+                                                           double *__restrict__ out) {
+    for (int j = 0; 2 * j < w; j++) {
+        uint32_t r[4] = {(uint32_t)g, (uint32_t)(g >> 32), step, (stream << 16) | (uint32_t)j};
+        philox4x32_10(r, k0, k1);
+        double a = philox_unit(r[0], r[1]), b = philox_unit(r[2], r[3]);
+        if (gaussian) {
+            const double ua = a, ub = b;
+            nm_gauss_pair(ua, ub, a, b);
+        }
+        for (int q = 2 * j; q < 2 * j + 2 && q < w; q++) {
+            const double v = q & 1 ? b : a;
+            if (gaussian) {
+                out[q] = nm_gauss_value(c[q], c[w + q], v);
+            } else {
+                const double e = LMPC_PP_ADD(c[q], LMPC_PP_MUL(v, c[w + q])), hi = c[2 * w + q];
+                out[q] = e < hi ? e : hi;
+            }
+        }
+    }
+}
+
+// one (scenario, step) per lane: record idx = i * T + k goes to out + idx * w
+__global__ __launch_bounds__(256) void noise_draw_kernel(const double *__restrict__ c, int w, int gaussian, uint32_t k0, uint32_t k1,
+                                                         unsigned long long goff, uint32_t step0, uint32_t stream, int T,
+                                                         long long total, double *__restrict__ out) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const long long i = idx / T;
+    const int k = (int)(idx - i * T);
+    noise_draw_record(c, w, gaussian, k0, k1, goff + (unsigned long long)i, step0 + (uint32_t)k, stream, out + idx * w);
+}
+
+std::string draw_problem(const lmpc_noise *n, int stream, int64_t N, int32_t step_offset, int T, const double *out) {
+    if (!n) return "noise: NULL source";
+    const std::string msg = noise_problem("noise", *n);
+    if (!msg.empty()) return msg;
+    if (!n->lo) return "noise.lo: NULL (a supplied source draws nothing)";
+    if (stream != 0 && stream != 1) return "stream: must be 0 (process) or 1 (measurement), got " + std::to_string(stream);
+    if (N < 0) return "N: negative";
+    if (T < 0) return "T: negative";
+    if (step_offset < 0) return "step_offset: negative";
+    if ((int64_t)step_offset + T > 2147483647LL) return "step_offset: step_offset + T exceeds 2^31 - 1";
+    if (T > 0 && N > (int64_t)0x7fffffff * 256 / T) return "N: N * T exceeds what one launch covers";
+    if (N > 0 && T > 0 && n->w > 0 && !out) return "out: NULL";
+    return "";
+}
+
+// [lo | span | hi] or [mean | std] as noise_draw_record takes them
+std::vector<double> draw_constants(const lmpc_noise &n) {
+    std::vector<double> c(n.lo, n.lo + n.w);
+    if (n.dist == LMPC_NOISE_GAUSSIAN) {
+        c.insert(c.end(), n.hi, n.hi + n.w);
+    } else {
+        for (int q = 0; q < n.w; q++) c.push_back(n.hi[q] - n.lo[q]);
+        c.insert(c.end(), n.hi, n.hi + n.w);
+    }
+    return c;
+}
+
 }  // namespace
 
 extern "C" {
+
+int lmpc_noise_draw_host(const lmpc_noise *noise, uint64_t seed, int stream, int64_t scenario_offset, int64_t N,
+                         int32_t step_offset, int T, double *out) {
+    const std::string msg = draw_problem(noise, stream, N, step_offset, T, out);
+    if (!msg.empty()) return fail(nullptr, LMPC_ERR_BADARG, "lmpc_noise_draw_host: " + msg);
+    if (N == 0 || T == 0 || noise->w == 0) return LMPC_OK;
+    const std::vector<double> c = draw_constants(*noise);
+    const int w = noise->w, gaussian = noise->dist == LMPC_NOISE_GAUSSIAN;
+    const uint32_t k0 = (uint32_t)(seed & 0xffffffffu), k1 = (uint32_t)(seed >> 32);
+    for (int64_t i = 0; i < N; i++)
+        for (int k = 0; k < T; k++)
+            noise_draw_record(c.data(), w, gaussian, k0, k1, (unsigned long long)scenario_offset + (unsigned long long)i,
+                              (uint32_t)(step_offset + k), (uint32_t)stream, out + ((size_t)i * T + k) * w);
+    return LMPC_OK;
+}
+
+int lmpc_noise_draw_device(lmpc_handle *h, const lmpc_noise *noise, uint64_t seed, int stream, int64_t scenario_offset,
+                           int64_t N, int32_t step_offset, int T, double *out, void *hip_stream) {
+    if (!h) return LMPC_ERR_BADARG;
+    const std::string msg = draw_problem(noise, stream, N, step_offset, T, out);
+    if (!msg.empty()) return fail(h, LMPC_ERR_BADARG, "lmpc_noise_draw_device: " + msg);
+    if (N == 0 || T == 0 || noise->w == 0) return LMPC_OK;
+    LMPC_NEED_DEVICE(h);
+    LMPC_ENTER_DEVICE(h);
+    hipStream_t st = (hipStream_t)hip_stream;
+    ScnConst K{};
+    const std::vector<double> c = draw_constants(*noise);
+    { const int rcu = upload_constants(h, c, K, st); if (rcu != LMPC_OK) return rcu; }
+    const long long total = (long long)N * T;
+    hipLaunchKernelGGL(noise_draw_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, K.c, noise->w,
+                       (int)(noise->dist == LMPC_NOISE_GAUSSIAN), (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32),
+                       (unsigned long long)scenario_offset, (uint32_t)step_offset, (uint32_t)stream, T, total, out);
+    HIP_TRY(h, hipGetLastError());
+    return LMPC_OK;
+}
+
 
 int lmpc_scenario_uncertain_check(int nth, int nout, const lmpc_observer *observer, const lmpc_scenario_sim *s,
                                   const lmpc_uncertainty *un) {
@@ -135,6 +257,8 @@ int lmpc_simulate_scenario_uncertain_device(lmpc_handle *h, int64_t N, int T, co
     U.key0 = (uint32_t)(un->seed & 0xffffffffu); U.key1 = (uint32_t)(un->seed >> 32);
     U.goff = (unsigned long long)un->scenario_offset;
     { const int rcu = upload_constants(h, hostC, K, st); if (rcu != LMPC_OK) return rcu; }
+    // the instantiations that hold the Gaussian sequence serve a run with such a source, and no other
+    const bool gauss = U.process.drawn == UNC_GAUSSIAN || U.meas.drawn == UNC_GAUSSIAN;
     const bool obs = s->use_observer != 0;
     const bool wantCost = s->cost && (s->cost_out || s->violation_out);
     const bool needUlast = wantCost && s->cost_out && s->cost->Rr;
@@ -176,7 +300,8 @@ int lmpc_simulate_scenario_uncertain_device(lmpc_handle *h, int64_t N, int T, co
         U.step = (uint32_t)(un->step_offset + k);
         U.w_out = un->W_traj ? un->W_traj + (size_t)k * N * nx : nullptr;
         dispatch_nx(nx, [&](auto NX) {
-            hipLaunchKernelGGL(uncertain_pre_kernel<decltype(NX)::value>, dim3(grid), dim3(256), sizeof(double) * 256 * (size_t)nx, st, A, K, U);
+            if (gauss) hipLaunchKernelGGL((uncertain_pre_kernel<decltype(NX)::value, true>), dim3(grid), dim3(256), sizeof(double) * 256 * (size_t)nx, st, A, K, U);
+            else hipLaunchKernelGGL(uncertain_pre_kernel<decltype(NX)::value>, dim3(grid), dim3(256), sizeof(double) * 256 * (size_t)nx, st, A, K, U);
         });
         HIP_TRY(h, hipGetLastError());
         const uint64_t *wm = (s->warm && k > 0) ? h->simAct : nullptr;
@@ -186,7 +311,9 @@ int lmpc_simulate_scenario_uncertain_device(lmpc_handle *h, int64_t N, int T, co
         B.xtraj_next = X_traj ? X_traj + (size_t)(k + 1) * N * nx : nullptr;
         B.utraj = U_traj ? U_traj + (size_t)k * N * nu : nullptr;
         dispatch_nx(nx, [&](auto NX) {
-            if (wantCost) hipLaunchKernelGGL((uncertain_post_kernel<decltype(NX)::value, true>), dim3(grid), dim3(256), 0, st, B, K, U);
+            if (gauss && wantCost) hipLaunchKernelGGL((uncertain_post_kernel<decltype(NX)::value, true, true>), dim3(grid), dim3(256), 0, st, B, K, U);
+            else if (gauss) hipLaunchKernelGGL((uncertain_post_kernel<decltype(NX)::value, false, true>), dim3(grid), dim3(256), 0, st, B, K, U);
+            else if (wantCost) hipLaunchKernelGGL((uncertain_post_kernel<decltype(NX)::value, true>), dim3(grid), dim3(256), 0, st, B, K, U);
             else hipLaunchKernelGGL((uncertain_post_kernel<decltype(NX)::value, false>), dim3(grid), dim3(256), 0, st, B, K, U);
         });
         HIP_TRY(h, hipGetLastError());

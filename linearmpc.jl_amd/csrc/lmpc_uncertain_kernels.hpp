@@ -15,6 +15,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
+#include "lmpc_noise_math.hpp"
 #include "lmpc_scenario_kernels.hpp"
 
 namespace lmpc {
@@ -42,12 +45,16 @@ __host__ __device__ __forceinline__ double philox_unit(uint32_t a, uint32_t b) {
     return (double)(((uint64_t)a << 21) | (uint64_t)(b >> 11)) * 0x1.0p-53;
 }
 
-// one noise source: a supplied block (drawn == 0: column k of src, absent = zeros) or the box [lo, hi] in ScnConst::c
+// one noise source: a supplied block (drawn == 0: column k of src, absent = zeros), the box [lo, hi] in ScnConst::c
+// (drawn == 1) or a Gaussian (drawn == 2: the record carries the descriptor's dist as drawn = 1 + dist, so its size and
+// the kernels' argument layout are the ones they had)
 struct UncSource {
     ThetaBlock src;
     int w, drawn;
-    int lo, span, hi;                 // offsets in doubles into ScnConst::c; span = hi - lo formed on the host
+    int lo, span, hi;                 // offsets in doubles into ScnConst::c; span = hi - lo formed on the host;
+                                      // Gaussian: lo = the means, span = hi = the standard deviations
 };
+constexpr int UNC_UNIFORM = 1, UNC_GAUSSIAN = 2;
 
 // what one step's launches know of the uncertainty
 struct UncStep {
@@ -84,17 +91,39 @@ struct UncDraws {
     }
 };
 
-// component q of a source at step k for scenario i: e = min(hi, lo + u * span), one multiply and one add
-__device__ __forceinline__ double unc_value(const UncSource &S, const double *__restrict__ c, UncDraws &D, long long i, int k, int q) {
+// UncDraws of the kernels instantiated with GAUSS: the standard normal pair of a block (lmpc_noise_math.hpp) is formed
+// when its first component is asked for and kept next to the words, which the uniform path goes on using.
+struct UncDrawsGauss : UncDraws {
+    double z0, z1;
+    int jz;
+    __device__ __forceinline__ UncDrawsGauss(const UncStep &U, long long i, uint32_t stream_) : UncDraws(U, i, stream_), z0(0.0), z1(0.0), jz(-1) {}
+    __device__ __forceinline__ double normal(int q) {
+        if ((q >> 1) != jz) {
+            const double ua = unit(q & ~1), ub = unit(q | 1);
+            jz = q >> 1;
+            nm_gauss_pair(ua, ub, z0, z1);
+        }
+        return (q & 1) ? z1 : z0;
+    }
+};
+
+// component q of a source at step k for scenario i: e = min(hi, lo + u * span), one multiply and one add; with Draws =
+// UncDrawsGauss a Gaussian source gives e = mean + std * z, one multiply and one add, no clamp
+template <class Draws>
+__device__ __forceinline__ double unc_value(const UncSource &S, const double *__restrict__ c, Draws &D, long long i, int k, int q) {
     if (!S.drawn) return block_at(S.src, i, k, q);
+    if constexpr (std::is_same<Draws, UncDrawsGauss>::value)
+        if (S.drawn == UNC_GAUSSIAN) return nm_gauss_value(c[S.lo + q], c[S.span + q], D.normal(q));
     const double e = __dadd_rn(c[S.lo + q], __dmul_rn(D.unit(q), c[S.span + q]));
     const double hi = c[S.hi + q];
     return e < hi ? e : hi;
 }
 
 // PRE kernel of step k: scenario_pre_kernel with v_j added to ym_j as the last addition (the place the descriptor's
-// noise block has; the two are exclusive).  Same two phases, same 256 * nx doubles of dynamic LDS.
-template <int NXT>
+// noise block has; the two are exclusive).  Same two phases, same 256 * nx doubles of dynamic LDS.  GAUSS: the
+// instantiation that can draw a Gaussian source (chosen on the host when either source is one), so that the logarithm,
+// the square root and sin_ / cos_ cost the other runs no register.
+template <int NXT, bool GAUSS = false>
 __global__ __launch_bounds__(256) void uncertain_pre_kernel(ScnPre A, ScnConst K, UncStep U) {
     extern __shared__ double unc_lds[];
     constexpr int NXA = NXT > 0 ? NXT : 32;
@@ -109,7 +138,7 @@ __global__ __launch_bounds__(256) void uncertain_pre_kernel(ScnPre A, ScnConst K
         if (obs) for_nx<NXT>(nx, [&](int c) { xh[c] = A.xhat[i * nx + c]; xn[c] = xh[c]; });
         else for_nx<NXT>(nx, [&](int c) { xn[c] = xo[c]; });
         const int ms = 1 + nx + A.nd;
-        UncDraws dv(U, i, 1u);
+        typename std::conditional<GAUSS, UncDrawsGauss, UncDraws>::type dv(U, i, 1u);
         for (int j = 0; j < A.ny; j++) {
             const double *mr = K.c + K.meas + j * ms;
             double ym = mr[0], y = 0.0;
@@ -158,7 +187,7 @@ __global__ __launch_bounds__(256) void uncertain_pre_kernel(ScnPre A, ScnConst K
 // the finished row sums, x_a <- x_a + Gw_a0 e_0 + Gw_a1 e_1 + ... term by term (x_a <- x_a + e_a without Gw).  W_traj:
 // row a = 0 + Gw_a0 e_0 + ... in the same order, or e_a.  The terms are visited component by component (one draw per
 // component) with the rows' running sums side by side, which is the same order of additions for every row.
-template <int NXT, bool COST>
+template <int NXT, bool COST, bool GAUSS = false>
 __global__ __launch_bounds__(256) void uncertain_post_kernel(ScnPost A, ScnConst K, UncStep U) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= A.n) return;
@@ -202,7 +231,7 @@ __global__ __launch_bounds__(256) void uncertain_post_kernel(ScnPost A, ScnConst
     dynamics_rows<NXT>(K.c + K.plant + prow, xo, xn, nx, nu, A.nd, u, dk);
     const int nw = U.process.w;
     if (nw > 0) {
-        UncDraws de(U, i, 0u);
+        typename std::conditional<GAUSS, UncDrawsGauss, UncDraws>::type de(U, i, 0u);
         if (U.gw < 0) {
             for_nx<NXT>(nx, [&](int a) {
                 const double e = unc_value(U.process, K.c, de, i, A.k, a);

@@ -9,13 +9,15 @@ at once, on the scenario loop of the library (`lmpc_simulate_scenario_device`, i
                                                   from given gains; as `observer=` it adds dhats
     evaluate_cost / constraint_violation          utils.jl:397-425, on the device
     Uniform(lo, hi)                               a noise source drawn on the device, uniform in the box [lo, hi]
+    Gaussian(mean, std)                           a noise source drawn on the device, independent normal components
+    noise_draw(source, ...)                       the draws of either on the host (`lmpc_noise_draw_host`)
 
 Of the reference's plant hook (`Simulation(dynamics, mpc)`, `scenario.dynamics`) the two uses its manual, examples and
 tests make are covered (`lmpc_simulate_scenario_uncertain_device`): additive process noise on the state --
 `Scenario(process_noise=)` with `Simulation(Gw=, seed=)` -- and plants that are not the controller's model -- a list
-of `Plant`s.  Draws made on the device are uniform (`Uniform`); Gaussian noise (example/observer.jl) is drawn by the
-caller and given as an array, with Gw = B: the device library's log / cos / sqrt cannot be restated bit for bit on a
-host.  A NONLINEAR true plant -- the `true_dynamics` x + Ts f(x, u, d) of a controller built from `Model(f, h, xo, uo, Ts)`
+of `Plant`s.  Draws made on the device are uniform (`Uniform`) or Gaussian (`Gaussian`: example/observer.jl's
+`B*randn` is `Gaussian(0, 1)` with Gw = B, a covariance goes through Gw as its Cholesky factor); both are the stated
+sequences of include/lmpc_hip.h, which a host restates bit for bit (`noise_draw`).  A NONLINEAR true plant -- the `true_dynamics` x + Ts f(x, u, d) of a controller built from `Model(f, h, xo, uo, Ts)`
 (simulation.jl:40,110,126, model.jl:87) -- is a `NonlinearPlant` (nonlinear.py): a Python function traced into a plant
 program that `lmpc_simulate_scenario_nonlinear_device` interprets, with `params=` as its per-scenario parameters.
 Callbacks (`scenario.callback`) and a nonlinear measurement have no counterpart.  An MPC with reference condensation
@@ -28,7 +30,7 @@ import numpy as np
 from .solver import BatchedQP
 
 __all__ = ["Plant", "Scenario", "Simulation", "evaluate_cost", "constraint_violation", "OffsetFreeObserver",
-           "offset_free_observer", "Uniform"]
+           "offset_free_observer", "Uniform", "Gaussian", "noise_draw"]
 
 
 class Plant:
@@ -69,10 +71,44 @@ class Uniform:
             raise ValueError("the bounds must be finite with lo <= hi")
 
 
+class Gaussian:
+    """A noise source drawn on the device: component q normal with mean[q] and standard deviation std[q] (std == 0: the
+    constant mean), independent components, by the Box-Muller sequence include/lmpc_hip.h states on the same
+    counter-based generator as `Uniform` -- a draw depends on (seed, scenario, step, stream, component) alone.  A scalar
+    mean or std is repeated to the other's length."""
+    dist = 1                                      # LMPC_NOISE_GAUSSIAN
+
+    def __init__(self, mean, std):
+        mean, std = np.atleast_1d(np.asarray(mean, float)), np.atleast_1d(np.asarray(std, float))
+        if mean.ndim != 1 or std.ndim != 1:
+            raise ValueError("mean and std must be scalars or vectors")
+        if mean.size == 1 and std.size > 1:
+            mean = np.repeat(mean, std.size)
+        if std.size == 1 and mean.size > 1:
+            std = np.repeat(std, mean.size)
+        if mean.shape != std.shape:
+            raise ValueError("mean and std must have the same length")
+        if not np.isfinite(mean).all():
+            raise ValueError("the means must be finite")
+        if not (np.isfinite(std).all() and (std >= 0).all()):
+            raise ValueError("the standard deviations must be finite and not negative")
+        self.mean, self.std = mean, std
+
+    lo = property(lambda self: self.mean)         # the fields of lmpc_noise that carry them
+    hi = property(lambda self: self.std)
+
+
+def noise_draw(source, N, T, seed=0, stream=0, scenario_offset=0, step_offset=0):
+    """`lmpc_noise_draw_host`: the e a `Uniform` or `Gaussian` source gives the loop for scenarios scenario_offset ..
+    + N - 1 and steps step_offset .. + T - 1 (stream 0: process noise, 1: measurement noise), computed on the CPU:
+    (N, w, T), the shape of a per-scenario supplied block.  Needs no GPU."""
+    return BatchedQP.noise_draw_host(source, N, T, seed, stream, scenario_offset, step_offset)
+
+
 class Scenario:
     """simulation.jl:13-35 for N_scen scenarios.  Trajectories keep their own length; `trajectory` gives them over
     the N steps of the run, cut or held at the last column (simulation.jl:69-88).  process_noise (added to the state
-    through Simulation's Gw) and measurement_noise (added to ym, as `noise` is): a `Uniform`, drawn on the device, or
+    through Simulation's Gw) and measurement_noise (added to ym, as `noise` is): a `Uniform` or a `Gaussian`, drawn on the device, or
     an array (w, T) / (N_scen, w, T) of supplied draws."""
 
     def __init__(self, x0, N=1000, r=None, d=None, p=None, noise=None, process_noise=None, measurement_noise=None):
@@ -84,7 +120,7 @@ class Scenario:
         if self.noise is not None and measurement_noise is not None:
             raise ValueError("noise and measurement_noise are the same slot: give one of them")
         self.process_noise, self.measurement_noise = (
-            a if isinstance(a, Uniform) else self._traj(a, k)
+            a if isinstance(a, (Uniform, Gaussian)) else self._traj(a, k)
             for a, k in ((process_noise, "process_noise"), (measurement_noise, "measurement_noise")))
 
     def _traj(self, a, name):
@@ -254,7 +290,7 @@ class Simulation:
     Uncertainty (`lmpc_simulate_scenario_uncertain_device`): the scenario's process_noise e_k acts as w_k = Gw e_k on
     the state (Gw None: identity) and `ws` (N_scen, nx, N) is added; its measurement_noise is added to ym; plant = a
     list of `Plant`s of equal nx, nu, nd, ny: scenario i is stepped by plant plant_index[i] (default i mod the list's
-    length) and all share the FIRST one's measurement rows; seed keys the draws of a `Uniform`.  Without any of these
+    length) and all share the FIRST one's measurement rows; seed keys the draws of a `Uniform` or a `Gaussian`.  Without any of these
     the existing path runs unchanged; with an `ExplicitMPC` or an `OffsetFreeObserver` they raise ValueError.
     plant = a `NonlinearPlant` (`lmpc_simulate_scenario_nonlinear_device`): the true plant is its traced program, stepped
     on the device; params (nq,) or (N_scen, nq) are its q; process_noise, measurement_noise, Gw, seed and observer= as
@@ -333,7 +369,7 @@ class Simulation:
             (lambda *a, **kw: empc.controller.simulate_scenario_device(*a, mode=mode, **kw))
         want = ("U", "X", "Y", "Ym", "Xhat") + (("D",) if plant.nd else ())
         if uncertain or nonlinear:
-            src = lambda a: a if (a is None or isinstance(a, Uniform)) else torch.from_numpy(np.ascontiguousarray(a[..., :T])).to(dev)
+            src = lambda a: a if (a is None or isinstance(a, (Uniform, Gaussian))) else torch.from_numpy(np.ascontiguousarray(a[..., :T])).to(dev)
             pidx = None if plant_index is None else torch.from_numpy(
                 np.ascontiguousarray(np.asarray(plant_index).reshape(S).astype(np.int32))).to(dev)
             run = lambda *a, want, **kw: model.simulate_scenario_uncertain(

@@ -629,7 +629,7 @@ class BatchedQP:
     def uncertainty(self, N, nx, process=None, measurement_noise=None, Gw=None, seed=0, scenario_offset=0, step_offset=0,
                     plants=None, plant_index=None, W=None):
         """`lmpc_uncertainty` from its parts.  process / measurement_noise: None, an object with `lo` and `hi` (drawn on
-        the device, uniform in the box) or a CUDA tensor (w, Tc) shared / (N, w, Tc) per scenario (supplied draws).
+        the device: uniform in the box, or, with `dist == 1`, Gaussian with means lo and standard deviations hi) or a CUDA tensor (w, Tc) shared / (N, w, Tc) per scenario (supplied draws).
         Gw (nx, nw) host array or None.  plants: (n_plants, nx, 1 + nx + nu + nd) host array or None; plant_index: int32
         CUDA tensor (N,) or None.  W: the (T, N, nx) CUDA tensor that takes W_traj, or None.  Returns (struct, keep-alive)."""
         un, keep = _cabi.Uncertainty(), []
@@ -641,7 +641,7 @@ class BatchedQP:
                 lo, hi = _f64(np.asarray(a.lo, float).reshape(-1)), _f64(np.asarray(a.hi, float).reshape(-1))
                 if lo.shape != hi.shape:
                     raise ValueError("lo and hi of a drawn noise source must have the same length")
-                dst.w, dst.lo, dst.hi = lo.size, lo.ctypes.data, hi.ctypes.data
+                dst.w, dst.dist, dst.lo, dst.hi = lo.size, int(getattr(a, "dist", 0)), lo.ctypes.data, hi.ctypes.data
                 keep.extend([lo, hi])
                 return
             if a.dim() == 3 and a.shape[0] != N:
@@ -673,6 +673,39 @@ class BatchedQP:
             un.W_traj = W.data_ptr()
         return un, keep
 
+    @staticmethod
+    def _drawn_source(source):
+        """`lmpc_noise` of an object with `lo` and `hi` (and `dist`): (struct, keep-alive)"""
+        lo, hi = _f64(np.asarray(source.lo, float).reshape(-1)), _f64(np.asarray(source.hi, float).reshape(-1))
+        if lo.shape != hi.shape:
+            raise ValueError("lo and hi of a drawn noise source must have the same length")
+        n = _cabi.Noise()
+        n.w, n.dist, n.lo, n.hi = lo.size, int(getattr(source, "dist", 0)), lo.ctypes.data, hi.ctypes.data
+        return n, (lo, hi)
+
+    @staticmethod
+    def noise_draw_host(source, N, T, seed=0, stream=0, scenario_offset=0, step_offset=0):
+        """`lmpc_noise_draw_host`: the draws of a `Uniform` / `Gaussian` source on the CPU as a numpy array (N, w, T), a
+        view of the (N, T, w) buffer the C side fills.  Needs no GPU and no handle."""
+        n, keep = BatchedQP._drawn_source(source)
+        out = np.empty((int(N), int(T), n.w))
+        check(lib().lmpc_noise_draw_host(ctypes.byref(n), int(seed) & (2 ** 64 - 1), int(stream), int(scenario_offset), int(N),
+                                         int(step_offset), int(T), _vp(out.ctypes.data)))
+        return out.transpose(0, 2, 1)
+
+    def noise_draw(self, source, N, T, seed=0, stream=0, scenario_offset=0, step_offset=0, noise_stream=None):
+        """`lmpc_noise_draw_device`: the same draws made on this handle's GPU, one kernel, enqueued on `noise_stream`
+        (default: torch's current stream), not synchronised.  Returns a CUDA tensor (N, w, T), a view of the contiguous
+        (N, T, w) buffer: given back as `process=` / `measurement_noise=` it is the supplied block without a copy."""
+        import torch
+        n, keep = self._drawn_source(source)
+        dev = torch.device("cuda", self.device)
+        out = torch.empty((int(N), int(T), n.w), dtype=torch.float64, device=dev)
+        st = torch.cuda.current_stream(dev).cuda_stream if noise_stream is None else noise_stream
+        check(lib().lmpc_noise_draw_device(self._h, ctypes.byref(n), int(seed) & (2 ** 64 - 1), int(stream), int(scenario_offset),
+                                           int(N), int(step_offset), int(T), _vp(out.data_ptr()), _vp(st)), self._h)
+        return out.transpose(1, 2)
+
     def uncertain_check(self, desc, un, observer_dims="handle"):
         """`lmpc_scenario_uncertain_check` of a descriptor and an uncertainty against this handle's dimensions (host only)."""
         od = getattr(self, "_obs", None) if observer_dims == "handle" else observer_dims
@@ -685,7 +718,7 @@ class BatchedQP:
         """The scenario loop under uncertainty (`lmpc_simulate_scenario_uncertain_device`): `simulate_scenario` with
         additive process noise w_k = Gw e_k on the state, additive measurement noise and a table of plant variants
         (`uncertainty` says how each is given; `plant` stays the descriptor's plant and steps everyone without
-        `plants`).  The draws are uniform in a box: Gaussian noise is drawn by the caller and supplied as a block.
+        `plants`).  A drawn source is uniform in a box (`Uniform`) or Gaussian (`Gaussian`).
         want may name "W" (T, N, nx), the w_k that acted.  Everything else, and the dict returned, as `simulate_scenario`."""
         import torch
         N, nx = int(x.shape[0]), int(x.shape[1])
