@@ -509,6 +509,26 @@ int lmpc_wave_stats(lmpc_handle *h, unsigned long long out[5]);
 #define LMPC_WAVE_INFO_WORDS 20
 int lmpc_wave_launch_info(const lmpc_handle *h, int32_t *out, int max);
 
+/* The same for the four-problems-per-wavefront kernel (row_kernel): the handle's four most recent row-kernel launches,
+ * OLDEST first, LMPC_ROW_INFO_WORDS words each; returns how many (< 0: error).  A call makes at most one (the only pass
+ * of a batch, or the first of two -- the second is a wavefront-kernel launch and shows in lmpc_wave_launch_info).
+ * Host memory only.  A batch the row kernel does not take ("row_kernel" 1 is a request: warm starts, the Gram form, a
+ * closed loop, an ACTIVE row, an iteration limit below 2, no covering shape, ...) leaves no entry.  Words of an entry:
+ *    [0] running number of the launch in the handle's life (1, 2, ...), counted apart from the wavefront kernel's
+ *    [1] sizeof(real): 8 / 4   [2] position slots S   [3] variable slots NS   [4] constraint slots MS
+ *    [5] leading dimension CAPP   [6] BNB  -- the template arguments of row_kernel
+ *    [7] wavefronts per workgroup (nwv; each carries four problems)   [8] workgroups per CU chosen
+ *    [9] workgroups (grid)     [10] spacing ps of a problem's factor in LDS (reals)
+ *   [11] dynamic LDS bytes per workgroup   [12] aux: 1 = the per-problem constants staged in LDS (ten-slot shapes)
+ *   [13] pass: 0 the only one, 1 the first of two   [14] working-set capacity of this launch
+ *   [15] problems per ticket (qchunk)   [16] 1 = problems handed out through the ticket counter, 0 = static split
+ *   [17] 1 = the launch walks a work list (behind a screening / tiers pass)
+ *   [18] problems of the batch (saturated at 2^31 - 1)
+ *   [19] bytes of search snapshots the handle holds after this launch (BNB; saturated at 2^31 - 1; 0 otherwise)
+ * For tests and benchmark reports. */
+#define LMPC_ROW_INFO_WORDS 20
+int lmpc_row_launch_info(const lmpc_handle *h, int32_t *out, int max);
+
 /* Device time per lmpc_solve_batch* call, measured with HIP events recorded on the launch
  * stream (switch on with lmpc_profile(h, 1); timing-only events, hipEventDisableSystemFence: a default event's
  * system-scope cache writeback added ~1.7 us to a 24 us call that rocprofv3's kernel trace does not see).  lmpc_profile_read waits for the recorded calls,

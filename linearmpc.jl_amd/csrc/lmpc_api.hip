@@ -1130,6 +1130,15 @@ int lmpc_wave_launch_info(const lmpc_handle *h, int32_t *out, int max) {
     return (int)k;
 }
 
+int lmpc_row_launch_info(const lmpc_handle *h, int32_t *out, int max) {
+    if (!h || !out || max < 0) return LMPC_ERR_BADARG;
+    long long k = h->rowRecN < 4 ? h->rowRecN : 4;
+    if (k > max) k = max;
+    for (long long q = 0; q < k; q++)                      // the k most recent entries of the ring, oldest first
+        std::memcpy(out + q * LMPC_ROW_INFO_WORDS, h->rowRec[(h->rowRecN - k + q) & 3], sizeof(int32_t) * LMPC_ROW_INFO_WORDS);
+    return (int)k;
+}
+
 const char *lmpc_kernel_name(const lmpc_handle *h) {
     if (!h) return "";
     if (h->avi) return h->kname.c_str();          // "avi" / "avi+prox"

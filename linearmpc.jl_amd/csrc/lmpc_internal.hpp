@@ -86,6 +86,9 @@ struct lmpc_handle {
     // launches, LMPC_WAVE_INFO_WORDS words each, and how many the handle has made in its life (host memory only)
     int32_t waveRec[4][LMPC_WAVE_INFO_WORDS] = {};
     long long waveRecN = 0;
+    // ... and launch_row_shape (lmpc_row_launch_info): the four most recent row-kernel launches, counted apart
+    int32_t rowRec[4][LMPC_ROW_INFO_WORDS] = {};
+    long long rowRecN = 0;
     int32_t *dRegTable = nullptr;  // hash table of lmpc_distinct_active_sets_device (lmpc_regions.hip): 16 control words + slots
     int regCap = 0;
     unsigned long long *dRegW1 = nullptr;   // one-word masks: key / count / first-index tables of regW1Cap slots each (clean

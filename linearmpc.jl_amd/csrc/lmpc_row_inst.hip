@@ -171,6 +171,14 @@ int launch_row_shape(lmpc_handle *h, const RowLaunch &rl, const R *dC, int64_t n
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * rl.nwv), rl.lds, st, prm);
     h->waveCtrSet ^= 1;
     HIP_TRY(h, hipGetLastError());
+    // what was enqueued, for lmpc_row_launch_info (include/lmpc_hip.h lists the words)
+    const auto sat = [](long long v) { return (int32_t)(v < 0x7fffffffll ? v : 0x7fffffffll); };
+    const int32_t rec[LMPC_ROW_INFO_WORDS] = {
+        (int32_t)((h->rowRecN + 1) & 0x7fffffff), (int32_t)sizeof(R), S, NS, MS, CAPP, BNB ? 1 : 0, rl.nwv, blocks, (int32_t)grid,
+        rl.ps, (int32_t)rl.lds, rl.aux, pass, cap, qchunk, queue != nullptr ? 1 : 0, wl.list != nullptr ? 1 : 0,
+        sat((long long)nprob), BNB ? sat((long long)h->rowBnbBytes) : 0};
+    for (int q = 0; q < LMPC_ROW_INFO_WORDS; q++) h->rowRec[h->rowRecN & 3][q] = rec[q];
+    h->rowRecN++;
     return LMPC_OK;
 }
 

@@ -205,6 +205,23 @@ class BatchedQP:
         recs = [dict(zip(self.WAVE_LAUNCH_FIELDS, (int(v) for v in out[q * W:(q + 1) * W]))) for q in range(k)]
         return [r for r in recs if r["seq"] > since]
 
+    ROW_LAUNCH_FIELDS = ("seq", "real_bytes", "S", "NS", "MS", "CAPP", "BNB", "nwv", "blocks", "grid", "ps", "lds", "aux",
+                         "pass", "cap", "qchunk", "queue", "worklist", "nprob", "snap_bytes")
+
+    def row_launch_info(self, since=0):
+        """The handle's most recent row-kernel launches (lmpc_row_launch_info; at most four are kept), oldest first:
+        one dict per launch with the template arguments of the row_kernel instantiation that ran (real_bytes, S, NS,
+        MS, CAPP, BNB) and its launch shape (nwv, blocks per CU, grid, ps, lds, aux, pass, cap, qchunk, queue,
+        worklist, nprob, snap_bytes).  "seq" numbers the row-kernel launches of the handle's life from 1; `since` as
+        in wave_launch_info.  A batch the row kernel did not take leaves no entry."""
+        W = len(self.ROW_LAUNCH_FIELDS)
+        out = (ctypes.c_int32 * (4 * W))()
+        k = lib().lmpc_row_launch_info(self._h, out, 4)
+        if k < 0:
+            check(k, self._h)
+        recs = [dict(zip(self.ROW_LAUNCH_FIELDS, (int(v) for v in out[q * W:(q + 1) * W]))) for q in range(k)]
+        return [r for r in recs if r["seq"] > since]
+
     def ldp(self):
         """The constant pack the kernels use (row-major) -- what tests hand to the oracle."""
         out = dict(M=np.empty((self.m, self.n)), du=np.empty(self.m), dl=np.empty(self.m),

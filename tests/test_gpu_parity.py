@@ -2701,13 +2701,26 @@ def test_tiers_pass_in_front_of_the_wavefront_kernel(lmpc):
 
 
 # ------------------------------------------------------------------ four problems per wavefront (lmpc_row_kernel.hpp)
-def _row_vs_wave_vs_oracle(lmpc, qp, theta, settings=None):
+def _row_launches(qp, since=None):
+    """Row-kernel launches in the handle's record (lmpc_row_launch_info): the last running number, or -- with `since` --
+    the launches made after it."""
+    if since is None:
+        r = qp.row_launch_info()
+        return r[-1]["seq"] if r else 0
+    return qp.row_launch_info(since)
+
+
+def _row_vs_wave_vs_oracle(lmpc, qp, theta, settings=None, row=True):
     """The row kernel (forced), the wavefront kernel (row kernel off) and the oracle on the same points: identical
-    x, exit flags, iteration counts and active sets."""
+    x, exit flags, iteration counts and active sets.  The handle's launch record must show a row-kernel launch with
+    "row_kernel" 1 (`row` = False: a handle the row kernel does not take -- none) and none with 0."""
     qp.set_option("row_kernel", 0)
+    seq = _row_launches(qp)
     ref = qp.solve(theta)
+    assert not _row_launches(qp, seq), "a row-kernel launch with \"row_kernel\" 0"
     qp.set_option("row_kernel", 1)
     got = _compare(qp, theta, settings=settings)
+    assert bool(_row_launches(qp, seq)) == row, ("row-kernel launches with \"row_kernel\" 1", _row_launches(qp, seq))
     for a, b in zip(ref, got):
         assert np.array_equal(a, b, equal_nan=True)
     return got
@@ -2739,6 +2752,9 @@ def test_row_kernel_random_problems(lmpc, n, mg, nth, nsoft, seed):
     rng = np.random.default_rng(seed)
     H, f, f_theta, A, bu, bl, W, sense = _random_qp(rng, n, mg, nth, nsoft)
     qp = lmpc.BatchedQP.from_mpqp(H, f, f_theta, A, bu, bl, W, sense, nout=min(n, 4))
+    # (n = 6, m = 26 is a lane-kernel handle by default, where "row_kernel" 1 asks for nothing: the launch record showed
+    # that this case had never reached the row kernel)
+    qp.set_option("wave", 1)
     theta = rng.uniform(-2, 2, (1500, nth)) * (0.4 if nth >= 12 else 1.0)
     x, ef, it, act = _row_vs_wave_vs_oracle(lmpc, qp, theta)
     assert (ef >= 1).any() and (ef != -7).all()
@@ -2831,7 +2847,7 @@ def test_row_kernel_immutable_one_sided_and_duplicated_rows(lmpc):
     bu2[n + 12] = bl2[n + 12] = 0.1; s2[n + 12] = 5
     q2 = lmpc.BatchedQP.from_mpqp(H, np.zeros(n), rng.standard_normal((n, nth)), A, bu2, bl2, W, s2, nout=3)
     assert q2.kernel_name == "wave"
-    _row_vs_wave_vs_oracle(lmpc, q2, theta[:500])
+    _row_vs_wave_vs_oracle(lmpc, q2, theta[:500], row=False)
 
 
 # ------------------------------------------------------------------ branch and bound on the row kernel (binary32)
@@ -2845,11 +2861,13 @@ def _bnb_row_vs_wave_vs_oracle(lmpc, qp, s, theta, nsample=200):
     out = {}
     for mode in (0, 1):
         qp.set_option("row_kernel", mode)
+        seq = _row_launches(qp)
         it_d = torch.empty(N, dtype=torch.int32, device="cuda")
         ac_d = torch.zeros((N, qp.words), dtype=torch.int64, device="cuda")
         x_d, ef_d = qp.solve_device(th_d, iters=it_d, active=ac_d)
         torch.cuda.synchronize()
         qp.check()
+        assert bool(_row_launches(qp, seq)) == bool(mode), (mode, _row_launches(qp, seq))
         out[mode] = (x_d.cpu().numpy(), ef_d.cpu().numpy(), it_d.cpu().numpy(), ac_d.cpu().numpy().view(np.uint64))
     for q in range(4):
         assert np.array_equal(out[0][q], out[1][q], equal_nan=(q == 0)), ("x", "exitflag", "iters", "active")[q]
@@ -2954,11 +2972,13 @@ def test_row_kernel_binary32_plain_solves(lmpc, name):
     out = {}
     for mode in (0, 1):
         qp.set_option("row_kernel", mode)
+        seq = _row_launches(qp)
         it_d = torch.empty(N, dtype=torch.int32, device="cuda")
         ac_d = torch.zeros((N, qp.words), dtype=torch.int64, device="cuda")
         x_d, ef_d = qp.solve_device(th_d, iters=it_d, active=ac_d)
         torch.cuda.synchronize()
         qp.check()
+        assert bool(_row_launches(qp, seq)) == bool(mode), (mode, _row_launches(qp, seq))
         out[mode] = (x_d.cpu().numpy(), ef_d.cpu().numpy(), it_d.cpu().numpy(), ac_d.cpu().numpy().view(np.uint64))
     for q in range(4):
         assert np.array_equal(out[0][q], out[1][q], equal_nan=(q == 0))
@@ -3021,11 +3041,13 @@ def test_row_kernel_branch_and_bound_f64(lmpc, name):
     out = {}
     for mode in (0, 1):
         qp.set_option("row_kernel", mode)
+        seq = _row_launches(qp)
         it_d = torch.empty(N, dtype=torch.int32, device="cuda")
         ac_d = torch.zeros((N, qp.words), dtype=torch.int64, device="cuda")
         x_d, ef_d = qp.solve_device(th_d, iters=it_d, active=ac_d)
         torch.cuda.synchronize()
         qp.check()
+        assert bool(_row_launches(qp, seq)) == bool(mode), (mode, _row_launches(qp, seq))
         out[mode] = (x_d.cpu().numpy(), ef_d.cpu().numpy(), it_d.cpu().numpy(), ac_d.cpu().numpy().view(np.uint64))
     for q in range(4):
         assert np.array_equal(out[0][q], out[1][q], equal_nan=(q == 0))

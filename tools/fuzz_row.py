@@ -72,7 +72,17 @@ def run_trial(rng, f32, N):
     keep = ~lim
     ok = (np.array_equal(ef[sel][keep], efo[keep]) and np.array_equal(it[sel][keep], ito[keep])
           and np.array_equal(ac[sel].view(np.uint64)[keep], acto[keep]) and np.array_equal(x[sel][keep], xo[keep], equal_nan=True))
-    return same, ok, H.shape[0], len(bu), qp.kernel_name, float((ef >= 1).mean()), float(it.mean()), int(lim.sum())
+    return same, ok, H.shape[0], len(bu), recorded_shape(qp), float((ef >= 1).mean()), float(it.mean()), int(lim.sum())
+
+
+def recorded_shape(qp):
+    """What the handle's last call launched on the row kernel (lmpc_row_launch_info), or that it launched nothing there."""
+    r = qp.row_launch_info()
+    if not r:
+        return "no row launch"
+    r = r[-1]
+    return (f"row<{'f64' if r['real_bytes'] == 8 else 'f32'}, {r['S']}, {r['NS']}, {r['MS']}, {r['CAPP']}{', bnb' if r['BNB'] else ''}> "
+            f"pass {r['pass']} cap {r['cap']} nwv {r['nwv']}")
 
 
 def main(trials=60, seed=1):

@@ -36,6 +36,19 @@ def random_hybrid(rng, big):
     return H, np.zeros(n), rng.standard_normal((n, nth)), A, bu, bl, W, sense
 
 
+LAST_SHAPE = ""
+
+
+def recorded_shape(qp):
+    """What the handle's last call launched on the row kernel (lmpc_row_launch_info), or that it launched nothing there."""
+    r = qp.row_launch_info()
+    if not r:
+        return "no row launch"
+    r = r[-1]
+    return (f"row<{'f64' if r['real_bytes'] == 8 else 'f32'}, {r['S']}, {r['NS']}, {r['MS']}, {r['CAPP']}, bnb> "
+            f"pass {r['pass']} cap {r['cap']} nwv {r['nwv']}")
+
+
 def run_trial(rng, big, N, s, so_cls, f64=False):
     H, f, fth, A, bu, bl, W, sense = random_hybrid(rng, big)
     qp = lmpc.BatchedQP.from_mpqp(H, f, fth, A, bu, bl, W, sense, **({} if f64 else {"settings": s}))
@@ -51,6 +64,8 @@ def run_trial(rng, big, N, s, so_cls, f64=False):
         qp.check()
         out[mode] = (x_d.cpu().numpy(), ef_d.cpu().numpy(), it_d.cpu().numpy(), ac_d.cpu().numpy())
     same = all(np.array_equal(out[0][q], out[1][q], equal_nan=(q == 0)) for q in range(4))
+    global LAST_SHAPE
+    LAST_SHAPE = recorded_shape(qp)                     # (what "row_kernel" 1 launched: lmpc_row_launch_info)
     from oracle import ldp as oldp
     sel = np.arange(0, N, max(1, N // 40))
     if f64:
@@ -77,7 +92,7 @@ def main(trials=40, seed=1):
         same, ok, n, m, nb, solved, its = run_trial(rng, big, 1500, s, oldp.Settings, f64)
         if not (same and ok):
             bad += 1
-        print(f"trial {t:3d} {'f64' if f64 else 'f32'} n={n:2d} m={m:2d} binaries={nb} solved {solved:.2f} iterations {its:7.1f}: "
+        print(f"trial {t:3d} {'f64' if f64 else 'f32'} n={n:2d} m={m:2d} binaries={nb} [{LAST_SHAPE}] solved {solved:.2f} iterations {its:7.1f}: "
               f"{'identical' if same else 'DIFFERENT from the wavefront kernel'}, {'oracle ok' if ok else 'ORACLE MISMATCH'}", flush=True)
     print("OK" if not bad else f"FAILED ({bad} trials)")
     return 1 if bad else 0
