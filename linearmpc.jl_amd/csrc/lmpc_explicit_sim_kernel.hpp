@@ -8,11 +8,9 @@
 //
 // Arithmetic: the correction, dynamics, cost and violation are the device functions of lmpc_sim_kernels.hpp /
 // lmpc_scenario_kernels.hpp (separate multiply and add), the controller is explicit_locate / explicit_affine of
-// lmpc_explicit_kernel.hpp (explicit fmas).  Two sums are written out here a second time, because the older kernels
-// have them inline and not as device functions: the measurement sum ym / y is a COPY of scenario_pre_kernel's, and the
-// running cost's add and final halving a COPY of scenario_post_kernel's.  The statements follow those two kernels one
-// for one; what keeps the copies in step is the tests' bit-for-bit comparison of this kernel with the lock-step form
-// (mode 0), which runs the originals.
+// lmpc_explicit_kernel.hpp (explicit fmas).  The measurement sum, the score of a step and the observer's predict are the
+// device functions the PRE / POST kernels are made of (scn_measure_row, scn_score_step, scn_observer_predict); theta is
+// formed entry by entry into registers, in scn_form_theta's order.
 //
 // State: x, xhat and uprev stay in the caller's arrays between two steps (the same lane reads back what it wrote; the
 // lines are its own), as the PRE / POST kernels keep them; theta lives in registers (double th[NT], static indices).
@@ -74,19 +72,11 @@ __global__ __launch_bounds__(256) void explicit_run_kernel(ExpRun A, ScnConst K,
             const long long row = (long long)k * A.N + i;
             const int ms = 1 + nx + A.nd;
             for (int jm = 0; jm < A.ny; jm++) {
-                const double *mr = K.c + K.meas + jm * ms;
-                double ym = mr[0], y = 0.0;
-                for_nx<NXT>(nx, [&](int c) {
-                    const double t = __dmul_rn(mr[1 + c], xo[c]);
-                    ym = __dadd_rn(ym, t); y = __dadd_rn(y, t);
-                });
-                for (int q = 0; q < A.nd; q++) {
-                    const double t = __dmul_rn(mr[1 + nx + q], dk(q));
-                    ym = __dadd_rn(ym, t); y = __dadd_rn(y, t);
-                }
+                const ScnMeas m = scn_measure_row<NXT>(K.c + K.meas + jm * ms, xo, nx, A.nd, dk);
+                double ym = m.ym;
                 if (A.noise.w > 0) ym = __dadd_rn(ym, block_at(A.noise, i, k, jm));
                 if (A.ym_traj) A.ym_traj[row * A.ny + jm] = ym;
-                if (A.y_traj) A.y_traj[row * A.ny + jm] = obs ? y : ym;
+                if (A.y_traj) A.y_traj[row * A.ny + jm] = obs ? m.y : ym;
                 if (obs) correct_row<NXT>(A.obs_meas + jm * ms, A.obs_kt + jm * nx, ym, xh, xn, nx, A.nd, dk);
             }
             for_nx<NXT>(nx, [&](int c) {
@@ -133,25 +123,8 @@ __global__ __launch_bounds__(256) void explicit_run_kernel(ExpRun A, ScnConst K,
         const int first = k == 0, last = k == A.T - 1;
         double xo[NXA], xn[NXA];
         for_nx<NXT>(nx, [&](int c) { xo[c] = A.x[i * nx + c]; });
-        if (A.cost) {
-            double ul[64];
-            if (K.cRr >= 0) for (int l = 0; l < nu; l++) ul[l] = first ? 0.0 : A.ulast[i * nu + l];
-            const double c = scn_step_cost(K, xo, nx, u, ul, nu, A.r, i, k);
-            const double run = __dadd_rn(first ? 0.0 : A.cost[i], c);
-            A.cost[i] = last ? __dmul_rn(0.5, run) : run;
-            if (K.cRr >= 0 && !last) for (int l = 0; l < nu; l++) A.ulast[i * nu + l] = u[l];
-        }
-        if (A.viol) {
-            const double w = scn_step_violation(K, xo, nx, u, nu);
-            const double old = first ? 0.0 : A.viol[i];
-            A.viol[i] = w > old ? w : old;
-        }
-        if (obs) {
-            double ho[NXA], hn[NXA];
-            for_nx<NXT>(nx, [&](int c) { ho[c] = A.xhat[i * nx + c]; });
-            dynamics_rows<NXT>(A.obs_dyn, ho, hn, nx, nu, A.nd, u, dk);
-            for_nx<NXT>(nx, [&](int c) { A.xhat[i * nx + c] = hn[c]; });
-        }
+        scn_score_step<false>(K, xo, nx, u, nu, A.cost, A.viol, A.ulast, A.r, i, k, first, last);
+        if (obs) scn_observer_predict<NXT>(A.obs_dyn, A.xhat + i * nx, nx, nu, A.nd, u, dk);
         dynamics_rows<NXT>(K.c + K.plant, xo, xn, nx, nu, A.nd, u, dk);
         for_nx<NXT>(nx, [&](int a) { A.x[i * nx + a] = xn[a]; });
         if (A.x_traj) for_nx<NXT>(nx, [&](int a) { A.x_traj[((long long)(k + 1) * A.N + i) * nx + a] = xn[a]; });

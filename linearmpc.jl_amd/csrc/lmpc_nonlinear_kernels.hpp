@@ -8,8 +8,8 @@
 // global memory where the program asks for them (an index into a private copy would be a runtime index: scratch).
 //
 // nonlinear_post_kernel is uncertain_post_kernel with dynamics_rows on the plant's rows replaced by the program: cost,
-// violation, the observer's predict, the draws and step_tail are the same device functions (scn_step_cost,
-// scn_step_violation, dynamics_rows on the OBSERVER's model, unc_value, step_tail), called in the same order.
+// violation, the observer's predict, the process noise and step_tail are the same device functions (scn_score_step,
+// scn_observer_predict on the OBSERVER's model, unc_process_noise, step_tail), called in the same order.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -71,58 +71,15 @@ __global__ __launch_bounds__(NL_LANES) void nonlinear_post_kernel(ScnPost A, Scn
     if constexpr (COST) {
         double xo[NXA];
         for_nx<NXT>(nx, [&](int c) { xo[c] = A.x[i * nx + c]; });
-        if (A.cost) {
-            double ul[64];
-            if (K.cRr >= 0) for (int l = 0; l < nu; l++) ul[l] = A.first ? 0.0 : A.ulast[i * nu + l];
-            double us[64];
-            for (int l = 0; l < nu; l++) us[l] = u[l];
-            const double c = scn_step_cost(K, xo, nx, us, ul, nu, A.r, i, A.k);
-            const double run = __dadd_rn(A.first ? 0.0 : A.cost[i], c);
-            A.cost[i] = A.last ? __dmul_rn(0.5, run) : run;
-            if (K.cRr >= 0 && !A.last) for (int l = 0; l < nu; l++) A.ulast[i * nu + l] = us[l];
-        }
-        if (A.viol) {
-            double us[64];
-            for (int l = 0; l < nu; l++) us[l] = u[l];
-            const double w = scn_step_violation(K, xo, nx, us, nu);
-            const double old = A.first ? 0.0 : A.viol[i];
-            A.viol[i] = w > old ? w : old;
-        }
+        scn_score_step<true>(K, xo, nx, u, nu, A.cost, A.viol, A.ulast, A.r, i, A.k, A.first, A.last);
     }
-    if (A.xhat) {                                      // the observer predicts with the handle's LINEAR model
-        double ho[NXA], hn[NXA];
-        for_nx<NXT>(nx, [&](int c) { ho[c] = A.xhat[i * nx + c]; });
-        dynamics_rows<NXT>(A.obs_dyn, ho, hn, nx, nu, A.nd, u, dk);
-        for_nx<NXT>(nx, [&](int c) { A.xhat[i * nx + c] = hn[c]; });
-    }
+    // the observer predicts with the handle's LINEAR model
+    if (A.xhat) scn_observer_predict<NXT>(A.obs_dyn, A.xhat + i * nx, nx, nu, A.nd, u, dk);
     NlEnv<decltype(dk)> E{nl_lds + threadIdx.x, A.x + i * nx, u, Q.q + i * Q.qstride, dk};
     plant_program_run(P, E);
     double xn[NXA];
     for_nx<NXT>(nx, [&](int a) { xn[a] = E.slot(Q.out_slot[a]); });
-    const int nw = U.process.w;
-    if (nw > 0) {
-        typename std::conditional<GAUSS, UncDrawsGauss, UncDraws>::type de(U, i, 0u);
-        if (U.gw < 0) {
-            for_nx<NXT>(nx, [&](int a) {
-                const double e = unc_value(U.process, K.c, de, i, A.k, a);
-                xn[a] = __dadd_rn(xn[a], e);
-                if (U.w_out) U.w_out[i * nx + a] = e;
-            });
-        } else {
-            const double *gw = K.c + U.gw;
-            double wv[NXA];
-            for_nx<NXT>(nx, [&](int a) { wv[a] = 0.0; });
-            for (int q = 0; q < nw; q++) {
-                const double e = unc_value(U.process, K.c, de, i, A.k, q);
-                for_nx<NXT>(nx, [&](int a) {
-                    const double t = __dmul_rn(gw[a * nw + q], e);
-                    xn[a] = __dadd_rn(xn[a], t);
-                    wv[a] = __dadd_rn(wv[a], t);
-                });
-            }
-            if (U.w_out) for_nx<NXT>(nx, [&](int a) { U.w_out[i * nx + a] = wv[a]; });
-        }
-    }
+    unc_process_noise<NXT, typename std::conditional<GAUSS, UncDrawsGauss, UncDraws>::type>(U, K.c, i, A.k, nx, xn);
     for_nx<NXT>(nx, [&](int a) { A.x[i * nx + a] = xn[a]; });
     if (A.xtraj_next) for_nx<NXT>(nx, [&](int a) { A.xtraj_next[i * nx + a] = xn[a]; });
     step_tail(i, u, nu, A.uprev + i * A.nup, (double *)nullptr, A.nup, A.utraj, A.flag, A.flag_min, A.first);

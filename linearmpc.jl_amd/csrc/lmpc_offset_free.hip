@@ -31,14 +31,62 @@ void dispatch_pair(int nx, int ndo, F &&f) {
 std::string offset_free_problem(lmpc_handle *h, int64_t N, int T, const lmpc_scenario_sim *s, const lmpc_offset_free *of,
                                 const double *x, const double *xaug, const double *uprev, bool device) {
     if (xaug && !h->obsC) return "xaug: given without an observer (lmpc_set_observer has not been called on this handle)";
-    lmpc_observer od{h->obsNx, h->obsNu, h->obsNd, h->obsNy, nullptr, nullptr, nullptr};
-    std::string msg = scenario_problem(h->P.nth, h->P.nout, h->obsC ? &od : nullptr, s, of, true);
-    if (!msg.empty()) return msg;
-    if (N < 0) return "N: negative";
-    if (T < 0) return "T: negative";
-    if (N > 0 && !x) return "x: NULL";
-    if (device && N > 0 && s->nuprev > 0 && !uprev) return "uprev: NULL with nuprev > 0";
-    return "";
+    const HandleObserver ob(h);
+    std::string msg = scenario_problem(h->P.nth, h->P.nout, ob.ptr, s, of, true);
+    if (msg.empty()) msg = call_size_problem(N, T, x);
+    if (msg.empty()) msg = call_array_problem(N, s, nullptr, uprev, device);
+    return msg;
+}
+
+// the run itself, on device arrays, once the call has passed its refusals
+int run(lmpc_handle *h, int64_t N, int T, const lmpc_scenario_sim *s, const lmpc_offset_free *of, double *x, double *xaug,
+        double *uprev, double *U_traj, double *X_traj, int32_t *flag_min, hipStream_t st) {
+    { const int rce = api_ensure_sim(h, N); if (rce != LMPC_OK) return rce; }
+    const int nx = s->nx, nu = s->nu, nd = s->nd, ny = s->ny, nup = s->nuprev, ndo = of->n_offset_free, na = nx + ndo;
+    std::vector<double> hostC;
+    ScnConst K = pack_constants(hostC, nx, nu, nd, ny, s->plant, s->measurement, s->cost);
+    { const int rcu = upload_constants(h, hostC, K, st); if (rcu != LMPC_OK) return rcu; }
+    const bool wantCost = scn_want_cost(s);
+    ScnScratch scr;
+    { const int rcs = scn_scratch(h, &h->scnScr, &h->scnScrCap, N, s, xaug ? 0 : (size_t)na, scr); if (rcs != LMPC_OK) return rcs; }
+    if (!xaug) {                                       // set_state!(observer, x0): [x0; 0], observer.jl:74-90
+        xaug = scr.state;
+        hipLaunchKernelGGL(offset_free_init_kernel, dim3((unsigned)(((size_t)N * na + 255) / 256)), dim3(256), 0, st, xaug, x, nx,
+                           na, (long long)N);
+        HIP_TRY(h, hipGetLastError());
+    }
+    if (X_traj) HIP_TRY(h, hipMemcpyAsync(X_traj, x, sizeof(double) * (size_t)N * nx, hipMemcpyDeviceToDevice, st));
+    // the offset-free records: the observer's arrays are na wide, the d block carries the estimate
+    const size_t obs_nd = (size_t)na * (1 + na + nu + nd);
+    const size_t obs_nm = (size_t)ny * (1 + na + nd);
+    OfPre A{};
+    A.x = x; A.xaug = xaug; A.uprev = uprev; A.theta = h->simTheta;
+    A.obs_meas = h->obsC + obs_nd; A.obs_kt = h->obsC + obs_nd + obs_nm;
+    A.r = to_block(&s->r); A.d = to_block(&s->d); A.p = to_block(&s->p); A.noise = to_block(&s->noise);
+    if (s->d.w == 0) A.d.src = nullptr;               // no measured trajectory: d_k = 0 (d.H still sets the columns)
+    A.nx = nx; A.ndo = ndo; A.ny = ny; A.nd = nd; A.nup = nup; A.n = (long long)N;
+    OfPost B{};
+    B.x = x; B.xaug = xaug; B.uprev = uprev; B.u = h->simU; B.flag = h->simFlag;
+    B.obs_dyn = h->obsC; B.d = A.d; B.r = A.r;
+    B.flag_min = flag_min; B.cost = wantCost ? s->cost_out : nullptr; B.viol = wantCost ? s->violation_out : nullptr;
+    B.ulast = scr.ulast; B.nx = nx; B.ndo = ndo; B.nu = nu; B.nd = nd; B.nup = nup; B.n = (long long)N;
+    const unsigned grid = (unsigned)((N + 255) / 256);
+    return scn_loop(h, s, N, T, U_traj, X_traj, A, B,
+        [&](int k) {
+            A.dhat_out = of->Dhat_traj ? of->Dhat_traj + (size_t)k * N * ndo : nullptr;
+            dispatch_pair(nx, ndo, [&](auto NX, auto ND) {
+                hipLaunchKernelGGL((offset_free_pre_kernel<decltype(NX)::value, decltype(ND)::value>), dim3(grid), dim3(256),
+                                   sizeof(double) * 256 * (size_t)na, st, A, K);
+            });
+        },
+        [&](int k) { return scn_solve(h, s, N, k, st); },
+        [&](int) {
+            dispatch_pair(nx, ndo, [&](auto NX, auto ND) {
+                constexpr int a = decltype(NX)::value, b = decltype(ND)::value;
+                if (wantCost) hipLaunchKernelGGL((offset_free_post_kernel<a, b, true>), dim3(grid), dim3(256), 0, st, B, K);
+                else hipLaunchKernelGGL((offset_free_post_kernel<a, b, false>), dim3(grid), dim3(256), 0, st, B, K);
+            });
+        });
 }
 
 }  // namespace
@@ -69,82 +117,16 @@ int lmpc_simulate_scenario_offset_free_device(lmpc_handle *h, int64_t N, int T, 
     if (N == 0 || T == 0) return LMPC_OK;
     LMPC_NEED_DEVICE(h);
     LMPC_ENTER_DEVICE(h);
-    hipStream_t st = (hipStream_t)stream;
-    { const int rce = api_ensure_sim(h, N); if (rce != LMPC_OK) return rce; }
-    const int nx = s->nx, nu = s->nu, nd = s->nd, ny = s->ny, nup = s->nuprev, ndo = of->n_offset_free, na = nx + ndo;
-    std::vector<double> hostC;
-    ScnConst K = pack_constants(hostC, nx, nu, nd, ny, s->plant, s->measurement, s->cost);
-    { const int rcu = upload_constants(h, hostC, K, st); if (rcu != LMPC_OK) return rcu; }
-    const bool wantCost = s->cost && (s->cost_out || s->violation_out);
-    const bool needUlast = wantCost && s->cost_out && s->cost->Rr;
-    // per-run scratch: the observer state when the caller keeps none, the previous control of the cost's du term
-    const size_t needScr = (size_t)N * ((!xaug ? (size_t)na : 0) + (needUlast ? (size_t)nu : 0));
-    if (needScr > h->scnScrCap) {
-        hipFree(h->scnScr); h->scnScr = nullptr; h->scnScrCap = 0;
-        HIP_TRY(h, hipMalloc(&h->scnScr, sizeof(double) * needScr));
-        h->scnScrCap = needScr;
-    }
-    double *scr = h->scnScr;
-    if (!xaug) {                                       // set_state!(observer, x0): [x0; 0], observer.jl:74-90
-        xaug = scr; scr += (size_t)N * na;
-        hipLaunchKernelGGL(offset_free_init_kernel, dim3((unsigned)(((size_t)N * na + 255) / 256)), dim3(256), 0, st, xaug, x, nx,
-                           na, (long long)N);
-        HIP_TRY(h, hipGetLastError());
-    }
-    double *ulast = needUlast ? scr : nullptr;
-    if (X_traj) HIP_TRY(h, hipMemcpyAsync(X_traj, x, sizeof(double) * (size_t)N * nx, hipMemcpyDeviceToDevice, st));
-    const size_t obs_nd = (size_t)na * (1 + na + nu + nd);
-    const size_t obs_nm = (size_t)ny * (1 + na + nd);
-    OfPre A{};
-    A.x = x; A.xaug = xaug; A.uprev = uprev; A.theta = h->simTheta;
-    A.obs_meas = h->obsC + obs_nd; A.obs_kt = h->obsC + obs_nd + obs_nm;
-    A.r = to_block(&s->r); A.d = to_block(&s->d); A.p = to_block(&s->p); A.noise = to_block(&s->noise);
-    if (s->d.w == 0) A.d.src = nullptr;               // no measured trajectory: d_k = 0 (d.H still sets the columns)
-    A.nx = nx; A.ndo = ndo; A.ny = ny; A.nd = nd; A.nup = nup; A.n = (long long)N;
-    OfPost B{};
-    B.x = x; B.xaug = xaug; B.uprev = uprev; B.u = h->simU; B.flag = h->simFlag;
-    B.obs_dyn = h->obsC; B.d = A.d; B.r = A.r;
-    B.flag_min = flag_min; B.cost = wantCost ? s->cost_out : nullptr; B.viol = wantCost ? s->violation_out : nullptr;
-    B.ulast = ulast; B.nx = nx; B.ndo = ndo; B.nu = nu; B.nd = nd; B.nup = nup; B.n = (long long)N;
-    const unsigned grid = (unsigned)((N + 255) / 256);
-    for (int k = 0; k < T; k++) {
-        A.k = k;
-        A.r.k0 = A.r.H > 0 ? k + 1 : k;
-        A.d.k0 = k; A.p.k0 = k;
-        A.ym_out = s->Ym_traj ? s->Ym_traj + (size_t)k * N * ny : nullptr;
-        A.y_out = s->Y_traj ? s->Y_traj + (size_t)k * N * ny : nullptr;
-        A.xhat_out = s->Xhat_traj ? s->Xhat_traj + (size_t)k * N * nx : nullptr;
-        A.d_out = s->D_traj ? s->D_traj + (size_t)k * N * nd : nullptr;
-        A.dhat_out = of->Dhat_traj ? of->Dhat_traj + (size_t)k * N * ndo : nullptr;
-        dispatch_pair(nx, ndo, [&](auto NX, auto ND) {
-            hipLaunchKernelGGL((offset_free_pre_kernel<decltype(NX)::value, decltype(ND)::value>), dim3(grid), dim3(256),
-                               sizeof(double) * 256 * (size_t)na, st, A, K);
-        });
-        HIP_TRY(h, hipGetLastError());
-        const uint64_t *wm = (s->warm && k > 0) ? h->simAct : nullptr;
-        const int rc = api_launch(h, N, h->simTheta, h->simU, h->simFlag, nullptr, s->warm ? h->simAct : nullptr, wm, st);
-        if (rc != LMPC_OK) return rc;
-        B.k = k; B.first = k == 0; B.last = k == T - 1;
-        B.xtraj_next = X_traj ? X_traj + (size_t)(k + 1) * N * nx : nullptr;
-        B.utraj = U_traj ? U_traj + (size_t)k * N * nu : nullptr;
-        dispatch_pair(nx, ndo, [&](auto NX, auto ND) {
-            constexpr int a = decltype(NX)::value, b = decltype(ND)::value;
-            if (wantCost) hipLaunchKernelGGL((offset_free_post_kernel<a, b, true>), dim3(grid), dim3(256), 0, st, B, K);
-            else hipLaunchKernelGGL((offset_free_post_kernel<a, b, false>), dim3(grid), dim3(256), 0, st, B, K);
-        });
-        HIP_TRY(h, hipGetLastError());
-    }
-    return LMPC_OK;
+    return run(h, N, T, s, of, x, xaug, uprev, U_traj, X_traj, flag_min, (hipStream_t)stream);
 }
 
 int lmpc_simulate_scenario_offset_free(lmpc_handle *h, int64_t N, int T, const lmpc_scenario_sim *s,
                                        const lmpc_offset_free *of, double *x, double *xaug, double *uprev, double *U_traj,
                                        double *X_traj, int32_t *flag_min) {
     if (!h) return LMPC_ERR_BADARG;
-    {   // the refusals first, on the caller's descriptor: nothing is allocated for a call that cannot run
-        const std::string msg = offset_free_problem(h, N, T, s, of, x, xaug, uprev, false);
-        if (!msg.empty()) return fail(h, LMPC_ERR_BADARG, "lmpc_simulate_scenario_offset_free: " + msg);
-    }
+    // the refusals first, on the caller's descriptor: nothing is allocated for a call that cannot run
+    const std::string msg = offset_free_problem(h, N, T, s, of, x, xaug, uprev, false);
+    if (!msg.empty()) return fail(h, LMPC_ERR_BADARG, "lmpc_simulate_scenario_offset_free: " + msg);
     if (N == 0 || T == 0) return LMPC_OK;
     LMPC_NEED_DEVICE(h);
     LMPC_ENTER_DEVICE(h);
@@ -154,7 +136,7 @@ int lmpc_simulate_scenario_offset_free(lmpc_handle *h, int64_t N, int T, const l
     double *dxaug = (double *)sg.out(xaug, sizeof(double) * n * ((size_t)s->nx + ndo), true);
     lmpc_offset_free dof{of->n_offset_free, (double *)sg.out(of->Dhat_traj, sizeof(double) * T * n * ndo)};
     if (sg.err != hipSuccess) return sg.fail(h);
-    const int rc = lmpc_simulate_scenario_offset_free_device(h, N, T, &g.d, &dof, g.x, dxaug, g.uprev, g.U, g.X, g.flag_min, nullptr);
+    const int rc = run(h, N, T, &g.d, &dof, g.x, dxaug, g.uprev, g.U, g.X, g.flag_min, nullptr);
     if (rc == LMPC_OK && (!sg.ok(hipDeviceSynchronize(), "hipDeviceSynchronize") || !sg.download_all())) return sg.fail(h);
     return rc;
 }

@@ -5,9 +5,10 @@
 //
 // Two widths live side by side: the TRUE plant and the measurement act on nx states, the observer on na = nx + ndo.
 // Template arguments (NX, NDO): both counts at compile time when nx + ndo <= 8 (every index into a scenario's record is
-// static, for_nx's property), (0, 0) = run-time counts, na <= 32.  The sums are the ones of the scenario loop: correct_row
-// and dynamics_rows at width na on the observer's arrays, dynamics_rows at width nx on the plant's, scn_step_cost /
-// scn_step_violation on the true (x, u), step_tail last -- called, not restated, so that the loop equals
+// static, for_nx's property), (0, 0) = run-time counts, na <= 32.  The sums are the ones of the scenario loop:
+// scn_measure_row on the true state, correct_row and scn_observer_predict at width na on the observer's arrays,
+// dynamics_rows at width nx on the plant's, scn_score_step on the true (x, u), scn_form_theta with the estimate in the
+// d block, step_tail last -- called, not restated, so that the loop equals
 // lmpc_correct_state_device / lmpc_predict_state_device on the same handle bit for bit.
 #pragma once
 
@@ -62,19 +63,11 @@ __global__ __launch_bounds__(256) void offset_free_pre_kernel(OfPre A, ScnConst 
         for_nx<NA>(na, [&](int c) { xh[c] = A.xaug[i * na + c]; xn[c] = xh[c]; });
         const int ms = 1 + nx + A.nd, os = 1 + na + A.nd;
         for (int j = 0; j < A.ny; j++) {
-            const double *mr = K.c + K.meas + j * ms;
-            double ym = mr[0], y = 0.0;
-            for_nx<NX>(nx, [&](int c) {
-                const double t = __dmul_rn(mr[1 + c], xo[c]);
-                ym = __dadd_rn(ym, t); y = __dadd_rn(y, t);
-            });
-            for (int q = 0; q < A.nd; q++) {
-                const double t = __dmul_rn(mr[1 + nx + q], dk(q));
-                ym = __dadd_rn(ym, t); y = __dadd_rn(y, t);
-            }
+            const ScnMeas m = scn_measure_row<NX>(K.c + K.meas + j * ms, xo, nx, A.nd, dk);
+            double ym = m.ym;
             if (A.noise.w > 0) ym = __dadd_rn(ym, block_at(A.noise, i, A.k, j));
             if (A.ym_out) A.ym_out[i * A.ny + j] = ym;
-            if (A.y_out) A.y_out[i * A.ny + j] = y;
+            if (A.y_out) A.y_out[i * A.ny + j] = m.y;
             correct_row<NA>(A.obs_meas + j * os, A.obs_kt + j * na, ym, xh, xn, na, A.nd, dk);
         }
         for_nx<NA>(na, [&](int c) {
@@ -86,26 +79,12 @@ __global__ __launch_bounds__(256) void offset_free_pre_kernel(OfPre A, ScnConst 
         if (A.d_out) for (int q = 0; q < A.nd; q++) A.d_out[i * A.nd + q] = dk(q);
     }
     __syncthreads();
+    // the d block: max(d.H, 1) columns [d column k + c (held at the last); dhat]
     const int dcol = A.nd + ndo;
-    const int nr = A.r.width(), ndw = dcol * (A.d.H > 0 ? A.d.H : 1), npw = A.p.width();
-    const int nth = nx + nr + ndw + A.nup + npw;
-    const long long left = A.n - base;
-    const int rows = left < 256 ? (int)left : 256;
-    for (int idx = threadIdx.x; idx < rows * nth; idx += 256) {
-        const int sl = idx / nth;
-        int e = idx - sl * nth;
-        const long long s = base + sl;
-        double v;
-        if (e < nx) v = of_lds[sl * na + e];
-        else if ((e -= nx) < nr) v = block_entry(A.r, s, e);
-        else if ((e -= nr) < ndw) {
-            const int col = e / dcol, q = e - col * dcol;
-            v = q < A.nd ? block_at(A.d, s, A.d.k0 + col, q) : of_lds[sl * na + nx + (q - A.nd)];
-        }
-        else if ((e -= ndw) < A.nup) v = A.uprev[s * A.nup + e];
-        else v = block_entry(A.p, s, e - A.nup);
-        A.theta[base * nth + idx] = v;
-    }
+    scn_form_theta(A.theta, of_lds, na, nx, A.r, dcol * (A.d.H > 0 ? A.d.H : 1), [&](long long s, int sl, int e) {
+        const int col = e / dcol, q = e - col * dcol;
+        return q < A.nd ? block_at(A.d, s, A.d.k0 + col, q) : of_lds[sl * na + nx + (q - A.nd)];
+    }, A.uprev, A.nup, A.p, base, A.n);
 }
 
 struct OfPost {
@@ -131,7 +110,7 @@ __global__ __launch_bounds__(256) void offset_free_post_kernel(OfPost A, ScnCons
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= A.n) return;
     constexpr int NA = NX > 0 ? NX + NDO : 0;
-    constexpr int NXA = NX > 0 ? NX : 32, NAA = NA > 0 ? NA : 32;
+    constexpr int NXA = NX > 0 ? NX : 32;
     const int nx = NX > 0 ? NX : A.nx;
     const int na = nx + (NX > 0 ? NDO : A.ndo);
     const int nu = A.nu;
@@ -139,31 +118,8 @@ __global__ __launch_bounds__(256) void offset_free_post_kernel(OfPost A, ScnCons
     auto dk = [&](int q) { return block_at(A.d, i, A.k, q); };
     double xo[NXA], xn[NXA];
     for_nx<NX>(nx, [&](int c) { xo[c] = A.x[i * nx + c]; });
-    if constexpr (COST) {
-        if (A.cost) {
-            double ul[64];
-            if (K.cRr >= 0) for (int l = 0; l < nu; l++) ul[l] = A.first ? 0.0 : A.ulast[i * nu + l];
-            double us[64];
-            for (int l = 0; l < nu; l++) us[l] = u[l];
-            const double c = scn_step_cost(K, xo, nx, us, ul, nu, A.r, i, A.k);
-            const double run = __dadd_rn(A.first ? 0.0 : A.cost[i], c);
-            A.cost[i] = A.last ? __dmul_rn(0.5, run) : run;
-            if (K.cRr >= 0 && !A.last) for (int l = 0; l < nu; l++) A.ulast[i * nu + l] = us[l];
-        }
-        if (A.viol) {
-            double us[64];
-            for (int l = 0; l < nu; l++) us[l] = u[l];
-            const double w = scn_step_violation(K, xo, nx, us, nu);
-            const double old = A.first ? 0.0 : A.viol[i];
-            A.viol[i] = w > old ? w : old;
-        }
-    }
-    {
-        double ho[NAA], hn[NAA];
-        for_nx<NA>(na, [&](int c) { ho[c] = A.xaug[i * na + c]; });
-        dynamics_rows<NA>(A.obs_dyn, ho, hn, na, nu, A.nd, u, dk);
-        for_nx<NA>(na, [&](int c) { A.xaug[i * na + c] = hn[c]; });
-    }
+    if constexpr (COST) scn_score_step<true>(K, xo, nx, u, nu, A.cost, A.viol, A.ulast, A.r, i, A.k, A.first, A.last);
+    scn_observer_predict<NA>(A.obs_dyn, A.xaug + i * na, na, nu, A.nd, u, dk);
     dynamics_rows<NX>(K.c + K.plant, xo, xn, nx, nu, A.nd, u, dk);
     for_nx<NX>(nx, [&](int a) { A.x[i * nx + a] = xn[a]; });
     if (A.xtraj_next) for_nx<NX>(nx, [&](int a) { A.xtraj_next[i * nx + a] = xn[a]; });

@@ -1,6 +1,7 @@
-// Host side of the scenario loops, shared by lmpc_scenario.hip and lmpc_explicit_sim.hip: the refusals that need no
-// device, the run's constants packed into one buffer and uploaded into the handle's scratch, and the staging of a
-// host-pointer call's descriptor and arrays.
+// Host side of the scenario loops, shared by lmpc_scenario.hip, lmpc_uncertain.hip, lmpc_nonlinear.hip,
+// lmpc_offset_free.hip and lmpc_explicit_sim.hip: the refusals that need no device, the run's constants packed into one
+// buffer and uploaded into the handle's scratch, the staging of a host-pointer call's descriptor and arrays, and the
+// lock-step loop itself (scn_loop: per step the PRE launch, the solve, the POST launch) with what it is set up from.
 #pragma once
 
 #include <string>
@@ -78,6 +79,31 @@ inline std::string scenario_problem(int nth, int nout, const lmpc_observer *obs,
     return "";
 }
 
+// the handle's observer as scenario_problem takes it (nullptr: lmpc_set_observer has not been called)
+struct HandleObserver {
+    lmpc_observer od;
+    const lmpc_observer *ptr;
+    explicit HandleObserver(const lmpc_handle *h)
+        : od{h->obsNx, h->obsNu, h->obsNd, h->obsNy, nullptr, nullptr, nullptr}, ptr(h->obsC ? &od : nullptr) {}
+    HandleObserver(const HandleObserver &) = delete;   // ptr points into the object
+};
+
+// What every loop's entry point refuses of its call arguments once the descriptors have passed, in two parts (the
+// nonlinear loop's `q` stands between them): the sizes and the state ...
+inline std::string call_size_problem(int64_t N, int T, const double *x, const lmpc_uncertainty *un = nullptr) {
+    if (N < 0) return "N: negative";
+    if (T < 0) return "T: negative";
+    if (un && (int64_t)un->step_offset + T > 2147483647LL) return "step_offset: step_offset + T exceeds 2^31 - 1";
+    if (N > 0 && !x) return "x: NULL";
+    return "";
+}
+// ... and the arrays the descriptor decides about (`device`: a host-pointer twin takes a NULL uprev as zeros)
+inline std::string call_array_problem(int64_t N, const lmpc_scenario_sim *s, const double *xhat, const double *uprev, bool device) {
+    if (device && N > 0 && s->nuprev > 0 && !uprev) return "uprev: NULL with nuprev > 0";
+    if (xhat && !s->use_observer) return "xhat: given without use_observer";
+    return "";
+}
+
 // the run's constants in one host vector + their offsets; cost may be nullptr
 inline ScnConst pack_constants(std::vector<double> &v, int nx, int nu, int nd, int ny, const double *plant, const double *meas,
                         const lmpc_sim_cost *c) {
@@ -110,6 +136,101 @@ inline int upload_constants(lmpc_handle *h, const std::vector<double> &v, ScnCon
     HIP_TRY(h, hipMemcpyAsync(h->scnC, v.data(), sizeof(double) * v.size(), hipMemcpyHostToDevice, st));
     K.c = h->scnC;
     return LMPC_OK;
+}
+
+// ---- the lock-step loop
+
+inline bool scn_want_cost(const lmpc_scenario_sim *s) { return s->cost && (s->cost_out || s->violation_out); }
+
+// The per-run scratch [observer state | ulast] in *buf (*cap doubles, grown to fit): stateW doubles per scenario of
+// observer state when the caller keeps none (else 0), the previous control of the cost's du term when the run needs it.
+struct ScnScratch { double *state, *ulast; };
+inline int scn_scratch(lmpc_handle *h, double **buf, size_t *cap, int64_t N, const lmpc_scenario_sim *s, size_t stateW, ScnScratch &out) {
+    const size_t ulastW = scn_want_cost(s) && s->cost_out && s->cost->Rr ? (size_t)s->nu : 0;
+    const size_t needScr = (size_t)N * (stateW + ulastW);
+    if (needScr > *cap) {
+        (void)hipFree(*buf); *buf = nullptr; *cap = 0;
+        HIP_TRY(h, hipMalloc(buf, sizeof(double) * needScr));
+        *cap = needScr;
+    }
+    out.state = stateW ? *buf : nullptr;
+    out.ulast = ulastW ? *buf + (size_t)N * stateW : nullptr;
+    return LMPC_OK;
+}
+
+// the records of the PRE / POST kernels, all but what changes from step to step (scn_advance); theta, u, flag: the
+// solve's batch
+inline void scn_fill(const lmpc_handle *h, const lmpc_scenario_sim *s, int64_t N, double *x, double *xhat, double *uprev,
+                     int32_t *flag_min, double *theta, const double *u, const int32_t *flag, double *ulast, ScnPre &A, ScnPost &B) {
+    const bool obs = s->use_observer != 0, wantCost = scn_want_cost(s);
+    const size_t obs_nd = (size_t)h->obsNx * (1 + h->obsNx + h->obsNu + h->obsNd);
+    const size_t obs_nm = (size_t)h->obsNy * (1 + h->obsNx + h->obsNd);
+    A = ScnPre{};
+    A.x = x; A.xhat = obs ? xhat : nullptr; A.uprev = uprev; A.theta = theta;
+    A.obs_meas = obs ? h->obsC + obs_nd : nullptr; A.obs_kt = obs ? h->obsC + obs_nd + obs_nm : nullptr;
+    A.r = to_block(&s->r); A.d = to_block(&s->d); A.p = to_block(&s->p); A.noise = to_block(&s->noise);
+    A.nx = s->nx; A.ny = s->ny; A.nd = s->nd; A.nup = s->nuprev; A.n = (long long)N;
+    B = ScnPost{};
+    B.x = x; B.xhat = A.xhat; B.uprev = uprev; B.u = u; B.flag = flag;
+    B.obs_dyn = obs ? h->obsC : nullptr; B.d = A.d; B.r = A.r;
+    B.flag_min = flag_min; B.cost = wantCost ? s->cost_out : nullptr; B.viol = wantCost ? s->violation_out : nullptr;
+    B.ulast = ulast; B.nx = s->nx; B.nu = s->nu; B.nd = s->nd; B.nup = s->nuprev; B.n = (long long)N;
+}
+
+// The start of a run whose observer is nx wide: the scratch in *buf, xhat <- x when the caller keeps no observer state
+// (set_state!(mpc, x0), simulation.jl:92; the state then lives in the scratch), X_traj's first slice <- x, the records.
+inline int scn_begin(lmpc_handle *h, double **buf, size_t *cap, int64_t N, const lmpc_scenario_sim *s, double *x, double *xhat,
+                     double *uprev, double *X_traj, int32_t *flag_min, double *theta, const double *u, const int32_t *flag,
+                     hipStream_t st, ScnPre &A, ScnPost &B) {
+    const size_t bytes = sizeof(double) * (size_t)N * s->nx;
+    ScnScratch scr;
+    { const int rc = scn_scratch(h, buf, cap, N, s, s->use_observer && !xhat ? (size_t)s->nx : 0, scr); if (rc != LMPC_OK) return rc; }
+    if (scr.state) {
+        xhat = scr.state;
+        HIP_TRY(h, hipMemcpyAsync(xhat, x, bytes, hipMemcpyDeviceToDevice, st));
+    }
+    if (X_traj) HIP_TRY(h, hipMemcpyAsync(X_traj, x, bytes, hipMemcpyDeviceToDevice, st));
+    scn_fill(h, s, N, x, xhat, uprev, flag_min, theta, u, flag, scr.ulast, A, B);
+    return LMPC_OK;
+}
+
+// step k's fields of the two records (ScnPre / ScnPost or the offset-free loop's)
+template <class Pre, class Post>
+void scn_advance(Pre &A, Post &B, const lmpc_scenario_sim *s, int64_t N, int T, int k, double *U_traj, double *X_traj) {
+    const size_t row = (size_t)k * N;
+    A.k = k;
+    A.r.k0 = A.r.H > 0 ? k + 1 : k;                   // simulation.jl:102 get_preview(rs, k, Np) / rs[:, k]
+    A.d.k0 = k; A.p.k0 = k;                           // :103-104 get_preview(ds, k - 1, Np) / ds[:, k]
+    A.ym_out = s->Ym_traj ? s->Ym_traj + row * s->ny : nullptr;
+    A.y_out = s->Y_traj ? s->Y_traj + row * s->ny : nullptr;
+    A.xhat_out = s->Xhat_traj ? s->Xhat_traj + row * s->nx : nullptr;
+    A.d_out = s->D_traj ? s->D_traj + row * s->nd : nullptr;
+    B.k = k; B.first = k == 0; B.last = k == T - 1;
+    B.xtraj_next = X_traj ? X_traj + (row + N) * s->nx : nullptr;
+    B.utraj = U_traj ? U_traj + row * s->nu : nullptr;
+}
+
+// The loop: per step the records advanced, pre(k) (the PRE launch), solve(k) (LMPC_OK or the code to hand back, its
+// text already set), post(k) (the POST launch).  Nothing but enqueues unless solve waits.
+template <class Pre, class Post, class FPre, class FSolve, class FPost>
+int scn_loop(lmpc_handle *h, const lmpc_scenario_sim *s, int64_t N, int T, double *U_traj, double *X_traj, Pre &A, Post &B,
+             FPre &&pre, FSolve &&solve, FPost &&post) {
+    for (int k = 0; k < T; k++) {
+        scn_advance(A, B, s, N, T, k, U_traj, X_traj);
+        pre(k);
+        HIP_TRY(h, hipGetLastError());
+        { const int rc = solve(k); if (rc != LMPC_OK) return rc; }
+        post(k);
+        HIP_TRY(h, hipGetLastError());
+    }
+    return LMPC_OK;
+}
+
+// the handle's solve of step k on its closed-loop batch (simTheta -> simU, simFlag); warm start = the previous step's
+// final working set, the first step cold (as lmpc_simulate_ref_device)
+inline int scn_solve(lmpc_handle *h, const lmpc_scenario_sim *s, int64_t N, int k, hipStream_t st) {
+    const uint64_t *wm = (s->warm && k > 0) ? h->simAct : nullptr;
+    return api_launch(h, N, h->simTheta, h->simU, h->simFlag, nullptr, s->warm ? h->simAct : nullptr, wm, st);
 }
 
 // the host-pointer twins: the descriptor's trajectories and outputs and the caller's arrays staged on the device

@@ -89,14 +89,56 @@ struct ScnPre {
     long long n;
 };
 
-// PRE kernel of step k.  Phase 1, one lane per scenario: ym_j = h_j + sum_i C_ji x_i + sum_q Dd_jq d_q (+ v_j),
-// y_j = sum_i C_ji x_i + sum_q Dd_jq d_q with an observer (else y = ym), xhat <- correct(xhat, ym, d_k) by correct_row,
-// measurement by measurement (else xhat = x), the estimate into LDS.  Phase 2, the workgroup together: its 256 records
-// theta = [xhat; r-block; d-block; uprev; p-block] entry by entry, consecutive lanes on consecutive addresses
-// (form_parameter_kernel's property; a record can be 60+ doubles wide).  Dynamic LDS: 256 * nx doubles.
-template <int NXT>
-__global__ __launch_bounds__(256) void scenario_pre_kernel(ScnPre A, ScnConst K) {
-    extern __shared__ double scn_lds[];
+// One measurement row of the TRUE plant: ym = h_j + sum_c C_jc x_c + sum_q Dd_jq d_q (what a sensor reads, before any
+// noise) and y = the same sum without the offset; `mr` = K.c + K.meas + j * (1 + nx + nd).  The callers add the noise
+// terms onto ym: the descriptor's noise block first, then the uncertainty's measurement source.
+struct ScnMeas { double ym, y; };
+template <int NXT, class D>
+__device__ __forceinline__ ScnMeas scn_measure_row(const double *mr, const double *xo, int nx, int nd, D &&dk) {
+    double ym = mr[0], y = 0.0;
+    for_nx<NXT>(nx, [&](int c) {
+        const double t = __dmul_rn(mr[1 + c], xo[c]);
+        ym = __dadd_rn(ym, t); y = __dadd_rn(y, t);
+    });
+    for (int q = 0; q < nd; q++) {
+        const double t = __dmul_rn(mr[1 + nx + q], dk(q));
+        ym = __dadd_rn(ym, t); y = __dadd_rn(y, t);
+    }
+    return {ym, y};
+}
+
+// Phase 2 of a PRE kernel, the workgroup together: its 256 records theta = [xhat; r-block; d-block; uprev; p-block]
+// entry by entry, consecutive lanes on consecutive addresses (form_parameter_kernel's property; a record can be 60+
+// doubles wide).  xhat: the first nx entries of the lane's row (ldw doubles) in LDS; dblock(s, sl, e): entry e of the
+// d block, ndw wide, for scenario s = lane sl.
+template <class DB>
+__device__ __forceinline__ void scn_form_theta(double *theta, const double *lds, int ldw, int nx, const ThetaBlock &r, int ndw,
+                                               DB &&dblock, const double *uprev, int nup, const ThetaBlock &p, long long base,
+                                               long long n) {
+    const int nr = r.width(), npw = p.width();
+    const int nth = nx + nr + ndw + nup + npw;
+    const long long left = n - base;
+    const int rows = left < 256 ? (int)left : 256;
+    for (int idx = threadIdx.x; idx < rows * nth; idx += 256) {
+        const int sl = idx / nth;
+        int e = idx - sl * nth;
+        const long long s = base + sl;
+        double v;
+        if (e < nx) v = lds[sl * ldw + e];
+        else if ((e -= nx) < nr) v = block_entry(r, s, e);
+        else if ((e -= nr) < ndw) v = dblock(s, sl, e);
+        else if ((e -= ndw) < nup) v = uprev[s * nup + e];
+        else v = block_entry(p, s, e - nup);
+        theta[base * nth + idx] = v;
+    }
+}
+
+// Both phases of the PRE kernel of step k.  Phase 1, one lane per scenario: ym_j / y_j by scn_measure_row (+ v_j from the
+// descriptor's noise block, then ym_j = noise(j, ym_j): what the uncertain loop adds, nothing in the plain one), y = ym
+// without an observer, xhat <- correct(xhat, ym, d_k) by correct_row, measurement by measurement (else xhat = x), the
+// estimate into LDS.  Phase 2: scn_form_theta.  lds: 256 * nx doubles.
+template <int NXT, class V>
+__device__ __forceinline__ void scn_pre_step(const ScnPre &A, const ScnConst &K, double *lds, V &&noise) {
     constexpr int NXA = NXT > 0 ? NXT : 32;
     const int nx = NXT > 0 ? NXT : A.nx;
     const long long base = (long long)blockIdx.x * 256;
@@ -110,19 +152,12 @@ __global__ __launch_bounds__(256) void scenario_pre_kernel(ScnPre A, ScnConst K)
         else for_nx<NXT>(nx, [&](int c) { xn[c] = xo[c]; });
         const int ms = 1 + nx + A.nd;
         for (int j = 0; j < A.ny; j++) {
-            const double *mr = K.c + K.meas + j * ms;
-            double ym = mr[0], y = 0.0;
-            for_nx<NXT>(nx, [&](int c) {
-                const double t = __dmul_rn(mr[1 + c], xo[c]);
-                ym = __dadd_rn(ym, t); y = __dadd_rn(y, t);
-            });
-            for (int q = 0; q < A.nd; q++) {
-                const double t = __dmul_rn(mr[1 + nx + q], dk(q));
-                ym = __dadd_rn(ym, t); y = __dadd_rn(y, t);
-            }
+            const ScnMeas m = scn_measure_row<NXT>(K.c + K.meas + j * ms, xo, nx, A.nd, dk);
+            double ym = m.ym;
             if (A.noise.w > 0) ym = __dadd_rn(ym, block_at(A.noise, i, A.k, j));
+            ym = noise(j, ym);
             if (A.ym_out) A.ym_out[i * A.ny + j] = ym;
-            if (A.y_out) A.y_out[i * A.ny + j] = obs ? y : ym;
+            if (A.y_out) A.y_out[i * A.ny + j] = obs ? m.y : ym;
             // the innovation against the OBSERVER's model, then the gain
             if (obs) correct_row<NXT>(A.obs_meas + j * ms, A.obs_kt + j * nx, ym, xh, xn, nx, A.nd, dk);
         }
@@ -130,26 +165,19 @@ __global__ __launch_bounds__(256) void scenario_pre_kernel(ScnPre A, ScnConst K)
             if (obs) A.xhat[i * nx + c] = xn[c];
             if (A.xhat_out) A.xhat_out[i * nx + c] = xn[c];
         });
-        for_nx<NXT>(nx, [&](int c) { scn_lds[threadIdx.x * nx + c] = xn[c]; });
+        for_nx<NXT>(nx, [&](int c) { lds[threadIdx.x * nx + c] = xn[c]; });
         if (A.d_out) for (int q = 0; q < A.nd; q++) A.d_out[i * A.nd + q] = dk(q);
     }
     __syncthreads();
-    const int nr = A.r.width(), ndw = A.d.width(), npw = A.p.width();
-    const int nth = nx + nr + ndw + A.nup + npw;
-    const long long left = A.n - base;
-    const int rows = left < 256 ? (int)left : 256;
-    for (int idx = threadIdx.x; idx < rows * nth; idx += 256) {
-        const int sl = idx / nth;
-        int e = idx - sl * nth;
-        const long long s = base + sl;
-        double v;
-        if (e < nx) v = scn_lds[sl * nx + e];
-        else if ((e -= nx) < nr) v = block_entry(A.r, s, e);
-        else if ((e -= nr) < ndw) v = block_entry(A.d, s, e);
-        else if ((e -= ndw) < A.nup) v = A.uprev[s * A.nup + e];
-        else v = block_entry(A.p, s, e - A.nup);
-        A.theta[base * nth + idx] = v;
-    }
+    scn_form_theta(A.theta, lds, nx, nx, A.r, A.d.width(), [&](long long s, int, int e) { return block_entry(A.d, s, e); },
+                   A.uprev, A.nup, A.p, base, A.n);
+}
+
+// PRE kernel of step k (scn_pre_step without further noise).  Dynamic LDS: 256 * nx doubles.
+template <int NXT>
+__global__ __launch_bounds__(256) void scenario_pre_kernel(ScnPre A, ScnConst K) {
+    extern __shared__ double scn_lds[];
+    scn_pre_step<NXT>(A, K, scn_lds, [](int, double ym) { return ym; });
 }
 
 struct ScnPost {
@@ -167,9 +195,48 @@ struct ScnPost {
     long long n;
 };
 
-// POST kernel of step k, one lane per scenario: running cost / violation on (x_k, u_k) BEFORE the move,
-// xhat <- predict(xhat, u, d_k) by dynamics_rows on the observer's model, x <- f_offset + F x + G u + Gd d_k by
-// dynamics_rows on the true plant's array, then step_tail: uprev <- u, trajectories, smallest exit flag.
+// The score of step k for scenario i, on (x_k, u_k) BEFORE the move: the running cost (scn_step_cost added to cost[i],
+// halved with the last step; ulast: the scenario's previous control for the du term, kept here) and the running worst
+// constraint violation.  u: the scenario's nu controls.  COPYU: the POST kernels read u from global memory and score a
+// private copy; explicit_run_kernel's u is private already.
+template <bool COPYU>
+__device__ __forceinline__ void scn_score_step(const ScnConst &K, const double *xo, int nx, const double *u, int nu, double *cost,
+                                               double *viol, double *ulast, const ThetaBlock &r, long long i, int k, int first,
+                                               int last) {
+    if (cost) {
+        double ul[64];
+        if (K.cRr >= 0) for (int l = 0; l < nu; l++) ul[l] = first ? 0.0 : ulast[i * nu + l];
+        double us[COPYU ? 64 : 1];
+        const double *uu = u;
+        if constexpr (COPYU) { for (int l = 0; l < nu; l++) us[l] = u[l]; uu = us; }
+        const double c = scn_step_cost(K, xo, nx, uu, ul, nu, r, i, k);
+        const double run = __dadd_rn(first ? 0.0 : cost[i], c);
+        cost[i] = last ? __dmul_rn(0.5, run) : run;
+        if (K.cRr >= 0 && !last) for (int l = 0; l < nu; l++) ulast[i * nu + l] = uu[l];
+    }
+    if (viol) {
+        double us[COPYU ? 64 : 1];
+        const double *uu = u;
+        if constexpr (COPYU) { for (int l = 0; l < nu; l++) us[l] = u[l]; uu = us; }
+        const double w = scn_step_violation(K, xo, nx, uu, nu);
+        const double old = first ? 0.0 : viol[i];
+        viol[i] = w > old ? w : old;
+    }
+}
+
+// xh <- predict(xh, u, d_k) by dynamics_rows on the observer's model; xh: the scenario's record, NW / nw wide
+template <int NW, class D>
+__device__ __forceinline__ void scn_observer_predict(const double *obs_dyn, double *xh, int nw, int nu, int nd, const double *u, D &&dk) {
+    constexpr int NWA = NW > 0 ? NW : 32;
+    double ho[NWA], hn[NWA];
+    for_nx<NW>(nw, [&](int c) { ho[c] = xh[c]; });
+    dynamics_rows<NW>(obs_dyn, ho, hn, nw, nu, nd, u, dk);
+    for_nx<NW>(nw, [&](int c) { xh[c] = hn[c]; });
+}
+
+// POST kernel of step k, one lane per scenario: scn_score_step, xhat <- predict(xhat, u, d_k) by scn_observer_predict,
+// x <- f_offset + F x + G u + Gd d_k by dynamics_rows on the true plant's array, then step_tail: uprev <- u,
+// trajectories, smallest exit flag.
 template <int NXT, bool COST>
 __global__ __launch_bounds__(256) void scenario_post_kernel(ScnPost A, ScnConst K) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -181,31 +248,8 @@ __global__ __launch_bounds__(256) void scenario_post_kernel(ScnPost A, ScnConst 
     auto dk = [&](int q) { return block_at(A.d, i, A.k, q); };
     double xo[NXA], xn[NXA];
     for_nx<NXT>(nx, [&](int c) { xo[c] = A.x[i * nx + c]; });
-    if constexpr (COST) {
-        if (A.cost) {
-            double ul[64];
-            if (K.cRr >= 0) for (int l = 0; l < nu; l++) ul[l] = A.first ? 0.0 : A.ulast[i * nu + l];
-            double us[64];
-            for (int l = 0; l < nu; l++) us[l] = u[l];
-            const double c = scn_step_cost(K, xo, nx, us, ul, nu, A.r, i, A.k);
-            const double run = __dadd_rn(A.first ? 0.0 : A.cost[i], c);
-            A.cost[i] = A.last ? __dmul_rn(0.5, run) : run;
-            if (K.cRr >= 0 && !A.last) for (int l = 0; l < nu; l++) A.ulast[i * nu + l] = us[l];
-        }
-        if (A.viol) {
-            double us[64];
-            for (int l = 0; l < nu; l++) us[l] = u[l];
-            const double w = scn_step_violation(K, xo, nx, us, nu);
-            const double old = A.first ? 0.0 : A.viol[i];
-            A.viol[i] = w > old ? w : old;
-        }
-    }
-    if (A.xhat) {
-        double ho[NXA], hn[NXA];
-        for_nx<NXT>(nx, [&](int c) { ho[c] = A.xhat[i * nx + c]; });
-        dynamics_rows<NXT>(A.obs_dyn, ho, hn, nx, nu, A.nd, u, dk);
-        for_nx<NXT>(nx, [&](int c) { A.xhat[i * nx + c] = hn[c]; });
-    }
+    if constexpr (COST) scn_score_step<true>(K, xo, nx, u, nu, A.cost, A.viol, A.ulast, A.r, i, A.k, A.first, A.last);
+    if (A.xhat) scn_observer_predict<NXT>(A.obs_dyn, A.xhat + i * nx, nx, nu, A.nd, u, dk);
     dynamics_rows<NXT>(K.c + K.plant, xo, xn, nx, nu, A.nd, u, dk);
     for_nx<NXT>(nx, [&](int a) { A.x[i * nx + a] = xn[a]; });
     if (A.xtraj_next) for_nx<NXT>(nx, [&](int a) { A.xtraj_next[i * nx + a] = xn[a]; });

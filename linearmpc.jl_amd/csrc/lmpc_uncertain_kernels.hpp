@@ -5,11 +5,10 @@
 // scenario.  e_k and v_k are either read from a supplied block or drawn here, uniform in a box, from a counter-based
 // generator: a draw depends on (seed, global scenario, global step, stream, component) and on nothing of the launch.
 //
-// The sums are the ones of the scenario loop, called, not restated: correct_row and dynamics_rows, block_at /
-// block_entry, scn_step_cost / scn_step_violation, step_tail.  The measurement sum is inline in scenario_pre_kernel, so
-// uncertain_pre_kernel carries its fourth copy (scenario_pre_kernel, offset_free_pre_kernel, explicit_sim_run_kernel).
-// With every source absent and no plant table both kernels execute the arithmetic of scenario_pre_kernel /
-// scenario_post_kernel operation for operation.
+// The sums are the ones of the scenario loop, called, not restated: the PRE kernel is scn_pre_step with the measurement
+// source added to ym, the POST kernel scn_score_step, scn_observer_predict, dynamics_rows and step_tail around the
+// process noise (unc_process_noise).  With every source absent and no plant table both kernels execute the arithmetic
+// of scenario_pre_kernel / scenario_post_kernel operation for operation.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -126,67 +125,47 @@ __device__ __forceinline__ double unc_value(const UncSource &S, const double *__
 template <int NXT, bool GAUSS = false>
 __global__ __launch_bounds__(256) void uncertain_pre_kernel(ScnPre A, ScnConst K, UncStep U) {
     extern __shared__ double unc_lds[];
-    constexpr int NXA = NXT > 0 ? NXT : 32;
-    const int nx = NXT > 0 ? NXT : A.nx;
-    const long long base = (long long)blockIdx.x * 256;
-    const long long i = base + threadIdx.x;
-    if (i < A.n) {
-        double xo[NXA], xh[NXA], xn[NXA];
-        auto dk = [&](int q) { return block_at(A.d, i, A.k, q); };
-        for_nx<NXT>(nx, [&](int c) { xo[c] = A.x[i * nx + c]; });
-        const bool obs = A.xhat != nullptr;
-        if (obs) for_nx<NXT>(nx, [&](int c) { xh[c] = A.xhat[i * nx + c]; xn[c] = xh[c]; });
-        else for_nx<NXT>(nx, [&](int c) { xn[c] = xo[c]; });
-        const int ms = 1 + nx + A.nd;
-        typename std::conditional<GAUSS, UncDrawsGauss, UncDraws>::type dv(U, i, 1u);
-        for (int j = 0; j < A.ny; j++) {
-            const double *mr = K.c + K.meas + j * ms;
-            double ym = mr[0], y = 0.0;
-            for_nx<NXT>(nx, [&](int c) {
-                const double t = __dmul_rn(mr[1 + c], xo[c]);
-                ym = __dadd_rn(ym, t); y = __dadd_rn(y, t);
-            });
-            for (int q = 0; q < A.nd; q++) {
-                const double t = __dmul_rn(mr[1 + nx + q], dk(q));
-                ym = __dadd_rn(ym, t); y = __dadd_rn(y, t);
-            }
-            if (A.noise.w > 0) ym = __dadd_rn(ym, block_at(A.noise, i, A.k, j));
-            if (U.meas.w > 0) ym = __dadd_rn(ym, unc_value(U.meas, K.c, dv, i, A.k, j));
-            if (A.ym_out) A.ym_out[i * A.ny + j] = ym;
-            if (A.y_out) A.y_out[i * A.ny + j] = obs ? y : ym;
-            if (obs) correct_row<NXT>(A.obs_meas + j * ms, A.obs_kt + j * nx, ym, xh, xn, nx, A.nd, dk);
-        }
-        for_nx<NXT>(nx, [&](int c) {
-            if (obs) A.xhat[i * nx + c] = xn[c];
-            if (A.xhat_out) A.xhat_out[i * nx + c] = xn[c];
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    typename std::conditional<GAUSS, UncDrawsGauss, UncDraws>::type dv(U, i, 1u);
+    scn_pre_step<NXT>(A, K, unc_lds, [&](int j, double ym) {
+        return U.meas.w > 0 ? __dadd_rn(ym, unc_value(U.meas, K.c, dv, i, A.k, j)) : ym;
+    });
+}
+
+// Process noise onto the finished row sums xn of scenario i: x_a <- x_a + Gw_a0 e_0 + Gw_a1 e_1 + ... term by term
+// (x_a <- x_a + e_a without Gw).  W_traj: row a = 0 + Gw_a0 e_0 + ... in the same order, or e_a.  The terms are visited
+// component by component (one draw per component) with the rows' running sums side by side, which is the same order of
+// additions for every row.
+template <int NXT, class Draws>
+__device__ __forceinline__ void unc_process_noise(const UncStep &U, const double *__restrict__ c, long long i, int k, int nx, double *xn) {
+    const int nw = U.process.w;
+    if (nw <= 0) return;
+    Draws de(U, i, 0u);
+    if (U.gw < 0) {
+        for_nx<NXT>(nx, [&](int a) {
+            const double e = unc_value(U.process, c, de, i, k, a);
+            xn[a] = __dadd_rn(xn[a], e);
+            if (U.w_out) U.w_out[i * nx + a] = e;
         });
-        for_nx<NXT>(nx, [&](int c) { unc_lds[threadIdx.x * nx + c] = xn[c]; });
-        if (A.d_out) for (int q = 0; q < A.nd; q++) A.d_out[i * A.nd + q] = dk(q);
-    }
-    __syncthreads();
-    const int nr = A.r.width(), ndw = A.d.width(), npw = A.p.width();
-    const int nth = nx + nr + ndw + A.nup + npw;
-    const long long left = A.n - base;
-    const int rows = left < 256 ? (int)left : 256;
-    for (int idx = threadIdx.x; idx < rows * nth; idx += 256) {
-        const int sl = idx / nth;
-        int e = idx - sl * nth;
-        const long long s = base + sl;
-        double v;
-        if (e < nx) v = unc_lds[sl * nx + e];
-        else if ((e -= nx) < nr) v = block_entry(A.r, s, e);
-        else if ((e -= nr) < ndw) v = block_entry(A.d, s, e);
-        else if ((e -= ndw) < A.nup) v = A.uprev[s * A.nup + e];
-        else v = block_entry(A.p, s, e - A.nup);
-        A.theta[base * nth + idx] = v;
+    } else {
+        const double *gw = c + U.gw;
+        double wv[NXT > 0 ? NXT : 32];
+        for_nx<NXT>(nx, [&](int a) { wv[a] = 0.0; });
+        for (int q = 0; q < nw; q++) {
+            const double e = unc_value(U.process, c, de, i, k, q);
+            for_nx<NXT>(nx, [&](int a) {
+                const double t = __dmul_rn(gw[a * nw + q], e);
+                xn[a] = __dadd_rn(xn[a], t);
+                wv[a] = __dadd_rn(wv[a], t);
+            });
+        }
+        if (U.w_out) for_nx<NXT>(nx, [&](int a) { U.w_out[i * nx + a] = wv[a]; });
     }
 }
 
 // POST kernel of step k: scenario_post_kernel with the scenario's own plant rows (table + idx * nx * (1 + nx + nu + nd);
-// a plant_index entry is taken as unsigned, modulo n_plants, so no entry addresses outside the table), and then, onto
-// the finished row sums, x_a <- x_a + Gw_a0 e_0 + Gw_a1 e_1 + ... term by term (x_a <- x_a + e_a without Gw).  W_traj:
-// row a = 0 + Gw_a0 e_0 + ... in the same order, or e_a.  The terms are visited component by component (one draw per
-// component) with the rows' running sums side by side, which is the same order of additions for every row.
+// a plant_index entry is taken as unsigned, modulo n_plants, so no entry addresses outside the table), and then
+// unc_process_noise onto the finished row sums.
 template <int NXT, bool COST, bool GAUSS = false>
 __global__ __launch_bounds__(256) void uncertain_post_kernel(ScnPost A, ScnConst K, UncStep U) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -198,61 +177,15 @@ __global__ __launch_bounds__(256) void uncertain_post_kernel(ScnPost A, ScnConst
     auto dk = [&](int q) { return block_at(A.d, i, A.k, q); };
     double xo[NXA], xn[NXA];
     for_nx<NXT>(nx, [&](int c) { xo[c] = A.x[i * nx + c]; });
-    if constexpr (COST) {
-        if (A.cost) {
-            double ul[64];
-            if (K.cRr >= 0) for (int l = 0; l < nu; l++) ul[l] = A.first ? 0.0 : A.ulast[i * nu + l];
-            double us[64];
-            for (int l = 0; l < nu; l++) us[l] = u[l];
-            const double c = scn_step_cost(K, xo, nx, us, ul, nu, A.r, i, A.k);
-            const double run = __dadd_rn(A.first ? 0.0 : A.cost[i], c);
-            A.cost[i] = A.last ? __dmul_rn(0.5, run) : run;
-            if (K.cRr >= 0 && !A.last) for (int l = 0; l < nu; l++) A.ulast[i * nu + l] = us[l];
-        }
-        if (A.viol) {
-            double us[64];
-            for (int l = 0; l < nu; l++) us[l] = u[l];
-            const double w = scn_step_violation(K, xo, nx, us, nu);
-            const double old = A.first ? 0.0 : A.viol[i];
-            A.viol[i] = w > old ? w : old;
-        }
-    }
-    if (A.xhat) {
-        double ho[NXA], hn[NXA];
-        for_nx<NXT>(nx, [&](int c) { ho[c] = A.xhat[i * nx + c]; });
-        dynamics_rows<NXT>(A.obs_dyn, ho, hn, nx, nu, A.nd, u, dk);
-        for_nx<NXT>(nx, [&](int c) { A.xhat[i * nx + c] = hn[c]; });
-    }
+    if constexpr (COST) scn_score_step<true>(K, xo, nx, u, nu, A.cost, A.viol, A.ulast, A.r, i, A.k, A.first, A.last);
+    if (A.xhat) scn_observer_predict<NXT>(A.obs_dyn, A.xhat + i * nx, nx, nu, A.nd, u, dk);
     long long prow = 0;
     if (U.n_plants > 0) {
         const unsigned long long g = U.plant_index ? (unsigned long long)(uint32_t)U.plant_index[i] : U.goff + (unsigned long long)i;
         prow = (long long)(g % (unsigned long long)U.n_plants) * ((long long)nx * (1 + nx + nu + A.nd));
     }
     dynamics_rows<NXT>(K.c + K.plant + prow, xo, xn, nx, nu, A.nd, u, dk);
-    const int nw = U.process.w;
-    if (nw > 0) {
-        typename std::conditional<GAUSS, UncDrawsGauss, UncDraws>::type de(U, i, 0u);
-        if (U.gw < 0) {
-            for_nx<NXT>(nx, [&](int a) {
-                const double e = unc_value(U.process, K.c, de, i, A.k, a);
-                xn[a] = __dadd_rn(xn[a], e);
-                if (U.w_out) U.w_out[i * nx + a] = e;
-            });
-        } else {
-            const double *gw = K.c + U.gw;
-            double wv[NXA];
-            for_nx<NXT>(nx, [&](int a) { wv[a] = 0.0; });
-            for (int q = 0; q < nw; q++) {
-                const double e = unc_value(U.process, K.c, de, i, A.k, q);
-                for_nx<NXT>(nx, [&](int a) {
-                    const double t = __dmul_rn(gw[a * nw + q], e);
-                    xn[a] = __dadd_rn(xn[a], t);
-                    wv[a] = __dadd_rn(wv[a], t);
-                });
-            }
-            if (U.w_out) for_nx<NXT>(nx, [&](int a) { U.w_out[i * nx + a] = wv[a]; });
-        }
-    }
+    unc_process_noise<NXT, typename std::conditional<GAUSS, UncDrawsGauss, UncDraws>::type>(U, K.c, i, A.k, nx, xn);
     for_nx<NXT>(nx, [&](int a) { A.x[i * nx + a] = xn[a]; });
     if (A.xtraj_next) for_nx<NXT>(nx, [&](int a) { A.xtraj_next[i * nx + a] = xn[a]; });
     step_tail(i, u, nu, A.uprev + i * A.nup, (double *)nullptr, A.nup, A.utraj, A.flag, A.flag_min, A.first);
