@@ -305,25 +305,25 @@ int launch_screen(lmpc_handle *h, int64_t nprob, const double *theta, double *x,
 }
 
 template <typename R>
-int launch_wave_t(lmpc_handle *h, const R *dC, int64_t nprob, const R *theta, R *x, int32_t *flag,
+int launch_wave_t(lmpc_handle *h, const WaveArgs &a, const R *dC, int64_t nprob, const R *theta, R *x, int32_t *flag,
                   int32_t *iters, uint64_t *active, const uint64_t *warm, hipStream_t st) {
     if constexpr (sizeof(R) == 8) {
         // plain batched solve (no plant step to fuse, no kept factorisation, no run-ahead): the instantiations built
         // without the closed-loop machinery
         if (!h->bnb && h->waveSim.FG == nullptr && !h->keepOn)
-            return h->waveGram ? launch_wave_inst<R, false, true, false>(h, dC, nprob, theta, x, flag, iters, active, warm, st)
-                               : launch_wave_inst<R, false, false, false>(h, dC, nprob, theta, x, flag, iters, active, warm, st);
+            return h->waveGram ? launch_wave_inst<R, false, true, false>(h, a, dC, nprob, theta, x, flag, iters, active, warm, st)
+                               : launch_wave_inst<R, false, false, false>(h, a, dC, nprob, theta, x, flag, iters, active, warm, st);
     }
     if (h->waveGram)
-        return h->bnb ? launch_wave_inst<R, true, true>(h, dC, nprob, theta, x, flag, iters, active, warm, st)
-                      : launch_wave_inst<R, false, true>(h, dC, nprob, theta, x, flag, iters, active, warm, st);
-    return h->bnb ? launch_wave_inst<R, true, false>(h, dC, nprob, theta, x, flag, iters, active, warm, st)
-                  : launch_wave_inst<R, false, false>(h, dC, nprob, theta, x, flag, iters, active, warm, st);
+        return h->bnb ? launch_wave_inst<R, true, true>(h, a, dC, nprob, theta, x, flag, iters, active, warm, st)
+                      : launch_wave_inst<R, false, true>(h, a, dC, nprob, theta, x, flag, iters, active, warm, st);
+    return h->bnb ? launch_wave_inst<R, true, false>(h, a, dC, nprob, theta, x, flag, iters, active, warm, st)
+                  : launch_wave_inst<R, false, false>(h, a, dC, nprob, theta, x, flag, iters, active, warm, st);
 }
 
-int launch_wave(lmpc_handle *h, int64_t nprob, const double *theta, double *x, int32_t *flag,
+int launch_wave(lmpc_handle *h, const WaveArgs &a, int64_t nprob, const double *theta, double *x, int32_t *flag,
                 int32_t *iters, uint64_t *active, const uint64_t *warm, hipStream_t st) {
-    return launch_wave_t<double>(h, h->dCw, nprob, theta, x, flag, iters, active, warm, st);
+    return launch_wave_t<double>(h, a, h->dCw, nprob, theta, x, flag, iters, active, warm, st);
 }
 
 // binary32 constant pack of the wave kernel (same layout as the binary64 one): every array of the
@@ -388,54 +388,60 @@ int ensure_lists(lmpc_handle *h, int64_t nprob, hipStream_t st) {
     return LMPC_OK;
 }
 
-#define LMPC_SCREEN_SWITCH(CALL)                                                                       \
-    switch (h->P.nth <= 16 ? h->P.nth : 32) { /* exact column count up to 16, padded beyond */        \
-        case 1: rc = CALL(8, 1); break;    case 2: rc = CALL(8, 2); break;                             \
-        case 3: rc = CALL(8, 3); break;    case 4: rc = CALL(8, 4); break;                             \
-        case 5: rc = CALL(8, 5); break;    case 6: rc = CALL(8, 6); break;                             \
-        case 7: rc = CALL(8, 7); break;    case 8: rc = CALL(8, 8); break;                             \
-        case 9: rc = CALL(16, 9); break;   case 10: rc = CALL(16, 10); break;                          \
-        case 11: rc = CALL(16, 11); break; case 12: rc = CALL(16, 12); break;                          \
-        case 13: rc = CALL(16, 13); break; case 14: rc = CALL(16, 14); break;                          \
-        case 15: rc = CALL(16, 15); break; case 16: rc = CALL(16, 16); break;                          \
-        default: rc = CALL(32, 32); break;                                                             \
+// the work-list counter set of this call and the one the call's iterating kernel clears for the next call
+void next_count_set(lmpc_handle *h, int32_t **now, int32_t **next) {
+    *now = h->dCount + (size_t)h->countSet * kShards * kCountStride;
+    *next = h->dCount + (size_t)(h->countSet ^ 1) * kShards * kCountStride;
+    h->countSet ^= 1;
+}
+
+// ... and the list a front pass over a batch of nprob problems filled, as the wavefront path takes it
+WaveList work_list(const int32_t *list, const int32_t *count, int32_t *count_next, int64_t nprob) {
+    WaveList wl;
+    wl.list = list; wl.count = count; wl.count_next = count_next; wl.seg_cap = lane_seg_cap(nprob);
+    return wl;
+}
+
+// The screening pass at the handle's column count (exact up to 16, padded beyond) in one of its modes: 0 plain, 1 closed
+// loop with the plant step fused in (SimFuse), 2 generated controller (GatherArgs), 3 several outputs, stored transposed
+template <int NTHMAX, int NT>
+int launch_screen_mode(lmpc_handle *h, int mode, int64_t nprob, const double *theta, double *x, int32_t *flag,
+                       int32_t *iters, uint64_t *active, const uint64_t *warm, int32_t *count, hipStream_t st) {
+    switch (mode) {
+        case 1: return launch_screen<NTHMAX, NT, 1>(h, nprob, theta, x, flag, iters, active, warm, count, st);
+        case 2: return launch_screen<NTHMAX, NT, 2>(h, nprob, theta, x, flag, iters, active, warm, count, st);
+        case 3: return launch_screen<NTHMAX, NT, 3>(h, nprob, theta, x, flag, iters, active, warm, count, st);
+        default: return launch_screen<NTHMAX, NT, 0>(h, nprob, theta, x, flag, iters, active, warm, count, st);
     }
+}
+
+int launch_screen_any(lmpc_handle *h, int mode, int64_t nprob, const double *theta, double *x, int32_t *flag,
+                      int32_t *iters, uint64_t *active, const uint64_t *warm, int32_t *count, hipStream_t st) {
+#define LMPC_SCR(NM, NT) case NT: return launch_screen_mode<NM, NT>(h, mode, nprob, theta, x, flag, iters, active, warm, count, st);
+    switch (h->P.nth <= 16 ? h->P.nth : 32) {
+        LMPC_SCR(8, 1) LMPC_SCR(8, 2) LMPC_SCR(8, 3) LMPC_SCR(8, 4) LMPC_SCR(8, 5) LMPC_SCR(8, 6) LMPC_SCR(8, 7) LMPC_SCR(8, 8)
+        LMPC_SCR(16, 9) LMPC_SCR(16, 10) LMPC_SCR(16, 11) LMPC_SCR(16, 12) LMPC_SCR(16, 13) LMPC_SCR(16, 14) LMPC_SCR(16, 15)
+        LMPC_SCR(16, 16)
+        default: return launch_screen_mode<32, 32>(h, mode, nprob, theta, x, flag, iters, active, warm, count, st);
+    }
+#undef LMPC_SCR
+}
 
 // wavefront-kernel handles: the streaming pass finishes what needs no iterations, the wavefront kernel walks the rest
 int launch_wave_screened(lmpc_handle *h, int64_t nprob, const double *theta, double *x, int32_t *flag,
                          int32_t *iters, uint64_t *active, const uint64_t *warm, hipStream_t st) {
-    const int rc0 = ensure_lists(h, nprob, st);
-    if (rc0 != LMPC_OK) return rc0;
-    EventTriple ev{};
-    if (h->prof) {
-        HIP_TRY(h, pool_event(h, &ev.a));
-        HIP_TRY(h, pool_event(h, &ev.mid));
-        HIP_TRY(h, pool_event(h, &ev.b));
-        HIP_TRY(h, hipEventRecord(ev.a, st));
-    }
-    int32_t *cnt_now = h->dCount + (size_t)h->countSet * kShards * kCountStride;
-    int32_t *cnt_next = h->dCount + (size_t)(h->countSet ^ 1) * kShards * kCountStride;
-    h->countSet ^= 1;
-    const bool wide = h->P.nout > 1 && h->P.nout <= 16;
-    int rc = LMPC_OK;
-    const bool simf = h->L.sim.FG != nullptr;     // closed loop, plant step fused in (lmpc_simulate_device)
-#define LMPC_SCRW(NM, NT) (simf ? launch_screen<NM, NT, 1>(h, nprob, theta, x, flag, iters, active, warm, cnt_now, st) \
-                           : wide ? launch_screen<NM, NT, 3>(h, nprob, theta, x, flag, iters, active, warm, cnt_now, st) \
-                                  : launch_screen<NM, NT, 0>(h, nprob, theta, x, flag, iters, active, warm, cnt_now, st))
-    LMPC_SCREEN_SWITCH(LMPC_SCRW)
-#undef LMPC_SCRW
-    if (h->prof) HIP_TRY(h, hipEventRecord(ev.mid, st));
-    if (rc == LMPC_OK) {
-        h->waveList.list = h->dList; h->waveList.count = cnt_now; h->waveList.count_next = cnt_next;
-        h->waveList.seg_cap = lane_seg_cap(nprob);
-        rc = launch_wave(h, nprob, theta, x, flag, iters, active, warm, st);
-        h->waveList = WaveList{};
-    }
-    if (h->prof) {
-        if (rc == LMPC_OK) { HIP_TRY(h, hipEventRecord(ev.b, st)); h->events.push_back(ev); }
-        else { hipEventDestroy(ev.a); hipEventDestroy(ev.mid); hipEventDestroy(ev.b); }
-    }
-    return rc;
+    LMPC_TRY(ensure_lists(h, nprob, st));
+    ProfBracket prof(h, st);
+    LMPC_TRY(prof.begin(h->prof));
+    int32_t *cnt_now, *cnt_next;
+    next_count_set(h, &cnt_now, &cnt_next);
+    // closed loop with the plant step fused in (lmpc_simulate_device), else several outputs stored transposed, else plain
+    const int mode = h->L.sim.FG != nullptr ? 1 : (h->P.nout > 1 && h->P.nout <= 16 ? 3 : 0);
+    int rc = launch_screen_any(h, mode, nprob, theta, x, flag, iters, active, warm, cnt_now, st);
+    LMPC_TRY(prof.mid());
+    if (rc == LMPC_OK)
+        rc = launch_wave(h, wave_args(h, work_list(h->dList, cnt_now, cnt_next, nprob)), nprob, theta, x, flag, iters, active, warm, st);
+    return prof.end(rc);
 }
 
 // With or without the tiers pass?  Returns the variant for this call (0 = with, 1 = without) and, in *measure, the
@@ -477,6 +483,19 @@ int qp_ab_choose(lmpc_handle *h, int64_t nprob, hipStream_t st, int *measure) {
     return variant;
 }
 
+// ... the two event records around a call that is to be timed as variant `measure` (-1: none)
+int qp_ab_begin(lmpc_handle *h, int measure, hipStream_t st) {
+    if (measure >= 0) HIP_TRY(h, hipEventRecord(h->qpAbEv[measure][0], st));
+    return LMPC_OK;
+}
+int qp_ab_end(lmpc_handle *h, int measure, int rc, int64_t nprob, hipStream_t st) {
+    if (measure >= 0 && rc == LMPC_OK) {
+        HIP_TRY(h, hipEventRecord(h->qpAbEv[measure][1], st));
+        h->qpAbN[measure] = nprob; h->qpAbPending[measure] = true;
+    }
+    return rc;
+}
+
 // Small problems with many rows (lmpc_qp_tiers_kernel.hpp): the tiers pass over the whole batch -- it finishes what the
 // screening pass would and every problem on an append-only path, optimal or infeasible -- then the wavefront kernel on
 // its work list.  Cold plain binary64 solves in the n-chain form only.
@@ -488,31 +507,16 @@ bool qp_tiers_applies(const lmpc_handle *h, int64_t nprob, const double *x, cons
 
 int launch_wave_tiered(lmpc_handle *h, int64_t nprob, const double *theta, double *x, int32_t *flag, int32_t *iters,
                        uint64_t *active, hipStream_t st) {
-    const int rc0 = ensure_lists(h, nprob, st);
-    if (rc0 != LMPC_OK) return rc0;
-    EventTriple ev{};
-    if (h->prof) {
-        HIP_TRY(h, pool_event(h, &ev.a));
-        HIP_TRY(h, pool_event(h, &ev.mid));
-        HIP_TRY(h, pool_event(h, &ev.b));
-        HIP_TRY(h, hipEventRecord(ev.a, st));
-    }
-    int32_t *cnt_now = h->dCount + (size_t)h->countSet * kShards * kCountStride;
-    int32_t *cnt_next = h->dCount + (size_t)(h->countSet ^ 1) * kShards * kCountStride;
-    h->countSet ^= 1;
+    LMPC_TRY(ensure_lists(h, nprob, st));
+    ProfBracket prof(h, st);
+    LMPC_TRY(prof.begin(h->prof));
+    int32_t *cnt_now, *cnt_next;
+    next_count_set(h, &cnt_now, &cnt_next);
     int rc = launch_qp_tiers(h, nprob, theta, x, flag, iters, active, h->dList, cnt_now, lane_seg_cap(nprob), st, false);
-    if (h->prof) HIP_TRY(h, hipEventRecord(ev.mid, st));
-    if (rc == LMPC_OK) {
-        h->waveList.list = h->dList; h->waveList.count = cnt_now; h->waveList.count_next = cnt_next;
-        h->waveList.seg_cap = lane_seg_cap(nprob);
-        rc = launch_wave(h, nprob, theta, x, flag, iters, active, nullptr, st);
-        h->waveList = WaveList{};
-    }
-    if (h->prof) {
-        if (rc == LMPC_OK) { HIP_TRY(h, hipEventRecord(ev.b, st)); h->events.push_back(ev); }
-        else { hipEventDestroy(ev.a); hipEventDestroy(ev.mid); hipEventDestroy(ev.b); }
-    }
-    return rc;
+    LMPC_TRY(prof.mid());
+    if (rc == LMPC_OK)
+        rc = launch_wave(h, wave_args(h, work_list(h->dList, cnt_now, cnt_next, nprob)), nprob, theta, x, flag, iters, active, nullptr, st);
+    return prof.end(rc);
 }
 
 // First large batch of a FRESH wavefront-kernel handle: whether a batch first runs at a smaller working-set capacity (two
@@ -538,16 +542,18 @@ int wave_probe(lmpc_handle *h, const double *theta, int64_t nprob, hipStream_t s
     int32_t *pf = nullptr;
     HIP_TRY(h, hipMalloc(&px, sizeof(double) * (size_t)kProbe * h->P.nout));
     if (hipMalloc(&pf, sizeof(int32_t) * (size_t)kProbe) != hipSuccess) { hipFree(px); return fail(h, LMPC_ERR_HIP, "lmpc: probe scratch"); }
-    // the probe is a plain cold solve: closed-loop fusion, work lists, kept factors and profiling stay out of it
-    const SimFuse sim = h->L.sim; const WaveSim wsim = h->waveSim; const WaveList wl = h->waveList;
-    const int phase = h->asyncPhase; const bool keep = h->keepOn, prof = h->prof;
-    h->L.sim = SimFuse{}; h->waveSim = WaveSim{}; h->waveList = WaveList{}; h->asyncPhase = 0; h->keepOn = false; h->prof = false;
     int rc = LMPC_OK;
-    if (wave_screens(h, nprob)) rc = ensure_lists(h, nprob, st);          // (sized for the batch that follows, once)
-    if (rc == LMPC_OK)
-        rc = wave_screens(h, kProbe) ? launch_wave_screened(h, kProbe, theta, px, pf, nullptr, nullptr, nullptr, st)
-                                     : launch_wave(h, kProbe, theta, px, pf, nullptr, nullptr, nullptr, st);
-    h->L.sim = sim; h->waveSim = wsim; h->waveList = wl; h->asyncPhase = phase; h->keepOn = keep; h->prof = prof;
+    {
+        // the probe is a plain cold solve: closed-loop fusion, kept factors and profiling stay out of it
+        const Restore<SimFuse> noSim(h->L.sim, SimFuse{});
+        const Restore<WaveSim> noWaveSim(h->waveSim, WaveSim{});
+        const Restore<int> noPhase(h->asyncPhase, 0);
+        const Restore<bool> noKeep(h->keepOn, false), noProf(h->prof, false);
+        if (wave_screens(h, nprob)) rc = ensure_lists(h, nprob, st);          // (sized for the batch that follows, once)
+        if (rc == LMPC_OK)
+            rc = wave_screens(h, kProbe) ? launch_wave_screened(h, kProbe, theta, px, pf, nullptr, nullptr, nullptr, st)
+                                         : launch_wave(h, wave_args(h), kProbe, theta, px, pf, nullptr, nullptr, nullptr, st);
+    }
     if (rc == LMPC_OK && h->dStat && h->hStat) {
         unsigned long long raw[64 * 16];
         if (hipMemcpyAsync(raw, h->dStat, sizeof(raw), hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess) {
@@ -568,10 +574,9 @@ int wave_probe(lmpc_handle *h, const double *theta, int64_t nprob, hipStream_t s
 // scenarios of the round before's list run ahead in registers to their next step that needs iterations; those go on
 // the work list the iterating half (lane kernel or wavefront kernel) consumes.
 int launch_sim_run(lmpc_handle *h, int64_t nprob, const double *theta, uint64_t *active, const uint64_t *warm, hipStream_t st) {
-    { const int rc0 = ensure_lists(h, nprob, st); if (rc0 != LMPC_OK) return rc0; }
-    int32_t *cnt_now = h->dCount + (size_t)h->countSet * kShards * kCountStride;
-    int32_t *cnt_next = h->dCount + (size_t)(h->countSet ^ 1) * kShards * kCountStride;
-    h->countSet ^= 1;
+    LMPC_TRY(ensure_lists(h, nprob, st));
+    int32_t *cnt_now, *cnt_next;
+    next_count_set(h, &cnt_now, &cnt_next);
     h->asyncCntNow = cnt_now; h->asyncCntNext = cnt_next;
     const long long segCap = lane_seg_cap(nprob);
     if (!h->dList2) HIP_TRY(h, hipMalloc(&h->dList2, sizeof(int32_t) * (size_t)lane_seg_cap(h->listCap) * kShards));
@@ -610,55 +615,32 @@ int launch_sim_run(lmpc_handle *h, int64_t nprob, const double *theta, uint64_t 
     return LMPC_OK;
 }
 
-int launch(lmpc_handle *h, int64_t nprob, const double *theta, double *x, int32_t *flag,
-           int32_t *iters, uint64_t *active, const uint64_t *warm, hipStream_t st) {
-    if (h->avi) {
-        // non-symmetric H (variational objective): its own kernel; timing events around the one launch
-        EventTriple ev{};
-        if (h->prof) {
-            HIP_TRY(h, pool_event(h, &ev.a));
-            HIP_TRY(h, pool_event(h, &ev.b));
-            HIP_TRY(h, hipEventRecord(ev.a, st));
-        }
-        const int rca = launch_avi(h, nprob, theta, x, flag, iters, active, warm, st);
-        if (h->prof) {
-            if (rca == LMPC_OK) { HIP_TRY(h, hipEventRecord(ev.b, st)); h->events.push_back(ev); }
-            else { hipEventDestroy(ev.a); hipEventDestroy(ev.b); }
-        }
-        return rca;
-    }
-    if (h->useWave) {
-        // scenario-asynchronous closed loop on the wavefront path: streaming half = sim_run_kernel on the handle's
-        // screening pack, iterating half = the wavefront kernel on that pass's work list (it advances the scenarios
-        // it solves, WaveSim)
-        if (h->asyncPhase == 1) return launch_sim_run(h, nprob, theta, active, warm, st);
-        if (h->asyncPhase == 2) {
-            h->waveList.list = h->asyncListOut; h->waveList.count = h->asyncCntNow; h->waveList.count_next = h->asyncCntNext;
-            h->waveList.seg_cap = lane_seg_cap(nprob);
-            const int rcw = launch_wave(h, nprob, theta, x, flag, iters, active, warm, st);
-            h->waveList = WaveList{};
-            return rcw;
-        }
-        if (!h->waveProbed && h->L.sim.FG == nullptr && h->waveSim.FG == nullptr) {
-            const int rcp = wave_probe(h, theta, nprob, st);
-            if (rcp != LMPC_OK) return rcp;
-        }
-        if (qp_tiers_applies(h, nprob, x, flag, warm)) {
-            int measure = -1;
-            const int variant = qp_ab_choose(h, nprob, st, &measure);
-            if (measure >= 0) HIP_TRY(h, hipEventRecord(h->qpAbEv[measure][0], st));
-            const int rct = variant == 0 ? launch_wave_tiered(h, nprob, theta, x, flag, iters, active, st)
-                          : (wave_screens(h, nprob) ? launch_wave_screened(h, nprob, theta, x, flag, iters, active, warm, st)
-                                                    : launch_wave(h, nprob, theta, x, flag, iters, active, warm, st));
-            if (measure >= 0 && rct == LMPC_OK) {
-                HIP_TRY(h, hipEventRecord(h->qpAbEv[measure][1], st));
-                h->qpAbN[measure] = nprob; h->qpAbPending[measure] = true;
-            }
-            return rct;
-        }
+// A batch on a wavefront-kernel handle: the tiers pass or the screening pass in front where they apply
+int launch_on_wave(lmpc_handle *h, int64_t nprob, const double *theta, double *x, int32_t *flag,
+                   int32_t *iters, uint64_t *active, const uint64_t *warm, hipStream_t st) {
+    // scenario-asynchronous closed loop on the wavefront path: streaming half = sim_run_kernel on the handle's
+    // screening pack, iterating half = the wavefront kernel on that pass's work list (it advances the scenarios
+    // it solves, WaveSim)
+    if (h->asyncPhase == 1) return launch_sim_run(h, nprob, theta, active, warm, st);
+    if (h->asyncPhase == 2)
+        return launch_wave(h, wave_args(h, work_list(h->asyncListOut, h->asyncCntNow, h->asyncCntNext, nprob)), nprob, theta, x, flag,
+                           iters, active, warm, st);
+    if (!h->waveProbed && h->L.sim.FG == nullptr && h->waveSim.FG == nullptr) LMPC_TRY(wave_probe(h, theta, nprob, st));
+    auto screened_or_plain = [&]() {
         return wave_screens(h, nprob) ? launch_wave_screened(h, nprob, theta, x, flag, iters, active, warm, st)
-                                      : launch_wave(h, nprob, theta, x, flag, iters, active, warm, st);
-    }
+                                      : launch_wave(h, wave_args(h), nprob, theta, x, flag, iters, active, warm, st);
+    };
+    if (!qp_tiers_applies(h, nprob, x, flag, warm)) return screened_or_plain();
+    int measure = -1;
+    const int variant = qp_ab_choose(h, nprob, st, &measure);
+    LMPC_TRY(qp_ab_begin(h, measure, st));
+    const int rc = variant == 0 ? launch_wave_tiered(h, nprob, theta, x, flag, iters, active, st) : screened_or_plain();
+    return qp_ab_end(h, measure, rc, nprob, st);
+}
+
+// A batch on a lane-kernel handle: the one-launch kernel, or a front pass (screening, tiers, sim_run) and the lane kernel
+int launch_on_lanes(lmpc_handle *h, int64_t nprob, const double *theta, double *x, int32_t *flag,
+                    int32_t *iters, uint64_t *active, const uint64_t *warm, hipStream_t st) {
     // block size: the one that keeps most wavefronts resident per CU under the 160 KiB LDS cap
     int bestB = 0, bestWaves = -1;
     size_t bestLds = 0;
@@ -680,17 +662,9 @@ int launch(lmpc_handle *h, int64_t nprob, const double *theta, double *x, int32_
     // unconstrained optimum is feasible, everything else is queued with its mask)
     const bool screened = will_screen(h, nprob);
     static_assert((kShards & (kShards - 1)) == 0, "the screening kernel masks the shard index");
-    if (screened) {
-        const int rc0 = ensure_lists(h, nprob, st);
-        if (rc0 != LMPC_OK) return rc0;
-    }
-    EventTriple ev{};
-    if (h->prof) {
-        HIP_TRY(h, pool_event(h, &ev.a));
-        HIP_TRY(h, pool_event(h, &ev.mid));
-        HIP_TRY(h, pool_event(h, &ev.b));
-        HIP_TRY(h, hipEventRecord(ev.a, st));
-    }
+    if (screened) LMPC_TRY(ensure_lists(h, nprob, st));
+    ProfBracket prof(h, st);
+    LMPC_TRY(prof.begin(h->prof));
     int rc = LMPC_OK;
     int ab_variant = 0, ab_measure = -1;          // (tiers pass on this path: measured like on the wavefront path)
     const bool sim = h->L.sim.FG != nullptr;      // closed-loop instantiations (SimFuse), lmpc_simulate* only
@@ -711,35 +685,22 @@ int launch(lmpc_handle *h, int64_t nprob, const double *theta, double *x, int32_
         // (an error word raised by an EARLIER call on this handle is reported here, before anything new is enqueued)
         rc = check_fast_err(h);
         if (rc == LMPC_OK) rc = launch_fast(h, nprob, theta, x, flag, iters, active, st);
-        if (h->prof) {       // one kernel: no event between "the two kernels" (each record is a packet the queue retires)
-            h->eventPool.push_back(ev.mid); ev.mid = nullptr;
-            if (rc == LMPC_OK) { HIP_TRY(h, hipEventRecord(ev.b, st)); h->events.push_back(ev); }
-            else { hipEventDestroy(ev.a); hipEventDestroy(ev.b); }
-        }
-        return rc;
+        prof.skip_mid();     // one kernel: no event between "the two kernels" (each record is a packet the queue retires)
+        return prof.end(rc);
     } else if (screened && !sim && !gather && warm == nullptr && x != nullptr && flag != nullptr && h->qpTiersOk &&
                h->qpTiers && h->P.ms < h->P.m && h->dCw != nullptr && h->S.iter_limit > h->P.n + 2 && h->asyncPhase == 0 &&
                (ab_variant = qp_ab_choose(h, nprob, st, &ab_measure)) == 0) {
         // general rows on the lane path: the tiers pass (lmpc_qp_tiers_kernel.hpp) instead of the screening pass -- it
         // finishes every append-only path, the lane kernel walks the rest
-        if (ab_measure >= 0) HIP_TRY(h, hipEventRecord(h->qpAbEv[ab_measure][0], st));
-        cnt_now = h->dCount + (size_t)h->countSet * kShards * kCountStride;
-        cnt_next = h->dCount + (size_t)(h->countSet ^ 1) * kShards * kCountStride;
-        h->countSet ^= 1;
+        LMPC_TRY(qp_ab_begin(h, ab_measure, st));
+        next_count_set(h, &cnt_now, &cnt_next);
         rc = launch_qp_tiers(h, nprob, theta, x, flag, iters, active, h->dList, cnt_now, lane_seg_cap(nprob), st, false);
     } else if (screened) {
-        if (ab_measure >= 0) HIP_TRY(h, hipEventRecord(h->qpAbEv[ab_measure][0], st));
-        cnt_now = h->dCount + (size_t)h->countSet * kShards * kCountStride;
-        cnt_next = h->dCount + (size_t)(h->countSet ^ 1) * kShards * kCountStride;
-        h->countSet ^= 1;
-#define LMPC_SCR(NM, NT) (sim ? launch_screen<NM, NT, 1>(h, nprob, theta, x, flag, iters, active, warm, cnt_now, st) \
-                         : gather ? launch_screen<NM, NT, 2>(h, nprob, theta, x, flag, iters, active, warm, cnt_now, st) \
-                         : wide ? launch_screen<NM, NT, 3>(h, nprob, theta, x, flag, iters, active, warm, cnt_now, st) \
-                                : launch_screen<NM, NT, 0>(h, nprob, theta, x, flag, iters, active, warm, cnt_now, st))
-        LMPC_SCREEN_SWITCH(LMPC_SCR)
-#undef LMPC_SCR
+        LMPC_TRY(qp_ab_begin(h, ab_measure, st));
+        next_count_set(h, &cnt_now, &cnt_next);
+        rc = launch_screen_any(h, sim ? 1 : (gather ? 2 : (wide ? 3 : 0)), nprob, theta, x, flag, iters, active, warm, cnt_now, st);
     }
-    if (h->prof) HIP_TRY(h, hipEventRecord(ev.mid, st));
+    LMPC_TRY(prof.mid());
     const int32_t *list = screened ? (h->asyncPhase == 2 ? h->asyncListOut : h->dList) : nullptr;
     const int32_t *count = cnt_now;
     // problems whose constraints are exactly the n simple bounds (ms == m == n == N) get the
@@ -755,15 +716,19 @@ int launch(lmpc_handle *h, int64_t nprob, const double *theta, double *x, int32_
 #undef LMPC_LN
         default: rc = fail(h, LMPC_ERR_UNSUPPORTED, "lmpc: no kernel instantiation"); break;
     }
-    if (ab_measure >= 0 && rc == LMPC_OK) {
-        HIP_TRY(h, hipEventRecord(h->qpAbEv[ab_measure][1], st));
-        h->qpAbN[ab_measure] = nprob; h->qpAbPending[ab_measure] = true;
+    return prof.end(qp_ab_end(h, ab_measure, rc, nprob, st));
+}
+
+int launch(lmpc_handle *h, int64_t nprob, const double *theta, double *x, int32_t *flag,
+           int32_t *iters, uint64_t *active, const uint64_t *warm, hipStream_t st) {
+    if (h->avi) {
+        // non-symmetric H (variational objective): its own kernel; timing events around the one launch
+        ProfBracket prof(h, st);
+        LMPC_TRY(prof.begin(h->prof, false));
+        return prof.end(launch_avi(h, nprob, theta, x, flag, iters, active, warm, st));
     }
-    if (h->prof) {
-        if (rc == LMPC_OK) { HIP_TRY(h, hipEventRecord(ev.b, st)); h->events.push_back(ev); }
-        else { hipEventDestroy(ev.a); hipEventDestroy(ev.mid); hipEventDestroy(ev.b); }
-    }
-    return rc;
+    return h->useWave ? launch_on_wave(h, nprob, theta, x, flag, iters, active, warm, st)
+                      : launch_on_lanes(h, nprob, theta, x, flag, iters, active, warm, st);
 }
 
 // scratch of the closed-loop entry points (binary64-sized; the binary32 loop uses the same buffers)
@@ -795,7 +760,7 @@ bool api_wave_screens(const lmpc_handle *h, int64_t nprob) { return wave_screens
 int api_wave_probe(lmpc_handle *h, const double *theta, int64_t nprob, hipStream_t st) { return wave_probe(h, theta, nprob, st); }
 int api_launch_wave_f32(lmpc_handle *h, const float *dC, int64_t nprob, const float *theta, float *x, int32_t *flag, int32_t *iters,
                         uint64_t *active, const uint64_t *warm, hipStream_t st) {
-    return launch_wave_t<float>(h, dC, nprob, theta, x, flag, iters, active, warm, st);
+    return launch_wave_t<float>(h, wave_args(h), dC, nprob, theta, x, flag, iters, active, warm, st);
 }
 }  // namespace lmpc
 
@@ -834,10 +799,10 @@ static void preload_code(lmpc_handle *h) {
             (void)launch_qp_tiers(h, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, true);
         if (h->dCw && h->useWave) {
             h->preloadOnly = true;
-            (void)launch_wave(h, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+            (void)launch_wave(h, wave_args(h), 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
             // (hybrid problems are the ones solved in binary32 too -- lmpc_solve_batch_f32*: that unit and its pack as well)
             if (h->bnb && ensure_f32(h) == LMPC_OK)
-                (void)launch_wave_t<float>(h, h->dCwf, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+                (void)launch_wave_t<float>(h, wave_args(h), h->dCwf, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
             h->preloadOnly = false;
         }
     }
@@ -1075,7 +1040,7 @@ int lmpc_solve_batch_f32_device(lmpc_handle *h, int64_t N, const float *theta, f
     LMPC_ENTER_DEVICE(h);
     int rc = ensure_f32(h);
     if (rc != LMPC_OK) return rc;
-    return launch_wave_t<float>(h, h->dCwf, N, theta, x, exitflag, iters, active, warm, (hipStream_t)stream);
+    return launch_wave_t<float>(h, wave_args(h), h->dCwf, N, theta, x, exitflag, iters, active, warm, (hipStream_t)stream);
 }
 
 // ONE theta, as the reference's online call has it (utils.jl:268-283; compute_control in a Simulation loop): no staging
@@ -1315,10 +1280,9 @@ int lmpc_reserve(lmpc_handle *h, int64_t N, void *stream) {
         if (hipMalloc(&pf, sizeof(int32_t) * 4) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(pt); return LMPC_OK; }
         int rc = LMPC_OK;
         if (hipMemsetAsync(pt, 0, sizeof(double) * nr, st) == hipSuccess) {
-            const bool prof = h->prof, probe = h->waveProbe;
-            h->prof = false; h->waveProbe = false;             // (not a batch: no events, no probe)
-            rc = launch_wave(h, 1, pt, pt + h->P.nth, pf, nullptr, nullptr, nullptr, st);
-            h->prof = prof; h->waveProbe = probe;
+            const Restore<bool> noProf(h->prof, false);        // (not a batch: no events, no probe)
+            const Restore<int> noProbe(h->waveProbe, 0);
+            rc = launch_wave(h, wave_args(h), 1, pt, pt + h->P.nth, pf, nullptr, nullptr, nullptr, st);
             (void)hipStreamSynchronize(st);
         }
         (void)hipGetLastError();

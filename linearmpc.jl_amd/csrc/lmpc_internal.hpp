@@ -63,13 +63,11 @@ struct lmpc_handle {
     bool bnb = false;           // rows flagged BINARY: branch and bound in the wavefront kernel
     int waveCap = 0;            // tuning: wavefronts per CU for the wave kernel's grid (0 = 16)
     bool waveQueue = true;      // tuning: dynamic problem queue of the wave kernel (0 = static split)
-    lmpc::WaveList waveList{};  // set around a launch that follows the screening pass
     lmpc::WaveSim waveSim{};    // scenario-asynchronous closed loop on the wavefront path (kstep == nullptr: off)
     int screenWave = 1;         // tuning: screening pass in front of the wavefront kernel where it applies ("screen_wave")
     bool screenPackOnly = false;   // the lane-style pack holds only what the screening pass reads (wave-only problem)
     int32_t *dQueue = nullptr;
     int waveOvfSet = 0;         // ... and which pair of overflow counters this CALL uses
-    int wavePass = 0;           // set by launch_wave_inst around its launches: 0 one pass, 1 / 2 first / second of two
     int waveTwoPass = -1;       // option "wave_two_pass": -1 auto, 0 off, 1 whenever the capacity allows
     int waveCap1 = 24;          // option "wave_cap1": working-set capacity of the first pass when "wave_two_pass" is 1
     int32_t *dOvfList1 = nullptr;
@@ -236,7 +234,6 @@ extern thread_local std::string g_setup_err;
 
 namespace lmpc {
 
-hipError_t pool_event(lmpc_handle *h, hipEvent_t *e);
 int fail(lmpc_handle *h, int code, const std::string &msg);
 // the one-launch kernel's error word (lmpc_fast_inst.hip): LMPC_OK, or LMPC_ERR_HIP once per raised error
 int check_fast_err(lmpc_handle *h);
@@ -247,6 +244,80 @@ int check_fast_err(lmpc_handle *h);
         if (e__ != hipSuccess)                                                               \
             return lmpc::fail(h, LMPC_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
     } while (0)
+
+#define LMPC_TRY(call) do { const int rct__ = (call); if (rct__ != LMPC_OK) return rct__; } while (0)
+
+// a handle field set for a scope and put back on every way out of it
+template <class T>
+struct Restore {
+    T &ref;
+    const T old;
+    Restore(T &r, const T &tmp) : ref(r), old(r) { r = tmp; }
+    Restore(const Restore &) = delete;
+    Restore &operator=(const Restore &) = delete;
+    ~Restore() { ref = old; }
+};
+
+// Profiling bracket of one call: three pooled events on the launch stream -- begin, mid (between a front pass and the
+// iterating kernel), end.  end() hands a call that succeeded to h->events (lmpc_profile_read); on every other way out,
+// an early return included, the events are given back.  Nothing is created or recorded while profiling is off.
+hipError_t pool_event(lmpc_handle *h, hipEvent_t *e);
+struct ProfBracket {
+    lmpc_handle *const h;
+    const hipStream_t st;
+    EventTriple ev{nullptr, nullptr, nullptr};
+    bool on = false;
+    ProfBracket(lmpc_handle *h_, hipStream_t st_) : h(h_), st(st_) {}
+    ProfBracket(const ProfBracket &) = delete;
+    ProfBracket &operator=(const ProfBracket &) = delete;
+    ~ProfBracket() { drop(); }
+    // with_mid false: a call of one launch from the start (no middle event is taken)
+    int begin(bool enable, bool with_mid = true) {
+        if (!enable) return LMPC_OK;
+        on = true;
+        HIP_TRY(h, pool_event(h, &ev.a));
+        if (with_mid) HIP_TRY(h, pool_event(h, &ev.mid));
+        HIP_TRY(h, pool_event(h, &ev.b));
+        HIP_TRY(h, hipEventRecord(ev.a, st));
+        return LMPC_OK;
+    }
+    int mid() {
+        if (on && ev.mid) HIP_TRY(h, hipEventRecord(ev.mid, st));
+        return LMPC_OK;
+    }
+    // the call turned out to be one launch: the middle event goes back unrecorded
+    void skip_mid() {
+        if (on && ev.mid) { h->eventPool.push_back(ev.mid); ev.mid = nullptr; }
+    }
+    int end(int rc) {
+        if (on && rc == LMPC_OK) {
+            HIP_TRY(h, hipEventRecord(ev.b, st));
+            h->events.push_back(ev);
+            on = false;
+        }
+        return rc;
+    }
+    void drop() {
+        if (!on) return;
+        for (hipEvent_t e : {ev.a, ev.mid, ev.b}) if (e) (void)hipEventDestroy(e);
+        on = false;
+    }
+};
+
+// What one launch on the wavefront path (wavefront kernel or row kernel) is told by its caller, down the chain
+// launch_wave -> launch_wave_t -> launch_wave_inst -> launch_wave_cfg and launch_row* -> launch_row_shape.
+struct WaveArgs {
+    int pass = 0;               // 0: the only pass; 1: first of two (smaller capacity); 2: second (walks the first one's overflow list)
+    WaveList list{};            // work list of a front pass (list == nullptr: the whole batch)
+    int cap = 0;                // working-set capacity of this launch (the kernel's ldc = cap | 1)
+    int level = -1, nwv = 0;    // preferred LDS staging level (-1 = automatic) and wavefronts per workgroup (0 = automatic)
+};
+// ... of a launch at the handle's own capacity and tuning ("wave_cap", "wave_level", "wave_nwv")
+inline WaveArgs wave_args(const lmpc_handle *h, const WaveList &list = WaveList{}) {
+    WaveArgs a;
+    a.list = list; a.cap = h->W.cap; a.level = h->waveLevel; a.nwv = h->waveNwv;
+    return a;
+}
 
 // LMPC_OK, or LMPC_ERR_NOGPU with the library's one text for it; `count`: the number of devices, for the callers that
 // go on to check an ordinal (h == nullptr: the text goes where a failed setup's does)
@@ -363,6 +434,13 @@ int launch_fast_multi(lmpc_handle *h, int nb, int64_t nprob, const double *const
 int wave_first_pass_cap(lmpc_handle *h, int64_t nprob);
 void wave_stat_read(const lmpc_handle *h, unsigned long long out[4]);
 int wave_reserve(lmpc_handle *h, int64_t nprob, hipStream_t st);
+// the wavefront path's lazily allocated scratch (defined once, next to wave_reserve; each does nothing where its
+// buffer is in place and large enough): ticket and overflow counters, working-set statistics with their mapped host
+// copy, the first pass's overflow list, the slow path's list with its per-thread scratch
+int wave_scratch_counters(lmpc_handle *h, hipStream_t st);
+int wave_scratch_stats(lmpc_handle *h, hipStream_t st);
+int wave_scratch_list1(lmpc_handle *h, int64_t nprob);
+int wave_scratch_slow(lmpc_handle *h, int64_t nprob);
 
 // lmpc_api.hip's launch policy and scratch for the second API unit (lmpc_api_loop.hip); that unit's code preload
 int api_launch(lmpc_handle *h, int64_t nprob, const double *theta, double *x, int32_t *flag, int32_t *iters, uint64_t *active,
@@ -379,33 +457,34 @@ void scenario_preload();
 void offset_free_preload();
 
 // four problems per wavefront (lmpc_row_inst.hip): capacity the batch would run at on that kernel (0: it does not take
-// the batch), and its launch as the only pass (pass 0) or the first of two (pass 1) of a wavefront-kernel call
+// the batch), and its launch as the only pass (a.pass 0) or the first of two (a.pass 1) of a wavefront-kernel call at
+// a.cap rows
 int row_pass_cap(lmpc_handle *h, int64_t nprob, size_t rs, bool warm, bool gram, bool bnb);
 template <typename R>
-int launch_row(lmpc_handle *h, const R *dC, int64_t nprob, const R *theta, R *x, int32_t *flag, int32_t *iters,
-               uint64_t *active, hipStream_t st, int cap, int pass);
-extern template int launch_row<double>(lmpc_handle *, const double *, int64_t, const double *, double *, int32_t *, int32_t *,
-                                       uint64_t *, hipStream_t, int, int);
-extern template int launch_row<float>(lmpc_handle *, const float *, int64_t, const float *, float *, int32_t *, int32_t *,
-                                      uint64_t *, hipStream_t, int, int);
+int launch_row(lmpc_handle *h, const WaveArgs &a, const R *dC, int64_t nprob, const R *theta, R *x, int32_t *flag,
+               int32_t *iters, uint64_t *active, hipStream_t st);
+extern template int launch_row<double>(lmpc_handle *, const WaveArgs &, const double *, int64_t, const double *, double *, int32_t *,
+                                       int32_t *, uint64_t *, hipStream_t);
+extern template int launch_row<float>(lmpc_handle *, const WaveArgs &, const float *, int64_t, const float *, float *, int32_t *,
+                                      int32_t *, uint64_t *, hipStream_t);
 // ... with branch and bound
 int row_bnb_pass_cap(lmpc_handle *h, int64_t nprob, size_t rs);
 template <typename R>
-int launch_row_bnb(lmpc_handle *h, const R *dC, int64_t nprob, const R *theta, R *x, int32_t *flag, int32_t *iters,
-                   uint64_t *active, hipStream_t st, int cap, int pass);
-extern template int launch_row_bnb<float>(lmpc_handle *, const float *, int64_t, const float *, float *, int32_t *, int32_t *,
-                                          uint64_t *, hipStream_t, int, int);
-extern template int launch_row_bnb<double>(lmpc_handle *, const double *, int64_t, const double *, double *, int32_t *, int32_t *,
-                                           uint64_t *, hipStream_t, int, int);
+int launch_row_bnb(lmpc_handle *h, const WaveArgs &a, const R *dC, int64_t nprob, const R *theta, R *x, int32_t *flag,
+                   int32_t *iters, uint64_t *active, hipStream_t st);
+extern template int launch_row_bnb<float>(lmpc_handle *, const WaveArgs &, const float *, int64_t, const float *, float *, int32_t *,
+                                          int32_t *, uint64_t *, hipStream_t);
+extern template int launch_row_bnb<double>(lmpc_handle *, const WaveArgs &, const double *, int64_t, const double *, double *, int32_t *,
+                                           int32_t *, uint64_t *, hipStream_t);
 
 // launch of the wavefront kernel for one batch (defined in lmpc_wave_launch.hpp, instantiated once per
 // (R, BNB) in lmpc_wave_inst.hip)
 template <typename R, bool BNB, bool GRAM, bool SIM = true>
-int launch_wave_inst(lmpc_handle *h, const R *dC, int64_t nprob, const R *theta, R *x, int32_t *flag,
+int launch_wave_inst(lmpc_handle *h, const WaveArgs &a, const R *dC, int64_t nprob, const R *theta, R *x, int32_t *flag,
                      int32_t *iters, uint64_t *active, const uint64_t *warm, hipStream_t st);
-#define LMPC_WAVE_EXTERN4(R, B, G, S)                                                                              \
-    extern template int launch_wave_inst<R, B, G, S>(lmpc_handle *, const R *, int64_t, const R *, R *, int32_t *, \
-                                                     int32_t *, uint64_t *, const uint64_t *, hipStream_t);
+#define LMPC_WAVE_EXTERN4(R, B, G, S)                                                                                \
+    extern template int launch_wave_inst<R, B, G, S>(lmpc_handle *, const WaveArgs &, const R *, int64_t, const R *, R *, \
+                                                     int32_t *, int32_t *, uint64_t *, const uint64_t *, hipStream_t);
 #define LMPC_WAVE_EXTERN(R, B, G) LMPC_WAVE_EXTERN4(R, B, G, true)
 LMPC_WAVE_EXTERN(double, false, false) LMPC_WAVE_EXTERN(double, true, false)
 LMPC_WAVE_EXTERN(float, false, false) LMPC_WAVE_EXTERN(float, true, false)

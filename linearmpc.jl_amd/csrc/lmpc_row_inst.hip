@@ -79,8 +79,9 @@ bool row_launch_for(const lmpc_handle *h, int cap, size_t rs, RowLaunch *out, bo
 }
 
 template <typename R, int S, int NS, int MS, int CAPP, bool BNB = false>
-int launch_row_shape(lmpc_handle *h, const RowLaunch &rl, const R *dC, int64_t nprob, const R *theta, R *x, int32_t *flag,
-                     int32_t *iters, uint64_t *active, hipStream_t st, int cap, int pass) {
+int launch_row_shape(lmpc_handle *h, const WaveArgs &a, const RowLaunch &rl, const R *dC, int64_t nprob, const R *theta, R *x,
+                     int32_t *flag, int32_t *iters, uint64_t *active, hipStream_t st) {
+    const int cap = a.cap, pass = a.pass;
     auto kern = row_kernel<R, S, NS, MS, CAPP, BNB>;
     if (rl.lds > 48 * 1024)
         HIP_TRY(h, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rl.lds));
@@ -121,15 +122,9 @@ int launch_row_shape(lmpc_handle *h, const RowLaunch &rl, const R *dC, int64_t n
         bnbR = static_cast<R *>(h->dRowBnb);
         bnbI = reinterpret_cast<int32_t *>(static_cast<char *>(h->dRowBnb) + sizeof(R) * nrowsB * bdepth * (size_t)row_snap_reals(S, CAPP));
     }
-    // counters: the protocol of launch_wave_cfg (two alternating sets, each launch clears the next one's)
+    // counters: the wavefront kernel's own (launch_wave_cfg: two alternating sets, each launch clears the next one's)
     constexpr int kP1 = kShards * kCountStride;
-    if (!h->dQueue) {
-        if (!h->dOvfCount) HIP_TRY(h, hipMalloc(&h->dOvfCount, sizeof(int32_t) * (2 * kP1 + 64)));
-        HIP_TRY(h, hipMemsetAsync(h->dOvfCount, 0, sizeof(int32_t) * (2 * kP1 + 64), st));
-        HIP_TRY(h, hipMalloc(&h->dQueue, 64));
-        HIP_TRY(h, hipMemsetAsync(h->dQueue, 0, 64, st));
-        h->waveCtrSet = 0; h->waveOvfSet = 0;
-    }
+    LMPC_TRY(wave_scratch_counters(h, st));
     const int os = h->waveOvfSet;
     int32_t *const p1Count = h->dOvfCount + os * kP1, *const p1Next = h->dOvfCount + (os ^ 1) * kP1;
     int32_t *const p2Next = h->dOvfCount + 2 * kP1 + 8 * (os ^ 1);
@@ -137,28 +132,16 @@ int launch_row_shape(lmpc_handle *h, const RowLaunch &rl, const R *dC, int64_t n
     int32_t *queue = nullptr;
     int qchunk = 1;
     const long long nrows = grid * rl.nwv * 4;
-    if (h->waveList.list != nullptr) {
+    const WaveList &wl = a.list;
+    if (wl.list != nullptr) {
         queue = h->dQueue + 8 * h->waveCtrSet;
     } else if (nprob > 2 * nrows && h->waveQueue) {
         const long long q = nprob / (32 * nrows);
         qchunk = q < 1 ? 1 : (q > 16 ? 16 : (int)q);
         queue = h->dQueue + 8 * h->waveCtrSet;
     }
-    if (pass == 1 && nprob > h->ovfCap1) {
-        hipFree(h->dOvfList1); h->dOvfList1 = nullptr; h->ovfCap1 = 0;
-        HIP_TRY(h, hipMalloc(&h->dOvfList1, sizeof(int32_t) * (size_t)nprob));
-        h->ovfCap1 = nprob;
-    }
-    if (!BNB && !h->hStat) {
-        unsigned long long *hp = nullptr;
-        HIP_TRY(h, hipHostMalloc(reinterpret_cast<void **>(&hp), 64, hipHostMallocMapped));
-        for (int q = 0; q < 8; q++) hp[q] = 0ull;
-        h->hStat = hp;
-        HIP_TRY(h, hipHostGetDevicePointer(reinterpret_cast<void **>(&h->dStatHost), hp, 0));
-        HIP_TRY(h, hipMalloc(&h->dStat, sizeof(unsigned long long) * 64 * 16));
-        HIP_TRY(h, hipMemsetAsync(h->dStat, 0, sizeof(unsigned long long) * 64 * 16, st));
-    }
-    const WaveList &wl = h->waveList;
+    if (pass == 1) LMPC_TRY(wave_scratch_list1(h, nprob));
+    if (!BNB) LMPC_TRY(wave_scratch_stats(h, st));
     RowParams<R> prm{};
     prm.P = Wl; prm.C = dC; prm.Sg = h->dSw; prm.theta = theta; prm.X = x; prm.exitflag = flag; prm.iters = iters;
     prm.active = active; prm.queue = queue; prm.qchunk = qchunk; prm.ps = rl.ps; prm.nprob = (long long)nprob;
@@ -255,11 +238,11 @@ int row_bnb_pass_cap(lmpc_handle *h, int64_t nprob, size_t rs) {
 #endif
 
 template <typename R>
-int launch_row(lmpc_handle *h, const R *dC, int64_t nprob, const R *theta, R *x, int32_t *flag, int32_t *iters,
-               uint64_t *active, hipStream_t st, int cap, int pass) {
+int launch_row(lmpc_handle *h, const WaveArgs &a, const R *dC, int64_t nprob, const R *theta, R *x, int32_t *flag,
+               int32_t *iters, uint64_t *active, hipStream_t st) {
     RowLaunch rl;
-    if (!row_launch_for(h, cap, sizeof(R), &rl)) return fail(h, LMPC_ERR_UNSUPPORTED, "lmpc: no row-kernel instantiation");
-#define LMPC_ROW(S_, NS_, MS_, CAPP_) launch_row_shape<R, S_, NS_, MS_, CAPP_>(h, rl, dC, nprob, theta, x, flag, iters, active, st, cap, pass)
+    if (!row_launch_for(h, a.cap, sizeof(R), &rl)) return fail(h, LMPC_ERR_UNSUPPORTED, "lmpc: no row-kernel instantiation");
+#define LMPC_ROW(S_, NS_, MS_, CAPP_) launch_row_shape<R, S_, NS_, MS_, CAPP_>(h, a, rl, dC, nprob, theta, x, flag, iters, active, st)
     switch (rl.shape) {
         case 0: return LMPC_ROW(1, 1, 4, 16);
         case 1: return LMPC_ROW(2, 2, 6, 31);
@@ -273,19 +256,19 @@ int launch_row(lmpc_handle *h, const R *dC, int64_t nprob, const R *theta, R *x,
 
 #ifdef LMPC_ROW_BNB
 template <typename R>
-int launch_row_bnb(lmpc_handle *h, const R *dC, int64_t nprob, const R *theta, R *x, int32_t *flag, int32_t *iters,
-                   uint64_t *active, hipStream_t st, int cap, int pass) {
+int launch_row_bnb(lmpc_handle *h, const WaveArgs &a, const R *dC, int64_t nprob, const R *theta, R *x, int32_t *flag,
+                   int32_t *iters, uint64_t *active, hipStream_t st) {
     RowLaunch rl;
-    if (!row_launch_for(h, cap, sizeof(R), &rl, true)) return fail(h, LMPC_ERR_UNSUPPORTED, "lmpc: no row-kernel instantiation");
-    if (rl.shape == 0) return launch_row_shape<R, 1, 1, 2, 16, true>(h, rl, dC, nprob, theta, x, flag, iters, active, st, cap, pass);
-    if (rl.shape == 1) return launch_row_shape<R, 3, 4, 4, 44, true>(h, rl, dC, nprob, theta, x, flag, iters, active, st, cap, pass);
-    return launch_row_shape<R, 3, 4, 4, 48, true>(h, rl, dC, nprob, theta, x, flag, iters, active, st, cap, pass);
+    if (!row_launch_for(h, a.cap, sizeof(R), &rl, true)) return fail(h, LMPC_ERR_UNSUPPORTED, "lmpc: no row-kernel instantiation");
+    if (rl.shape == 0) return launch_row_shape<R, 1, 1, 2, 16, true>(h, a, rl, dC, nprob, theta, x, flag, iters, active, st);
+    if (rl.shape == 1) return launch_row_shape<R, 3, 4, 4, 44, true>(h, a, rl, dC, nprob, theta, x, flag, iters, active, st);
+    return launch_row_shape<R, 3, 4, 4, 48, true>(h, a, rl, dC, nprob, theta, x, flag, iters, active, st);
 }
-template int launch_row_bnb<LMPC_ROW_REAL>(lmpc_handle *, const LMPC_ROW_REAL *, int64_t, const LMPC_ROW_REAL *, LMPC_ROW_REAL *, int32_t *,
-                                           int32_t *, uint64_t *, hipStream_t, int, int);
+template int launch_row_bnb<LMPC_ROW_REAL>(lmpc_handle *, const WaveArgs &, const LMPC_ROW_REAL *, int64_t, const LMPC_ROW_REAL *, LMPC_ROW_REAL *,
+                                           int32_t *, int32_t *, uint64_t *, hipStream_t);
 #else
-template int launch_row<LMPC_ROW_REAL>(lmpc_handle *, const LMPC_ROW_REAL *, int64_t, const LMPC_ROW_REAL *, LMPC_ROW_REAL *, int32_t *,
-                                       int32_t *, uint64_t *, hipStream_t, int, int);
+template int launch_row<LMPC_ROW_REAL>(lmpc_handle *, const WaveArgs &, const LMPC_ROW_REAL *, int64_t, const LMPC_ROW_REAL *, LMPC_ROW_REAL *,
+                                       int32_t *, int32_t *, uint64_t *, hipStream_t);
 #endif
 
 }  // namespace lmpc

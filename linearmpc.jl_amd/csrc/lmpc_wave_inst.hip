@@ -7,14 +7,63 @@ namespace lmpc {
 #ifndef LMPC_WV_SIM
 #define LMPC_WV_SIM 1
 #endif
-template int launch_wave_inst<LMPC_WV_REAL, (LMPC_WV_BNB != 0), (LMPC_WV_GRAM != 0), (LMPC_WV_SIM != 0)>(lmpc_handle *, const LMPC_WV_REAL *, int64_t,
-                                                                const LMPC_WV_REAL *, LMPC_WV_REAL *, int32_t *,
-                                                                int32_t *, uint64_t *, const uint64_t *, hipStream_t);
+template int launch_wave_inst<LMPC_WV_REAL, (LMPC_WV_BNB != 0), (LMPC_WV_GRAM != 0), (LMPC_WV_SIM != 0)>(lmpc_handle *, const WaveArgs &,
+                                                                const LMPC_WV_REAL *, int64_t, const LMPC_WV_REAL *, LMPC_WV_REAL *,
+                                                                int32_t *, int32_t *, uint64_t *, const uint64_t *, hipStream_t);
 #ifdef LMPC_WV_HELPERS
 // (one translation unit carries the launcher's non-template helpers the API file needs)
-int wave_first_pass_cap(lmpc_handle *h, int64_t nprob) { return wave_first_pass_cap_impl(h, nprob, sizeof(double)); }
+int wave_first_pass_cap(lmpc_handle *h, int64_t nprob) { return wave_first_pass_cap_impl(h, wave_args(h), nprob, sizeof(double)); }
 void wave_stat_read(const lmpc_handle *h, unsigned long long out[4]) { wave_stat_sums(h, out); }
 int wave_reserve(lmpc_handle *h, int64_t nprob, hipStream_t st) { return wave_reserve_impl(h, nprob, st); }
+
+// The ticket counter and the two sets of overflow counters (launch_wave_cfg describes their layout and protocol)
+int wave_scratch_counters(lmpc_handle *h, hipStream_t st) {
+    constexpr int kP1 = kShards * kCountStride;
+    if (h->dQueue) return LMPC_OK;
+    if (!h->dOvfCount) HIP_TRY(h, hipMalloc(&h->dOvfCount, sizeof(int32_t) * (2 * kP1 + 64)));
+    HIP_TRY(h, hipMemsetAsync(h->dOvfCount, 0, sizeof(int32_t) * (2 * kP1 + 64), st));
+    HIP_TRY(h, hipMalloc(&h->dQueue, 64));
+    HIP_TRY(h, hipMemsetAsync(h->dQueue, 0, 64, st));
+    h->waveCtrSet = 0; h->waveOvfSet = 0;
+    return LMPC_OK;
+}
+
+// working-set statistics: device counters + their mapped host copy
+int wave_scratch_stats(lmpc_handle *h, hipStream_t st) {
+    if (h->hStat) return LMPC_OK;
+    unsigned long long *hp = nullptr;
+    HIP_TRY(h, hipHostMalloc(reinterpret_cast<void **>(&hp), 64, hipHostMallocMapped));
+    for (int q = 0; q < 8; q++) hp[q] = 0ull;
+    h->hStat = hp;
+    HIP_TRY(h, hipHostGetDevicePointer(reinterpret_cast<void **>(&h->dStatHost), hp, 0));
+    HIP_TRY(h, hipMalloc(&h->dStat, sizeof(unsigned long long) * 64 * 16));
+    HIP_TRY(h, hipMemsetAsync(h->dStat, 0, sizeof(unsigned long long) * 64 * 16, st));
+    return LMPC_OK;
+}
+
+// the list of the points that outgrow a first pass
+int wave_scratch_list1(lmpc_handle *h, int64_t nprob) {
+    if (nprob <= h->ovfCap1) return LMPC_OK;
+    hipFree(h->dOvfList1); h->dOvfList1 = nullptr; h->ovfCap1 = 0;
+    HIP_TRY(h, hipMalloc(&h->dOvfList1, sizeof(int32_t) * (size_t)nprob));
+    h->ovfCap1 = nprob;
+    return LMPC_OK;
+}
+
+// the slow path's list and its per-thread scratch (sized for binary64: the binary32 calls of the handle use the same slices)
+int wave_scratch_slow(lmpc_handle *h, int64_t nprob) {
+    if (nprob > h->ovfCap) {
+        hipFree(h->dOvfList); h->dOvfList = nullptr; h->ovfCap = 0;
+        HIP_TRY(h, hipMalloc(&h->dOvfList, sizeof(int32_t) * (size_t)nprob));
+        h->ovfCap = nprob;
+    }
+    if (!h->dBigR) {
+        const int bigCap = h->capFull < kBigCap ? h->capFull : kBigCap;
+        HIP_TRY(h, hipMalloc(&h->dBigR, sizeof(double) * (size_t)kBigThreads * (size_t)big_scratch_reals(h->W.n, h->W.m, bigCap)));
+        HIP_TRY(h, hipMalloc(&h->dBigI, sizeof(int32_t) * (size_t)kBigThreads * (size_t)big_scratch_ints(h->W.m, bigCap)));
+    }
+    return LMPC_OK;
+}
 #endif
 }  // namespace lmpc
 

@@ -51,11 +51,10 @@ inline int wave_max_resident(int slots, bool bnb, size_t rs, int level, int nu, 
 // mass-spring: 16 waves with only M' staged 1.23e7/s, 8 waves with everything staged 0.85e7/s), and
 // at equal residency small workgroups win.  So: most wavefronts per CU first, then the highest
 // staging level that reaches it, then the smallest workgroup.
-inline WaveConfig wave_config_for(const lmpc_handle *h, size_t rs, bool packed) {
-    const WaveLayout &Wl = h->W;
+inline WaveConfig wave_config_for(const lmpc_handle *h, const WaveArgs &a, size_t rs, bool packed) {
     // per-wave factor L: square with an odd leading dimension, or packed strict lower triangle
     // (+ 64 reals: the multipliers, read back as LDS broadcasts)
-    const size_t perWave = rs * ((packed ? ((size_t)Wl.cap * (Wl.cap - 1) / 2) : ((size_t)Wl.cap * Wl.ldc)) + 64);
+    const size_t perWave = rs * ((packed ? ((size_t)a.cap * (a.cap - 1) / 2) : ((size_t)a.cap * (a.cap | 1))) + 64);
     // instantiations with many constraint slots or the B&B state are built for 512-thread workgroups
     // (more registers per lane, fewer resident wavefronts)
     const int slots = wave_slots(h->P.m, h->bnb);
@@ -66,11 +65,11 @@ inline WaveConfig wave_config_for(const lmpc_handle *h, size_t rs, bool packed) 
     // (packed, the 3 / 5 / 6-slot instantiations and everything beyond 256 rows are built for levels 0 and 1 only)
     const bool twoLevels = packed || h->P.m > 256 || slots == 3 || h->waveGram;
     for (int level = h->P.n > 64 ? 0 : (twoLevels ? 1 : 3); level >= 0; level--) {
-        if (h->waveLevel >= 0 && level != (twoLevels && h->waveLevel > 1 ? 1 : h->waveLevel)) continue;
+        if (a.level >= 0 && level != (twoLevels && a.level > 1 ? 1 : a.level)) continue;
         const int maxWaves = wave_max_resident(slots, h->bnb, rs, level, h->P.n > 64 ? 2 : 1, h->waveGram != 0);
         for (int nwv : {4, 8, 16, 12, 2, 1}) {
             if (nwv > maxNwv) continue;
-            if (h->waveNwv > 0 && nwv != h->waveNwv && !(h->waveNwv > maxNwv && nwv == maxNwv)) continue;
+            if (a.nwv > 0 && nwv != a.nwv && !(a.nwv > maxNwv && nwv == maxNwv)) continue;
             const size_t lds = perWave * nwv + wave_shared_bytes(h->P, level, rs, h->waveGram != 0);
             if (lds > kLdsMax) continue;
             int blocks = (int)(kLdsMax / lds);
@@ -87,8 +86,8 @@ inline WaveConfig wave_config_for(const lmpc_handle *h, size_t rs, bool packed) 
 // run on a zero-padded factor, three vector instructions per step instead of five, so it takes more than a quarter
 // more wavefronts to beat it -- hybrid f32, n = 60: 10 wavefronts per CU square 1.54e6/s, 16 packed 1.40e6/s; f64:
 // 5 square 6.9e5/s, 10 packed 8.4e5/s; the benchmark class at cap = 64: 4 square against 9 packed, packed 1.5x faster)
-inline WaveConfig wave_config(const lmpc_handle *h, size_t rs) {
-    const WaveConfig sq = wave_config_for(h, rs, false), pk = wave_config_for(h, rs, true);
+inline WaveConfig wave_config(const lmpc_handle *h, const WaveArgs &a, size_t rs) {
+    const WaveConfig sq = wave_config_for(h, a, rs, false), pk = wave_config_for(h, a, rs, true);
     if (h->wavePacked == 0) return sq;
     if (h->wavePacked == 1) return pk;
     // (round 4, branch and bound with lazy snapshots: the truncating restore and the zero-padded sweeps favour the square
@@ -122,9 +121,13 @@ inline void wave_stat_window(lmpc_handle *h, unsigned long long out[4]) {
     for (int q = 0; q < 4; q++) out[q] = cur[q] - h->statA[q];
 }
 
-// capacity of the first of two passes for a batch of nprob problems on this handle, 0 = one pass (see launch_wave_inst)
-inline int wave_first_pass_cap_impl(lmpc_handle *h, int64_t nprob, size_t rs) {
-    if (h->bnb || h->waveTwoPass == 0 || !h->bigPath || h->W.cap < 40 || nprob >= (int64_t)0x7fffffff) return 0;
+// a launch's arguments at another working-set capacity
+inline WaveArgs at_cap(WaveArgs a, int cap) { a.cap = cap; return a; }
+
+// capacity of the first of two passes for a batch of nprob problems that would run in one pass as `a` says, 0 = one
+// pass (see launch_wave_inst)
+inline int wave_first_pass_cap_impl(lmpc_handle *h, const WaveArgs &a, int64_t nprob, size_t rs) {
+    if (h->bnb || h->waveTwoPass == 0 || !h->bigPath || a.cap < 40 || nprob >= (int64_t)0x7fffffff) return 0;
     // run-ahead (closed loop, consecutive steps of a scenario on the factor in LDS), warm: a step that outgrows a first
     // pass restarts from the factor of the step before it -- which the first pass then has to write out after every
     // step (the kept-state buffers of the step-synchronous loop); without them, one pass
@@ -138,13 +141,9 @@ inline int wave_first_pass_cap_impl(lmpc_handle *h, int64_t nprob, size_t rs) {
         for (int q = 0; q < 3 && c1 == 0 && sum[0] >= 1000ull; q++)
             if ((sum[0] - sum[1 + q]) * 100ull <= 3ull * sum[0]) c1 = caps[q];
     }
-    if (c1 >= h->W.cap) c1 = 0;
+    if (c1 >= a.cap) c1 = 0;
     if (c1 > 0 && h->waveTwoPass < 0) {                   // only where the smaller factor buys residency, layout or staging
-        const WaveConfig full = wave_config(h, rs);
-        const int capW = h->W.cap, ldcW = h->W.ldc;
-        h->W.cap = c1; h->W.ldc = c1 | 1;
-        const WaveConfig t = wave_config(h, rs);
-        h->W.cap = capW; h->W.ldc = ldcW;
+        const WaveConfig full = wave_config(h, a, rs), t = wave_config(h, at_cap(a, c1), rs);
         // (a wavefront on the square factor counts 1.75 times one on the packed triangle: the weight wave_config itself
         // chooses the layout by -- N = 125 at 48 rows: 8 square against 8 packed, 10 % faster)
         const int st = t.nwv * t.blocksPerCU * (t.packed ? 4 : 7), sf = full.nwv * full.blocksPerCU * (full.packed ? 4 : 7);
@@ -160,43 +159,13 @@ inline int wave_first_pass_cap_impl(lmpc_handle *h, int64_t nprob, size_t rs) {
 // overflow counters, working-set statistics, the overflow lists of both passes, the slow path's scratch), allocated
 // now -- the launch paths then find it in place.  Branch-and-bound snapshots depend on the launch shape and stay lazy.
 inline int wave_reserve_impl(lmpc_handle *h, int64_t nprob, hipStream_t st) {
-    constexpr int kP1 = kShards * kCountStride;
-    if (!h->dQueue) {
-        if (!h->dOvfCount) HIP_TRY(h, hipMalloc(&h->dOvfCount, sizeof(int32_t) * (2 * kP1 + 64)));
-        HIP_TRY(h, hipMemsetAsync(h->dOvfCount, 0, sizeof(int32_t) * (2 * kP1 + 64), st));
-        HIP_TRY(h, hipMalloc(&h->dQueue, 64));
-        HIP_TRY(h, hipMemsetAsync(h->dQueue, 0, 64, st));
-        h->waveCtrSet = 0; h->waveOvfSet = 0;
-    }
+    LMPC_TRY(wave_scratch_counters(h, st));
     // (the first-pass list: a first pass may run on any handle since the row kernel takes batches of every size -- plain
     // solves as the first of two passes whenever the slow path lies behind its capacity, searches at 48 rows)
-    if (h->waveTwoPass != 0 && nprob < (int64_t)0x7fffffff && nprob > h->ovfCap1) {
-        hipFree(h->dOvfList1); h->dOvfList1 = nullptr; h->ovfCap1 = 0;
-        HIP_TRY(h, hipMalloc(&h->dOvfList1, sizeof(int32_t) * (size_t)nprob));
-        h->ovfCap1 = nprob;
-    }
+    if (h->waveTwoPass != 0 && nprob < (int64_t)0x7fffffff) LMPC_TRY(wave_scratch_list1(h, nprob));
     if (h->bnb || nprob >= (int64_t)0x7fffffff) return LMPC_OK;
-    if (!h->hStat) {
-        unsigned long long *hp = nullptr;
-        HIP_TRY(h, hipHostMalloc(reinterpret_cast<void **>(&hp), 64, hipHostMallocMapped));
-        for (int q = 0; q < 8; q++) hp[q] = 0ull;
-        h->hStat = hp;
-        HIP_TRY(h, hipHostGetDevicePointer(reinterpret_cast<void **>(&h->dStatHost), hp, 0));
-        HIP_TRY(h, hipMalloc(&h->dStat, sizeof(unsigned long long) * 64 * 16));
-        HIP_TRY(h, hipMemsetAsync(h->dStat, 0, sizeof(unsigned long long) * 64 * 16, st));
-    }
-    if (h->bigPath && h->capFull > h->W.cap) {                                            // the slow path may run
-        if (nprob > h->ovfCap) {
-            hipFree(h->dOvfList); h->dOvfList = nullptr; h->ovfCap = 0;
-            HIP_TRY(h, hipMalloc(&h->dOvfList, sizeof(int32_t) * (size_t)nprob));
-            h->ovfCap = nprob;
-        }
-        if (!h->dBigR) {
-            const int bigCap = h->capFull < kBigCap ? h->capFull : kBigCap;
-            HIP_TRY(h, hipMalloc(&h->dBigR, sizeof(double) * (size_t)kBigThreads * (size_t)big_scratch_reals(h->W.n, h->W.m, bigCap)));
-            HIP_TRY(h, hipMalloc(&h->dBigI, sizeof(int32_t) * (size_t)kBigThreads * (size_t)big_scratch_ints(h->W.m, bigCap)));
-        }
-    }
+    LMPC_TRY(wave_scratch_stats(h, st));
+    if (h->bigPath && h->capFull > h->W.cap) LMPC_TRY(wave_scratch_slow(h, nprob));     // the slow path may run
     return LMPC_OK;
 }
 
@@ -206,25 +175,22 @@ inline int wave_reserve_impl(lmpc_handle *h, int64_t nprob, hipStream_t st) {
 // rows that leaves eight rows beyond the binaries, IF that keeps more wavefronts resident; a point that outgrows it
 // (exit flag -7 inside the pass) is listed and searched again from scratch at the full capacity.  The search is
 // deterministic, so the result does not depend on the split.  "wave_two_pass" 0 switches it off.
-inline int bnb_first_pass_cap(lmpc_handle *h, int64_t nprob, size_t rs) {
+inline int bnb_first_pass_cap(lmpc_handle *h, const WaveArgs &a, int64_t nprob, size_t rs) {
     if (!h->bnb || h->waveTwoPass == 0 || nprob >= (int64_t)0x7fffffff || nprob < 4096) return 0;
     int c1 = 0;
     for (int c : {24, 32, 48})
         if (c1 == 0 && c >= h->nBinary + 8) c1 = c;
     if (h->waveTwoPass > 0 && h->waveCap1 > 0) c1 = h->waveCap1;
-    if (c1 == 0 || c1 + 4 > h->W.cap) return 0;
-    const WaveConfig full = wave_config(h, rs);
-    const int capW = h->W.cap, ldcW = h->W.ldc;
-    h->W.cap = c1; h->W.ldc = c1 | 1;
-    const WaveConfig t = wave_config(h, rs);
-    h->W.cap = capW; h->W.ldc = ldcW;
+    if (c1 == 0 || c1 + 4 > a.cap) return 0;
+    const WaveConfig full = wave_config(h, a, rs), t = wave_config(h, at_cap(a, c1), rs);
     return t.nwv * t.blocksPerCU > full.nwv * full.blocksPerCU ? c1 : 0;
 }
 
 template <typename R, int MR, int LDSC, bool BNB, bool PACKED, int NU = 1, bool GRAM = false, bool SIM = true>
-int launch_wave_cfg(lmpc_handle *h, const WaveConfig &cfg, const R *dC, int64_t nprob, const R *theta, R *x,
+int launch_wave_cfg(lmpc_handle *h, const WaveArgs &a, const WaveConfig &cfg, const R *dC, int64_t nprob, const R *theta, R *x,
                     int32_t *flag, int32_t *iters, uint64_t *active, const uint64_t *warm, hipStream_t st) {
-    const WaveLayout &Wl = h->W;                         // (work-list mode, screening pass in front: h->waveList, see launch())
+    WaveLayout Wl = h->W;                                // the handle's layout at this pass's capacity
+    Wl.cap = a.cap; Wl.ldc = a.cap | 1;
     // (SIM false: the instantiation without the closed-loop machinery -- the caller chose it for a plain batched solve)
     auto kern = wave_kernel<R, MR, LDSC, BNB, PACKED, NU, GRAM, SIM>;
     if (cfg.lds > 48 * 1024)
@@ -265,14 +231,8 @@ int launch_wave_cfg(lmpc_handle *h, const WaveConfig &cfg, const R *dC, int64_t 
     // shaped like a work list's counters (kShards words kCountStride apart, only word 0 ever non-zero), then the two
     // words of the last pass's overflow (the slow path's list).
     constexpr int kP1 = kShards * kCountStride;
-    if (!h->dQueue) {
-        if (!h->dOvfCount) HIP_TRY(h, hipMalloc(&h->dOvfCount, sizeof(int32_t) * (2 * kP1 + 64)));
-        HIP_TRY(h, hipMemsetAsync(h->dOvfCount, 0, sizeof(int32_t) * (2 * kP1 + 64), st));
-        HIP_TRY(h, hipMalloc(&h->dQueue, 64));
-        HIP_TRY(h, hipMemsetAsync(h->dQueue, 0, 64, st));
-        h->waveCtrSet = 0; h->waveOvfSet = 0;
-    }
-    const int pass = h->wavePass;                        // 0: the only pass; 1: first of two (smaller capacity); 2: second
+    LMPC_TRY(wave_scratch_counters(h, st));
+    const int pass = a.pass;
     const int os = h->waveOvfSet;
     int32_t *const p1Count = h->dOvfCount + os * kP1, *const p1Next = h->dOvfCount + (os ^ 1) * kP1;
     int32_t *const ovfCount = h->dOvfCount + 2 * kP1 + 8 * os, *const p2Next = h->dOvfCount + 2 * kP1 + 8 * (os ^ 1);
@@ -282,7 +242,7 @@ int launch_wave_cfg(lmpc_handle *h, const WaveConfig &cfg, const R *dC, int64_t 
     if (pass == 2) {                                     // the first pass's overflow list IS this pass's work list
         wl2.list = h->dOvfList1; wl2.count = p1Count; wl2.count_next = nullptr; wl2.seg_cap = (long long)nprob;
     }
-    const WaveList &wl = pass == 2 ? wl2 : h->waveList;
+    const WaveList &wl = pass == 2 ? wl2 : a.list;
     // more than two problems per resident wavefront: hand them out through the shared counter
     int32_t *queue = nullptr;
     int qchunk = 1;
@@ -299,31 +259,9 @@ int launch_wave_cfg(lmpc_handle *h, const WaveConfig &cfg, const R *dC, int64_t 
     // re-solved behind it, one problem per thread (no branch and bound there)
     const bool big = pass != 1 && !BNB && h->bigPath && h->capFull > Wl.cap && nprob < (int64_t)0x7fffffff;
     const int bigCap = h->capFull < kBigCap ? h->capFull : kBigCap;
-    if (pass == 1 && nprob > h->ovfCap1) {
-        hipFree(h->dOvfList1); h->dOvfList1 = nullptr; h->ovfCap1 = 0;
-        HIP_TRY(h, hipMalloc(&h->dOvfList1, sizeof(int32_t) * (size_t)nprob));
-        h->ovfCap1 = nprob;
-    }
-    if (!BNB && !h->hStat) {                             // working-set statistics: device counters + their mapped host copy
-        unsigned long long *hp = nullptr;
-        HIP_TRY(h, hipHostMalloc(reinterpret_cast<void **>(&hp), 64, hipHostMallocMapped));
-        for (int q = 0; q < 8; q++) hp[q] = 0ull;
-        h->hStat = hp;
-        HIP_TRY(h, hipHostGetDevicePointer(reinterpret_cast<void **>(&h->dStatHost), hp, 0));
-        HIP_TRY(h, hipMalloc(&h->dStat, sizeof(unsigned long long) * 64 * 16));
-        HIP_TRY(h, hipMemsetAsync(h->dStat, 0, sizeof(unsigned long long) * 64 * 16, st));
-    }
-    if (big) {
-        if (nprob > h->ovfCap) {
-            hipFree(h->dOvfList); h->dOvfList = nullptr; h->ovfCap = 0;
-            HIP_TRY(h, hipMalloc(&h->dOvfList, sizeof(int32_t) * (size_t)nprob));
-            h->ovfCap = nprob;
-        }
-        if (!h->dBigR) {     // sized for binary64: the binary32 calls of the handle use the same slices
-            HIP_TRY(h, hipMalloc(&h->dBigR, sizeof(double) * (size_t)kBigThreads * (size_t)big_scratch_reals(Wl.n, Wl.m, bigCap)));
-            HIP_TRY(h, hipMalloc(&h->dBigI, sizeof(int32_t) * (size_t)kBigThreads * (size_t)big_scratch_ints(Wl.m, bigCap)));
-        }
-    }
+    if (pass == 1) LMPC_TRY(wave_scratch_list1(h, nprob));
+    if (!BNB) LMPC_TRY(wave_scratch_stats(h, st));
+    if (big) LMPC_TRY(wave_scratch_slow(h, nprob));
     // branch and bound: room for one snapshot of a node's state per search depth and resident wavefront (sized for
     // binary64; the binary32 calls of the handle use the same slices)
     R *bnbR = nullptr;
@@ -373,18 +311,12 @@ int launch_wave_cfg(lmpc_handle *h, const WaveConfig &cfg, const R *dC, int64_t 
 }
 
 template <typename R, bool BNB, bool GRAM, bool SIM>
-int launch_wave_inst(lmpc_handle *h, const R *dC, int64_t nprob, const R *theta, R *x, int32_t *flag,
+int launch_wave_inst(lmpc_handle *h, const WaveArgs &a, const R *dC, int64_t nprob, const R *theta, R *x, int32_t *flag,
                      int32_t *iters, uint64_t *active, const uint64_t *warm, hipStream_t st) {
-    EventTriple ev{};
-    const bool prof = h->prof && h->waveList.list == nullptr && !h->preloadOnly;     // (behind the screening pass: launch_wave_screened's events)
-    if (prof) {
-        HIP_TRY(h, pool_event(h, &ev.a));
-        HIP_TRY(h, pool_event(h, &ev.mid));
-        HIP_TRY(h, pool_event(h, &ev.b));
-        HIP_TRY(h, hipEventRecord(ev.a, st));
-        HIP_TRY(h, hipEventRecord(ev.mid, st));
-    }
-    int rc;
+    // (behind a front pass the call's events are that pass's; no front pass here: begin and mid back to back)
+    ProfBracket prof(h, st);
+    LMPC_TRY(prof.begin(h->prof && a.list.list == nullptr && !h->preloadOnly));
+    LMPC_TRY(prof.mid());
     const int mr = wave_slots(h->P.m, BNB);
     if (BNB) warm = nullptr;                              // a B&B node takes its start from the search, not the caller
     // Two passes (no binaries): the factor of a 64-row working set takes 16-33 KB of LDS per wavefront, which is what
@@ -400,10 +332,11 @@ int launch_wave_inst(lmpc_handle *h, const R *dC, int64_t nprob, const R *theta,
     // launch configuration at that capacity is the better one (more wavefronts per CU or a higher staging level); one
     // pass until 1000 problems have been seen, for small batches, and if no capacity qualifies.
     // "wave_two_pass" 0 = never, 1 = always at "wave_cap1" rows (default 24), -1 (default) = as described.
-    WaveConfig cfg = wave_config(h, sizeof(R));
-    const int c1 = BNB ? bnb_first_pass_cap(h, nprob, sizeof(R)) : wave_first_pass_cap_impl(h, nprob, sizeof(R));
-    const int capW = h->W.cap, ldcW = h->W.ldc;
-    auto dispatch = [&]() -> int {
+    const int c1 = BNB ? bnb_first_pass_cap(h, a, nprob, sizeof(R)) : wave_first_pass_cap_impl(h, a, nprob, sizeof(R));
+    const int capW = a.cap;
+    // one launch of this kernel as `pa` says, at the launch configuration chosen for it
+    auto dispatch = [&](const WaveArgs &pa) -> int {
+    const WaveConfig cfg = wave_config(h, pa, sizeof(R));
     int rc;
     // long horizons (64 <= n <= 127): two variable slots per lane; built without LDS staging of the problem data
     // (M alone is up to 1 MB there) and without branch and bound
@@ -411,8 +344,8 @@ int launch_wave_inst(lmpc_handle *h, const R *dC, int64_t nprob, const R *theta,
         if constexpr (BNB) {
             rc = fail(h, LMPC_ERR_UNSUPPORTED, "lmpc: branch and bound covers n <= 64");
         } else {
-#define LMPC_WVU(MRR) (cfg.packed ? launch_wave_cfg<R, MRR, 0, false, true, 2, GRAM, SIM>(h, cfg, dC, nprob, theta, x, flag, iters, active, warm, st) \
-                                  : launch_wave_cfg<R, MRR, 0, false, false, 2, GRAM, SIM>(h, cfg, dC, nprob, theta, x, flag, iters, active, warm, st))
+#define LMPC_WVU(MRR) (cfg.packed ? launch_wave_cfg<R, MRR, 0, false, true, 2, GRAM, SIM>(h, pa, cfg, dC, nprob, theta, x, flag, iters, active, warm, st) \
+                                  : launch_wave_cfg<R, MRR, 0, false, false, 2, GRAM, SIM>(h, pa, cfg, dC, nprob, theta, x, flag, iters, active, warm, st))
             if (mr <= 2) rc = LMPC_WVU(2);
             else if (mr == 3) rc = LMPC_WVU(3);
             else if (mr == 4) rc = LMPC_WVU(4);
@@ -424,7 +357,7 @@ int launch_wave_inst(lmpc_handle *h, const R *dC, int64_t nprob, const R *theta,
         }
         return rc;
     }
-#define LMPC_WV4(MRR, LV, PK) launch_wave_cfg<R, MRR, LV, BNB, PK, 1, GRAM, SIM>(h, cfg, dC, nprob, theta, x, flag, iters, active, warm, st)
+#define LMPC_WV4(MRR, LV, PK) launch_wave_cfg<R, MRR, LV, BNB, PK, 1, GRAM, SIM>(h, pa, cfg, dC, nprob, theta, x, flag, iters, active, warm, st)
 #define LMPC_WV3(MRR, LV) LMPC_WV4(MRR, LV, false)
 #define LMPC_WV(MRR) (cfg.packed ? (cfg.level >= 1 ? LMPC_WV4(MRR, 1, true) : LMPC_WV4(MRR, 0, true)) \
                                  : (cfg.level >= 3 ? LMPC_WV3(MRR, 3) : (cfg.level == 2 ? LMPC_WV3(MRR, 2) : (cfg.level == 1 ? LMPC_WV3(MRR, 1) : LMPC_WV3(MRR, 0)))))
@@ -458,91 +391,57 @@ int launch_wave_inst(lmpc_handle *h, const R *dC, int64_t nprob, const R *theta,
 #undef LMPC_WV4
     return rc;
     };   // dispatch
-    if (h->preloadOnly) {
-        if constexpr (!BNB && !GRAM) {                        // (the row kernel's code object too, where a large batch would take it)
-            const int rcap = row_pass_cap(h, (int64_t)1 << 20, sizeof(R), false, GRAM, BNB);
-            if (rcap > 0) (void)launch_row<R>(h, dC, nprob, theta, x, flag, iters, active, st, rcap, 0);
-        }
-        if constexpr (BNB && !GRAM) {
-            const int rcap = row_bnb_pass_cap(h, (int64_t)1 << 20, sizeof(R));
-            if (rcap > 0) (void)launch_row_bnb<R>(h, dC, nprob, theta, x, flag, iters, active, st, rcap, 0);
-        }
-        return dispatch();
+    // Four problems per wavefront (lmpc_row_kernel.hpp) where it applies, in place of this kernel's own first pass
+    // (the search's row kernel for a handle with binaries)
+    auto row = [&](const WaveArgs &pa) -> int {
+        if constexpr (BNB) return launch_row_bnb<R>(h, pa, dC, nprob, theta, x, flag, iters, active, st);
+        else return launch_row<R>(h, pa, dC, nprob, theta, x, flag, iters, active, st);
+    };
+    auto row_cap = [&](int64_t np, bool warmStart) -> int {   // (0: the row kernel does not take the batch)
+        if constexpr (GRAM) return 0;
+        else if constexpr (BNB) return row_bnb_pass_cap(h, np, sizeof(R));
+        else return row_pass_cap(h, np, sizeof(R), warmStart, GRAM, BNB);
+    };
+    if (h->preloadOnly) {                                     // (the row kernel's code object too, where a large batch would take it)
+        const int rcap = row_cap((int64_t)1 << 20, false);
+        if (rcap > 0) (void)row(at_cap(a, rcap));
+        return dispatch(a);
     }
-    // Four problems per wavefront (lmpc_row_kernel.hpp) where it applies: as the only pass when its capacity holds every
-    // working set of the problem, else as the first of two passes in place of this kernel's own first pass.
-    if constexpr (!BNB && !GRAM) {
-        const int rcap = row_pass_cap(h, nprob, sizeof(R), warm != nullptr, GRAM, BNB);
-        if (rcap > 0) {
-            // (as the only pass where nothing lies behind its capacity; else what outgrows it is listed: for this kernel's
-            // second pass and, behind that, the slow path)
-            if (rcap >= capW && !(h->bigPath && h->capFull > capW)) {
-                rc = launch_row<R>(h, dC, nprob, theta, x, flag, iters, active, st, rcap, 0);
-            } else {
-                h->wavePass = 1;
-                rc = launch_row<R>(h, dC, nprob, theta, x, flag, iters, active, st, rcap, 1);
-                h->wavePass = 2;
-                // (what the row kernel lists is a handful of long solves: the second pass is a latency chain, so it takes the
-                // highest staging level that fits with small workgroups instead of the most wavefronts per CU --
-                // pendulum_N50: 0.22 -> 0.12 ms for the 327 of 2e5 points beyond 16 rows)
-                cfg = wave_config(h, sizeof(R));
-                if (h->waveLevel < 0 && h->waveNwv <= 0) {
-                    for (int lv = 3; lv >= 1; lv--) {
-                        h->waveLevel = lv; h->waveNwv = 2;
-                        const WaveConfig c2 = wave_config(h, sizeof(R));
-                        if (c2.level >= 1) { cfg = c2; break; }
-                    }
-                    h->waveLevel = -1; h->waveNwv = 0;
-                }
-                if (rc == LMPC_OK) rc = dispatch();
-                h->wavePass = 0;
-            }
-            h->waveOvfSet ^= 1;
-            if (prof) {
-                if (rc == LMPC_OK) { HIP_TRY(h, hipEventRecord(ev.b, st)); h->events.push_back(ev); }
-                else { hipEventDestroy(ev.a); hipEventDestroy(ev.mid); hipEventDestroy(ev.b); }
-            }
-            return rc;
+    // The first-pass launcher: the row kernel, else this kernel at c1 rows, else none (one pass).  The row kernel runs as
+    // the ONLY pass where nothing lies behind its capacity; else what outgrows it is listed: for this kernel's second
+    // pass and, behind that, the slow path.
+    const int rcap = row_cap(nprob, warm != nullptr);
+    const int cap1 = rcap > 0 ? rcap : c1;
+    bool rowOnly = false;
+    if (rcap > 0) {
+        if constexpr (BNB) rowOnly = rcap >= capW;            // (a search has no slow path behind it)
+        else if (rcap >= capW && !(h->bigPath && h->capFull > capW)) {
+            rowOnly = true;
         }
     }
-    if constexpr (BNB && !GRAM) {           // ... four searches per wavefront
-        const int rcap = row_bnb_pass_cap(h, nprob, sizeof(R));
-        if (rcap > 0) {
-            if (rcap >= capW) {
-                rc = launch_row_bnb<R>(h, dC, nprob, theta, x, flag, iters, active, st, rcap, 0);
-            } else {
-                h->wavePass = 1;
-                rc = launch_row_bnb<R>(h, dC, nprob, theta, x, flag, iters, active, st, rcap, 1);
-                h->wavePass = 2;
-                cfg = wave_config(h, sizeof(R));
-                if (rc == LMPC_OK) rc = dispatch();
-                h->wavePass = 0;
+    int rc;
+    if (rowOnly) {
+        rc = row(at_cap(a, rcap));
+    } else if (cap1 > 0) {
+        WaveArgs p1 = at_cap(a, cap1), p2 = a;
+        p1.pass = 1; p2.pass = 2;
+        rc = rcap > 0 ? row(p1) : dispatch(p1);
+        // (what the row kernel lists is a handful of long solves: the second pass is a latency chain, so it takes the
+        // highest staging level that fits with small workgroups instead of the most wavefronts per CU --
+        // pendulum_N50: 0.22 -> 0.12 ms for the 327 of 2e5 points beyond 16 rows)
+        if (rcap > 0 && !BNB && a.level < 0 && a.nwv <= 0) {
+            for (int lv = 3; lv >= 1; lv--) {
+                WaveArgs t = p2;
+                t.level = lv; t.nwv = 2;
+                if (wave_config(h, t, sizeof(R)).level >= 1) { p2 = t; break; }
             }
-            h->waveOvfSet ^= 1;
-            if (prof) {
-                if (rc == LMPC_OK) { HIP_TRY(h, hipEventRecord(ev.b, st)); h->events.push_back(ev); }
-                else { hipEventDestroy(ev.a); hipEventDestroy(ev.mid); hipEventDestroy(ev.b); }
-            }
-            return rc;
         }
-    }
-    if (c1 > 0) {
-        h->W.cap = c1; h->W.ldc = c1 | 1; h->wavePass = 1;
-        cfg = wave_config(h, sizeof(R));
-        rc = dispatch();
-        h->W.cap = capW; h->W.ldc = ldcW; h->wavePass = 2;
-        cfg = wave_config(h, sizeof(R));
-        if (rc == LMPC_OK) rc = dispatch();
-        h->wavePass = 0;
+        if (rc == LMPC_OK) rc = dispatch(p2);
     } else {
-        rc = dispatch();
+        rc = dispatch(a);
     }
     h->waveOvfSet ^= 1;
-    if (prof) {
-        if (rc == LMPC_OK) { HIP_TRY(h, hipEventRecord(ev.b, st)); h->events.push_back(ev); }
-        else { hipEventDestroy(ev.a); hipEventDestroy(ev.mid); hipEventDestroy(ev.b); }
-    }
-    return rc;
+    return prof.end(rc);
 }
 
 }  // namespace lmpc
