@@ -529,6 +529,38 @@ int lmpc_wave_launch_info(const lmpc_handle *h, int32_t *out, int max);
 #define LMPC_ROW_INFO_WORDS 20
 int lmpc_row_launch_info(const lmpc_handle *h, int32_t *out, int max);
 
+/* The same for the pass that runs IN FRONT of an iterating kernel and fills its work list (the screening pass or the
+ * tiers pass, qp_tiers_kernel): the handle's four most recent front-pass launches, OLDEST first, LMPC_FRONT_INFO_WORDS
+ * words each; returns how many (< 0: error).  Host memory only, written when the launch is enqueued.  A call without a
+ * front pass (the one-launch kernel, a wavefront-kernel call without screening, "screen" 0) leaves no entry.  Words:
+ *    [0] running number of the launch in the handle's life (1, 2, ...), counted apart from the other records
+ *    [1] kind: LMPC_FRONT_SCREEN (1) the screening pass, LMPC_FRONT_TIERS (2) the tiers pass
+ *    [2] template argument N of qp_tiers_kernel (0 for the screening pass)
+ *    [3] workgroups (grid)   [4] dynamic LDS bytes per workgroup   [5] problems of the batch (saturated at 2^31 - 1)
+ *    [6] seg_cap: entries a segment of the work list holds (saturated likewise)
+ *    [7] the kernel that walks the list: LMPC_WALK_LANE (1), LMPC_WALK_WAVE (2), LMPC_WALK_ROW (3)
+ * For tests and benchmark reports. */
+#define LMPC_FRONT_INFO_WORDS 8
+#define LMPC_FRONT_SCREEN 1
+#define LMPC_FRONT_TIERS 2
+#define LMPC_WALK_LANE 1
+#define LMPC_WALK_WAVE 2
+#define LMPC_WALK_ROW 3
+int lmpc_front_pass_info(const lmpc_handle *h, int32_t *out, int max);
+
+/* What a front pass left on the work list, for tests: with lmpc_set_option(h, "list_snapshot", 1) every call that runs
+ * a front pass enqueues, between that pass and the kernel behind it, a device-to-device copy of the call's counter set
+ * and of its LMPC_LIST_SHARDS x seg_cap list into a buffer the handle owns (allocated when the option is set, grown by
+ * the call that needs more, freed with the handle and by lmpc_release_scratch).  lmpc_work_list_read waits for the
+ * handle's device, then copies the counters of the most recent snapshot into counts[LMPC_LIST_SHARDS] and the list,
+ * segment after segment at seg_cap (word [6] of that call's lmpc_front_pass_info entry) words each, into
+ * list[list_words] (list may be NULL: counters only; list_words smaller than LMPC_LIST_SHARDS x seg_cap: LMPC_ERR_BADARG).
+ * Returns seg_cap, 0 if no snapshot has been taken (since the option was set or the scratch released), < 0 on error.
+ * With the option off (the default) no call changes; with it on, a call made inside a stream capture is refused
+ * (LMPC_ERR_UNSUPPORTED): the snapshot may have to allocate. */
+#define LMPC_LIST_SHARDS 64
+long long lmpc_work_list_read(lmpc_handle *h, int32_t *counts, int32_t *list, long long list_words);
+
 /* Device time per lmpc_solve_batch* call, measured with HIP events recorded on the launch
  * stream (switch on with lmpc_profile(h, 1); timing-only events, hipEventDisableSystemFence: a default event's
  * system-scope cache writeback added ~1.7 us to a 24 us call that rocprofv3's kernel trace does not see).  lmpc_profile_read waits for the recorded calls,

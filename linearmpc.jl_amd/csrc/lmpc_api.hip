@@ -291,7 +291,7 @@ int launch_lane(lmpc_handle *h, int B, size_t lds, int64_t nprob, const double *
 
 template <int NTHMAX, int NT, int MODE>
 int launch_screen(lmpc_handle *h, int64_t nprob, const double *theta, double *x, int32_t *flag,
-                  int32_t *iters, uint64_t *active, const uint64_t *warm, int32_t *count, hipStream_t st) {
+                  int32_t *iters, uint64_t *active, const uint64_t *warm, int32_t *count, hipStream_t st, FrontLaunch *fl) {
     const int B = 256;
     // several outputs per problem: room for the wave-private transpose of the outputs (plain mode)
     const size_t lds = MODE == 3 ? sizeof(double) * B * (size_t)h->P.nout : 0;
@@ -301,6 +301,7 @@ int launch_screen(lmpc_handle *h, int64_t nprob, const double *theta, double *x,
     hipLaunchKernelGGL((screen_kernel<NTHMAX, NT, MODE>), dim3(grid), dim3(B), lds, st, h->L, h->dC, theta, x, flag,
                        iters, active, warm, h->dList, count, segCap, kShards, (long long)nprob);
     HIP_TRY(h, hipGetLastError());
+    if (fl) *fl = FrontLaunch{LMPC_FRONT_SCREEN, 0, (long long)grid, lds};
     return LMPC_OK;
 }
 
@@ -402,27 +403,70 @@ WaveList work_list(const int32_t *list, const int32_t *count, int32_t *count_nex
     return wl;
 }
 
+// what a front pass enqueued, for lmpc_front_pass_info (include/lmpc_hip.h lists the words)
+void front_record(lmpc_handle *h, const FrontLaunch &fl, int64_t nprob, int walker) {
+    const auto sat = [](long long v) { return (int32_t)(v < 0x7fffffffll ? v : 0x7fffffffll); };
+    const int32_t rec[LMPC_FRONT_INFO_WORDS] = {
+        (int32_t)((h->frontRecN + 1) & 0x7fffffff), fl.kind, fl.n, sat(fl.grid), sat((long long)fl.lds), sat((long long)nprob),
+        sat(lane_seg_cap(nprob)), walker};
+    for (int q = 0; q < LMPC_FRONT_INFO_WORDS; q++) h->frontRec[h->frontRecN & 3][q] = rec[q];
+    h->frontRecN++;
+}
+
+int ensure_snapshot(lmpc_handle *h, int64_t nprob);
+// option "list_snapshot": the buffer for a batch of nprob problems (one counter set, then kShards segments), made ready
+// before the call enqueues anything (nothing with the option off)
+int snapshot_prepare(lmpc_handle *h, int64_t nprob, hipStream_t st) {
+    if (!h->listSnapshot) return LMPC_OK;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
+        (void)hipGetLastError();
+        return fail(h, LMPC_ERR_UNSUPPORTED, "lmpc: \"list_snapshot\" 1 does not work inside a stream capture");
+    }
+    return ensure_snapshot(h, nprob);
+}
+int ensure_snapshot(lmpc_handle *h, int64_t nprob) {
+    const size_t words = (size_t)kShards * kCountStride + (size_t)kShards * (size_t)lane_seg_cap(nprob);
+    if (words <= h->snapCap) return LMPC_OK;
+    (void)hipFree(h->dSnap); h->dSnap = nullptr; h->snapCap = 0; h->snapSegCap = 0;
+    HIP_TRY(h, hipMalloc(&h->dSnap, sizeof(int32_t) * words));
+    h->snapCap = words;
+    return LMPC_OK;
+}
+
+// ... and the copy itself, enqueued between a front pass and the kernel that walks its list
+int list_snapshot(lmpc_handle *h, const int32_t *count, int64_t nprob, hipStream_t st) {
+    if (!h->listSnapshot) return LMPC_OK;
+    const size_t segCap = (size_t)lane_seg_cap(nprob);
+    HIP_TRY(h, hipMemcpyAsync(h->dSnap, count, sizeof(int32_t) * kShards * kCountStride, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(h, hipMemcpyAsync(h->dSnap + (size_t)kShards * kCountStride, h->dList, sizeof(int32_t) * kShards * segCap,
+                              hipMemcpyDeviceToDevice, st));
+    h->snapSegCap = (long long)segCap;
+    return LMPC_OK;
+}
+
 // The screening pass at the handle's column count (exact up to 16, padded beyond) in one of its modes: 0 plain, 1 closed
 // loop with the plant step fused in (SimFuse), 2 generated controller (GatherArgs), 3 several outputs, stored transposed
 template <int NTHMAX, int NT>
 int launch_screen_mode(lmpc_handle *h, int mode, int64_t nprob, const double *theta, double *x, int32_t *flag,
-                       int32_t *iters, uint64_t *active, const uint64_t *warm, int32_t *count, hipStream_t st) {
+                       int32_t *iters, uint64_t *active, const uint64_t *warm, int32_t *count, hipStream_t st, FrontLaunch *fl) {
     switch (mode) {
-        case 1: return launch_screen<NTHMAX, NT, 1>(h, nprob, theta, x, flag, iters, active, warm, count, st);
-        case 2: return launch_screen<NTHMAX, NT, 2>(h, nprob, theta, x, flag, iters, active, warm, count, st);
-        case 3: return launch_screen<NTHMAX, NT, 3>(h, nprob, theta, x, flag, iters, active, warm, count, st);
-        default: return launch_screen<NTHMAX, NT, 0>(h, nprob, theta, x, flag, iters, active, warm, count, st);
+        case 1: return launch_screen<NTHMAX, NT, 1>(h, nprob, theta, x, flag, iters, active, warm, count, st, fl);
+        case 2: return launch_screen<NTHMAX, NT, 2>(h, nprob, theta, x, flag, iters, active, warm, count, st, fl);
+        case 3: return launch_screen<NTHMAX, NT, 3>(h, nprob, theta, x, flag, iters, active, warm, count, st, fl);
+        default: return launch_screen<NTHMAX, NT, 0>(h, nprob, theta, x, flag, iters, active, warm, count, st, fl);
     }
 }
 
 int launch_screen_any(lmpc_handle *h, int mode, int64_t nprob, const double *theta, double *x, int32_t *flag,
-                      int32_t *iters, uint64_t *active, const uint64_t *warm, int32_t *count, hipStream_t st) {
-#define LMPC_SCR(NM, NT) case NT: return launch_screen_mode<NM, NT>(h, mode, nprob, theta, x, flag, iters, active, warm, count, st);
+                      int32_t *iters, uint64_t *active, const uint64_t *warm, int32_t *count, hipStream_t st,
+                      FrontLaunch *fl = nullptr) {
+#define LMPC_SCR(NM, NT) case NT: return launch_screen_mode<NM, NT>(h, mode, nprob, theta, x, flag, iters, active, warm, count, st, fl);
     switch (h->P.nth <= 16 ? h->P.nth : 32) {
         LMPC_SCR(8, 1) LMPC_SCR(8, 2) LMPC_SCR(8, 3) LMPC_SCR(8, 4) LMPC_SCR(8, 5) LMPC_SCR(8, 6) LMPC_SCR(8, 7) LMPC_SCR(8, 8)
         LMPC_SCR(16, 9) LMPC_SCR(16, 10) LMPC_SCR(16, 11) LMPC_SCR(16, 12) LMPC_SCR(16, 13) LMPC_SCR(16, 14) LMPC_SCR(16, 15)
         LMPC_SCR(16, 16)
-        default: return launch_screen_mode<32, 32>(h, mode, nprob, theta, x, flag, iters, active, warm, count, st);
+        default: return launch_screen_mode<32, 32>(h, mode, nprob, theta, x, flag, iters, active, warm, count, st, fl);
     }
 #undef LMPC_SCR
 }
@@ -431,13 +475,16 @@ int launch_screen_any(lmpc_handle *h, int mode, int64_t nprob, const double *the
 int launch_wave_screened(lmpc_handle *h, int64_t nprob, const double *theta, double *x, int32_t *flag,
                          int32_t *iters, uint64_t *active, const uint64_t *warm, hipStream_t st) {
     LMPC_TRY(ensure_lists(h, nprob, st));
+    LMPC_TRY(snapshot_prepare(h, nprob, st));
     ProfBracket prof(h, st);
     LMPC_TRY(prof.begin(h->prof));
     int32_t *cnt_now, *cnt_next;
     next_count_set(h, &cnt_now, &cnt_next);
     // closed loop with the plant step fused in (lmpc_simulate_device), else several outputs stored transposed, else plain
     const int mode = h->L.sim.FG != nullptr ? 1 : (h->P.nout > 1 && h->P.nout <= 16 ? 3 : 0);
-    int rc = launch_screen_any(h, mode, nprob, theta, x, flag, iters, active, warm, cnt_now, st);
+    FrontLaunch fl;
+    int rc = launch_screen_any(h, mode, nprob, theta, x, flag, iters, active, warm, cnt_now, st, &fl);
+    if (rc == LMPC_OK) { front_record(h, fl, nprob, LMPC_WALK_WAVE); rc = list_snapshot(h, cnt_now, nprob, st); }
     LMPC_TRY(prof.mid());
     if (rc == LMPC_OK)
         rc = launch_wave(h, wave_args(h, work_list(h->dList, cnt_now, cnt_next, nprob)), nprob, theta, x, flag, iters, active, warm, st);
@@ -508,11 +555,14 @@ bool qp_tiers_applies(const lmpc_handle *h, int64_t nprob, const double *x, cons
 int launch_wave_tiered(lmpc_handle *h, int64_t nprob, const double *theta, double *x, int32_t *flag, int32_t *iters,
                        uint64_t *active, hipStream_t st) {
     LMPC_TRY(ensure_lists(h, nprob, st));
+    LMPC_TRY(snapshot_prepare(h, nprob, st));
     ProfBracket prof(h, st);
     LMPC_TRY(prof.begin(h->prof));
     int32_t *cnt_now, *cnt_next;
     next_count_set(h, &cnt_now, &cnt_next);
-    int rc = launch_qp_tiers(h, nprob, theta, x, flag, iters, active, h->dList, cnt_now, lane_seg_cap(nprob), st, false);
+    FrontLaunch fl;
+    int rc = launch_qp_tiers(h, nprob, theta, x, flag, iters, active, h->dList, cnt_now, lane_seg_cap(nprob), st, false, &fl);
+    if (rc == LMPC_OK) { front_record(h, fl, nprob, LMPC_WALK_WAVE); rc = list_snapshot(h, cnt_now, nprob, st); }
     LMPC_TRY(prof.mid());
     if (rc == LMPC_OK)
         rc = launch_wave(h, wave_args(h, work_list(h->dList, cnt_now, cnt_next, nprob)), nprob, theta, x, flag, iters, active, nullptr, st);
@@ -692,13 +742,19 @@ int launch_on_lanes(lmpc_handle *h, int64_t nprob, const double *theta, double *
                (ab_variant = qp_ab_choose(h, nprob, st, &ab_measure)) == 0) {
         // general rows on the lane path: the tiers pass (lmpc_qp_tiers_kernel.hpp) instead of the screening pass -- it
         // finishes every append-only path, the lane kernel walks the rest
+        LMPC_TRY(snapshot_prepare(h, nprob, st));
         LMPC_TRY(qp_ab_begin(h, ab_measure, st));
         next_count_set(h, &cnt_now, &cnt_next);
-        rc = launch_qp_tiers(h, nprob, theta, x, flag, iters, active, h->dList, cnt_now, lane_seg_cap(nprob), st, false);
+        FrontLaunch fl;
+        rc = launch_qp_tiers(h, nprob, theta, x, flag, iters, active, h->dList, cnt_now, lane_seg_cap(nprob), st, false, &fl);
+        if (rc == LMPC_OK) { front_record(h, fl, nprob, LMPC_WALK_LANE); rc = list_snapshot(h, cnt_now, nprob, st); }
     } else if (screened) {
+        LMPC_TRY(snapshot_prepare(h, nprob, st));
         LMPC_TRY(qp_ab_begin(h, ab_measure, st));
         next_count_set(h, &cnt_now, &cnt_next);
-        rc = launch_screen_any(h, sim ? 1 : (gather ? 2 : (wide ? 3 : 0)), nprob, theta, x, flag, iters, active, warm, cnt_now, st);
+        FrontLaunch fl;
+        rc = launch_screen_any(h, sim ? 1 : (gather ? 2 : (wide ? 3 : 0)), nprob, theta, x, flag, iters, active, warm, cnt_now, st, &fl);
+        if (rc == LMPC_OK) { front_record(h, fl, nprob, LMPC_WALK_LANE); rc = list_snapshot(h, cnt_now, nprob, st); }
     }
     LMPC_TRY(prof.mid());
     const int32_t *list = screened ? (h->asyncPhase == 2 ? h->asyncListOut : h->dList) : nullptr;
@@ -1104,6 +1160,31 @@ int lmpc_row_launch_info(const lmpc_handle *h, int32_t *out, int max) {
     return (int)k;
 }
 
+int lmpc_front_pass_info(const lmpc_handle *h, int32_t *out, int max) {
+    if (!h || !out || max < 0) return LMPC_ERR_BADARG;
+    long long k = h->frontRecN < 4 ? h->frontRecN : 4;
+    if (k > max) k = max;
+    for (long long q = 0; q < k; q++)                      // the k most recent entries of the ring, oldest first
+        std::memcpy(out + q * LMPC_FRONT_INFO_WORDS, h->frontRec[(h->frontRecN - k + q) & 3], sizeof(int32_t) * LMPC_FRONT_INFO_WORDS);
+    return (int)k;
+}
+
+long long lmpc_work_list_read(lmpc_handle *h, int32_t *counts, int32_t *list, long long list_words) {
+    if (!h || !counts) return LMPC_ERR_BADARG;
+    if (!h->dSnap || h->snapSegCap <= 0) return 0;
+    const long long need = (long long)kShards * h->snapSegCap;
+    if (list && list_words < need) return fail(h, LMPC_ERR_BADARG, "lmpc_work_list_read: list_words is smaller than 64 x seg_cap");
+    LMPC_ENTER_DEVICE(h);
+    hipError_t e = hipDeviceSynchronize();
+    int32_t cnt[kShards * kCountStride];
+    if (e == hipSuccess) e = hipMemcpy(cnt, h->dSnap, sizeof(cnt), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && list)
+        e = hipMemcpy(list, h->dSnap + (size_t)kShards * kCountStride, sizeof(int32_t) * (size_t)need, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(h, LMPC_ERR_HIP, std::string("lmpc_work_list_read: ") + hipGetErrorString(e));
+    for (int s = 0; s < kShards; s++) counts[s] = cnt[s * kCountStride];
+    return h->snapSegCap;
+}
+
 const char *lmpc_kernel_name(const lmpc_handle *h) {
     if (!h) return "";
     if (h->avi) return h->kname.c_str();          // "avi" / "avi+prox"
@@ -1243,6 +1324,14 @@ int lmpc_set_option(lmpc_handle *h, const char *name, int value) {
         h->qpAbCalls = 0; h->qpAbNsPer[0] = h->qpAbNsPer[1] = -1.0; h->qpAbPending[0] = h->qpAbPending[1] = false; h->qpAbCnt[0] = h->qpAbCnt[1] = 0;   // (measure again)
         return LMPC_OK;
     }
+    if (std::strcmp(name, "list_snapshot") == 0) {
+        // (tests: what a front pass left on the work list, lmpc_work_list_read; the buffer for the lists the handle
+        // holds now, a larger batch grows it)
+        h->listSnapshot = value != 0; h->snapSegCap = 0;
+        if (!h->listSnapshot || h->listCap <= 0) return LMPC_OK;
+        LMPC_ENTER_DEVICE(h);
+        return ensure_snapshot(h, h->listCap);
+    }
     if (std::strcmp(name, "avi_tiers") == 0) { h->aviTiers = value != 0; return LMPC_OK; }
     if (std::strcmp(name, "avi_tiers_first") == 0) {
         h->aviTiersFirst = value < 0 ? -1 : (value > 3 ? 3 : value); h->aviTiersOcc[0] = 0; return LMPC_OK;
@@ -1301,6 +1390,7 @@ int lmpc_release_scratch(lmpc_handle *h) {
     auto rel = [](auto *&p) { if (p) { (void)hipFree(p); p = nullptr; } };
     rel(h->sTheta); rel(h->sX); rel(h->sFlag); rel(h->sIter); rel(h->sAct); rel(h->sWarm); h->sCap = 0;
     rel(h->dList); rel(h->dList2); rel(h->dList3); rel(h->dCount); h->listCap = 0; h->countSet = 0;
+    rel(h->dSnap); h->snapCap = 0; h->snapSegCap = 0;
     rel(h->simTheta); rel(h->simTheta2); rel(h->simU); rel(h->simFG); rel(h->simFlag); rel(h->simAct); rel(h->simK); h->simCap = 0;
     rel(h->ccTheta); rel(h->ccAct); rel(h->ccFlag); h->ccCap = 0; h->ccWarmN = -1;
     rel(h->ccStage); rel(h->ccStageFlag); h->ccStageCap = 0; h->ccStagePer = 0;
@@ -1333,7 +1423,7 @@ void lmpc_free(lmpc_handle *h) {
     hipFree(h->dC); hipFree(h->sTheta); hipFree(h->sX); hipFree(h->sFlag); hipFree(h->sIter);
     hipFree(h->sAct); hipFree(h->sWarm); hipFree(h->dList); hipFree(h->dList2); hipFree(h->dList3); hipFree(h->dCount); hipFree(h->dCw); hipFree(h->dCwf); hipFree(h->dSw); hipFree(h->dQueue);
     hipFree(h->dOvfList); hipFree(h->dOvfCount); hipFree(h->dBigR); hipFree(h->dBigI); hipFree(h->dRegTable); hipFree(h->dRegW1); hipFree(h->dQpScan); hipFree(h->dFastCtr);
-    hipFree(h->dRowBnb);
+    hipFree(h->dRowBnb); hipFree(h->dSnap);
     hipFree(h->dBnbR); hipFree(h->dBnbI); hipFree(h->dKeepR); hipFree(h->dKeepI); hipFree(h->dOvfList1);
     if (h->hStat) hipHostFree(const_cast<unsigned long long *>(h->hStat));
     if (h->hRegOut) hipHostFree(h->hRegOut);

@@ -87,6 +87,14 @@ struct lmpc_handle {
     // ... and launch_row_shape (lmpc_row_launch_info): the four most recent row-kernel launches, counted apart
     int32_t rowRec[4][LMPC_ROW_INFO_WORDS] = {};
     long long rowRecN = 0;
+    // ... and of the front passes (lmpc_front_pass_info): the four most recent screening / tiers launches, counted apart
+    int32_t frontRec[4][LMPC_FRONT_INFO_WORDS] = {};
+    long long frontRecN = 0;
+    // option "list_snapshot": every front pass's counter set and work list copied aside for lmpc_work_list_read
+    int listSnapshot = 0;
+    int32_t *dSnap = nullptr;   // [kShards * kCountStride counter words | kShards * seg_cap list words]
+    size_t snapCap = 0;         // ... words allocated
+    long long snapSegCap = 0;   // ... seg_cap of the snapshot it holds (0: none)
     int32_t *dRegTable = nullptr;  // hash table of lmpc_distinct_active_sets_device (lmpc_regions.hip): 16 control words + slots
     int regCap = 0;
     unsigned long long *dRegW1 = nullptr;   // one-word masks: key / count / first-index tables of regW1Cap slots each (clean
@@ -416,12 +424,16 @@ int launch_avi_tiers(lmpc_handle *h, bool first, int kfirst, unsigned grid, hipS
                      int32_t *flag, int32_t *iters, uint64_t *active, const int32_t *list_in, const int32_t *count_in,
                      int32_t *list_out, int32_t *count_out, int32_t *count_clear, long long seg_cap, long long nprob, int *occ);
 
+// what a front pass's launcher enqueued, for the handle's record (lmpc_front_pass_info)
+struct FrontLaunch { int kind = 0, n = 0; long long grid = 0; size_t lds = 0; };
+
 // one-launch solver for small box-constrained problems (lmpc_fast_inst.hip)
 bool fast_covers(const lmpc_handle *h);
 void fast_preload(lmpc_handle *h);
 size_t qp_tiers_lds_bytes(int n, int m);
 int launch_qp_tiers(lmpc_handle *h, int64_t nprob, const double *theta, double *x, int32_t *flag, int32_t *iters,
-                    uint64_t *active, int32_t *list, int32_t *count, long long seg_cap, hipStream_t st, bool preload);
+                    uint64_t *active, int32_t *list, int32_t *count, long long seg_cap, hipStream_t st, bool preload,
+                    FrontLaunch *fl = nullptr);
 void avi_preload(lmpc_handle *h);
 int avi_reserve(lmpc_handle *h, int64_t nprob, hipStream_t st);
 int launch_fast(lmpc_handle *h, int64_t nprob, const double *theta, double *x, int32_t *flag, int32_t *iters,

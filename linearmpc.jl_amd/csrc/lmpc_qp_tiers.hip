@@ -12,7 +12,7 @@ namespace lmpc {
 namespace {
 template <int N>
 int go(lmpc_handle *h, int64_t nprob, const double *theta, double *x, int32_t *flag, int32_t *iters, uint64_t *active,
-       int32_t *list, int32_t *count, long long seg_cap, hipStream_t st, bool preload) {
+       int32_t *list, int32_t *count, long long seg_cap, hipStream_t st, bool preload, FrontLaunch *fl) {
     auto kern = qp_tiers_kernel<N>;
     const size_t lds = sizeof(double) * (size_t)QpTiersLds<N>::reals(h->P.m);
     if (lds > 48 * 1024)
@@ -50,6 +50,7 @@ int go(lmpc_handle *h, int64_t nprob, const double *theta, double *x, int32_t *f
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, st, h->W, h->dCw, theta, x, flag, iters, active, list, count,
                        seg_cap, (long long)nprob, h->dQpScan, soft);
     HIP_TRY(h, hipGetLastError());
+    if (fl) *fl = FrontLaunch{LMPC_FRONT_TIERS, N, grid, lds};
     return LMPC_OK;
 }
 }  // namespace
@@ -64,9 +65,10 @@ size_t qp_tiers_lds_bytes(int n, int m) {
 }
 
 int launch_qp_tiers(lmpc_handle *h, int64_t nprob, const double *theta, double *x, int32_t *flag, int32_t *iters,
-                    uint64_t *active, int32_t *list, int32_t *count, long long seg_cap, hipStream_t st, bool preload) {
+                    uint64_t *active, int32_t *list, int32_t *count, long long seg_cap, hipStream_t st, bool preload,
+                    FrontLaunch *fl) {
     switch (h->P.n) {
-#define LMPC_QT(N) case N: return go<N>(h, nprob, theta, x, flag, iters, active, list, count, seg_cap, st, preload);
+#define LMPC_QT(N) case N: return go<N>(h, nprob, theta, x, flag, iters, active, list, count, seg_cap, st, preload, fl);
         LMPC_QT(2) LMPC_QT(3) LMPC_QT(4) LMPC_QT(5) LMPC_QT(6) LMPC_QT(7) LMPC_QT(8) LMPC_QT(9) LMPC_QT(10) LMPC_QT(11) LMPC_QT(12)
 #undef LMPC_QT
         default: break;

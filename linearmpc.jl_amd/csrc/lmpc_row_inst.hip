@@ -162,6 +162,8 @@ int launch_row_shape(lmpc_handle *h, const WaveArgs &a, const RowLaunch &rl, con
         sat((long long)nprob), BNB ? sat((long long)h->rowBnbBytes) : 0};
     for (int q = 0; q < LMPC_ROW_INFO_WORDS; q++) h->rowRec[h->rowRecN & 3][q] = rec[q];
     h->rowRecN++;
+    // ... and in the record of the front pass whose list this launch walks (lmpc_front_pass_info)
+    if (wl.list != nullptr && h->frontRecN > 0) h->frontRec[(h->frontRecN - 1) & 3][7] = LMPC_WALK_ROW;
     return LMPC_OK;
 }
 

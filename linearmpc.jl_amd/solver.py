@@ -222,6 +222,41 @@ class BatchedQP:
         recs = [dict(zip(self.ROW_LAUNCH_FIELDS, (int(v) for v in out[q * W:(q + 1) * W]))) for q in range(k)]
         return [r for r in recs if r["seq"] > since]
 
+    FRONT_PASS_FIELDS = ("seq", "kind", "N", "grid", "lds", "nprob", "seg_cap", "walker")
+    FRONT_SCREEN, FRONT_TIERS = 1, 2
+    WALK_LANE, WALK_WAVE, WALK_ROW = 1, 2, 3
+    LIST_SHARDS = 64
+
+    def front_pass_info(self, since=0):
+        """The handle's most recent front-pass launches (lmpc_front_pass_info; at most four are kept), oldest first:
+        one dict per launch with its kind (FRONT_SCREEN the screening pass, FRONT_TIERS the tiers pass), the template
+        argument N of qp_tiers_kernel (0 for the screening pass), grid, lds, nprob, seg_cap and the kernel that walks
+        the list (WALK_LANE / WALK_WAVE / WALK_ROW).  "seq" and `since` as in wave_launch_info.  A call without a front
+        pass leaves no entry."""
+        W = len(self.FRONT_PASS_FIELDS)
+        out = (ctypes.c_int32 * (4 * W))()
+        k = lib().lmpc_front_pass_info(self._h, out, 4)
+        if k < 0:
+            check(k, self._h)
+        recs = [dict(zip(self.FRONT_PASS_FIELDS, (int(v) for v in out[q * W:(q + 1) * W]))) for q in range(k)]
+        return [r for r in recs if r["seq"] > since]
+
+    def work_list_read(self):
+        """What the most recent front pass left on the work list (lmpc_work_list_read; needs set_option("list_snapshot",
+        1) before the call): (counts, list) with counts the LIST_SHARDS segment counters and list a LIST_SHARDS x
+        seg_cap int32 array of which row s holds counts[s] entries -- or None if no snapshot has been taken."""
+        counts = np.zeros(self.LIST_SHARDS, np.int32)
+        seg = lib().lmpc_work_list_read(self._h, _ptr(counts), None, 0)
+        if seg < 0:
+            check(int(seg), self._h)
+        if seg == 0:
+            return None
+        lst = np.zeros((self.LIST_SHARDS, int(seg)), np.int32)
+        seg2 = lib().lmpc_work_list_read(self._h, _ptr(counts), _ptr(lst), lst.size)
+        if seg2 != seg:
+            check(int(seg2) if seg2 < 0 else -1, self._h)
+        return counts, lst
+
     def ldp(self):
         """The constant pack the kernels use (row-major) -- what tests hand to the oracle."""
         out = dict(M=np.empty((self.m, self.n)), du=np.empty(self.m), dl=np.empty(self.m),

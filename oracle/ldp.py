@@ -113,11 +113,27 @@ class Settings(ctypes.Structure):
 _lib = None
 
 
+def _stale():
+    return not os.path.exists(_LIB_PATH) or \
+        os.path.getmtime(_LIB_PATH) < max(os.path.getmtime(os.path.join(_HERE, f))
+                                          for f in ("daqp_ldp_oracle.c", "daqp_ldp_oracle_f32.c", "daqp_avi_oracle.c", "Makefile"))
+
+
 def build(force=False):
-    if force or not os.path.exists(_LIB_PATH) or \
-            os.path.getmtime(_LIB_PATH) < max(os.path.getmtime(os.path.join(_HERE, f))
-                                              for f in ("daqp_ldp_oracle.c", "daqp_ldp_oracle_f32.c", "daqp_avi_oracle.c", "Makefile")):
-        subprocess.run(["make", "-C", _HERE, "-s"], check=True)
+    """Rebuild liboracle.so if it is missing or older than its sources.  Several processes may get here at once (the
+    workers of tests/test_distributed_cpu.py are the first users of the oracle in a test run): one of them builds under
+    an exclusive file lock, the others wait and find the library fresh; the Makefile moves the finished file into place,
+    so nobody ever loads a half-written one."""
+    if force or _stale():
+        import fcntl
+        os.makedirs(os.path.dirname(_LIB_PATH), exist_ok=True)
+        with open(os.path.join(os.path.dirname(_LIB_PATH), ".build.lock"), "w") as lock:
+            fcntl.flock(lock, fcntl.LOCK_EX)
+            try:
+                if force or _stale():
+                    subprocess.run(["make", "-C", _HERE, "-s"], check=True)
+            finally:
+                fcntl.flock(lock, fcntl.LOCK_UN)
     return _LIB_PATH
 
 

@@ -100,14 +100,17 @@ def test_search(lmpc):
     _wave_form(lmpc, case, (), wc.theta(case, N), False, "branch and bound", records)
 
 
-def _row_form(lmpc, case, options, front, what, records):
+def _row_form(lmpc, case, options, front, what, records, front_record=None):
     qp = tr._handle(lmpc, case, options=options)
     th = rc.theta(case)[:N]
     ref = tr._ref(case, qp)
 
     def call():
+        seq = (qp.front_pass_info() or [dict(seq=0)])[-1]["seq"]
         got, rr, wr = tr._solve(qp, case, th)
         records(rr, wr)
+        if front_record is not None:
+            front_record(qp, qp.front_pass_info(seq))
         tr._same(got, ref, N, what)
     _profiled(qp, call, front, what)
 
@@ -117,8 +120,11 @@ def test_tiers_pass_and_wavefront_kernel(lmpc):
 
     def records(rr, wr):
         assert not rr and [(r["pass"], r["worklist"]) for r in wr] == [(0, 1)], (rr, wr)
+
+    def front_record(qp, recs):                              # (lmpc_front_pass_info: ONE tiers launch, the wavefront kernel behind it)
+        assert [(r["kind"], r["N"], r["nprob"], r["walker"]) for r in recs] == [(qp.FRONT_TIERS, case.n, N, qp.WALK_WAVE)], recs
     qp_opts = (("row_kernel", 0), ("qp_tiers", 2))
-    _row_form(lmpc, case, qp_opts, True, "tiers pass + wavefront kernel", records)
+    _row_form(lmpc, case, qp_opts, True, "tiers pass + wavefront kernel", records, front_record)
 
 
 def test_row_kernel_as_the_first_of_two_passes(lmpc):
