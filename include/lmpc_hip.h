@@ -561,6 +561,34 @@ int lmpc_front_pass_info(const lmpc_handle *h, int32_t *out, int max);
 #define LMPC_LIST_SHARDS 64
 long long lmpc_work_list_read(lmpc_handle *h, int32_t *counts, int32_t *list, long long list_words);
 
+/* The same for the chain of a variational handle (is_avi; lmpc_avi.hip): the handle's eight most recent launches of
+ * avi_tiers_kernel, avi_lane_kernel and avi_kernel, OLDEST first, LMPC_AVI_INFO_WORDS words each; returns how many
+ * (< 0: error).  A call makes three (the chain) or one (the slab kernel alone: warm start, iter_limit <= n + 1,
+ * "avi_tiers" 0, a problem the register kernels do not cover).  Host memory only, written when a launch is enqueued.
+ *    [0] running number of the launch in the handle's life (1, 2, ...), counted apart from the other records
+ *    [1] stage: LMPC_AVI_TIERS (1) avi_tiers_kernel<N, K, false>, LMPC_AVI_LANE (2) avi_lane_kernel<N, LIST>,
+ *        LMPC_AVI_SLAB (3) avi_kernel<LDSC, PROX>
+ *    [2] N   [3] K (0: lane and slab kernel)   [4] LIST: 1 = the launch walks a work list   [5] LDSC   [6] PROX
+ *    [7] workgroups (grid)   [8] dynamic LDS bytes per workgroup
+ *    [9] what the grid was sized with: workgroups per CU the instantiation keeps resident (register kernels, from
+ *        hipOccupancyMaxActiveBlocksPerMultiprocessor on the kernel that is launched), wavefronts per CU (slab kernel)
+ *   [10] problems of the batch (saturated at 2^31 - 1)   [11] seg_cap of the chain's lists (0: no list)
+ * For tests and benchmark reports. */
+#define LMPC_AVI_INFO_WORDS 12
+#define LMPC_AVI_INFO_KEPT 8
+#define LMPC_AVI_TIERS 1
+#define LMPC_AVI_LANE 2
+#define LMPC_AVI_SLAB 3
+int lmpc_avi_launch_info(const lmpc_handle *h, int32_t *out, int max);
+
+/* What the chain's first two launches left on their work lists, for tests: with lmpc_set_option(h, "list_snapshot", 1)
+ * a call that runs the chain enqueues a device-to-device copy of each list's counter set and of its LMPC_LIST_SHARDS x
+ * seg_cap entries right after the launch that filled it -- before the slab kernel, which clears the first set, and
+ * before the next call's first launch, which clears the second.  which = 0: the list of the launch over the whole
+ * batch, 1: the lane kernel's.  Arguments and return value as lmpc_work_list_read; 0 also after a call that made no
+ * list (the slab kernel alone).  A call made inside a stream capture is refused with the option on. */
+long long lmpc_avi_list_read(lmpc_handle *h, int which, int32_t *counts, int32_t *list, long long list_words);
+
 /* Device time per lmpc_solve_batch* call, measured with HIP events recorded on the launch
  * stream (switch on with lmpc_profile(h, 1); timing-only events, hipEventDisableSystemFence: a default event's
  * system-scope cache writeback added ~1.7 us to a 24 us call that rocprofv3's kernel trace does not see).  lmpc_profile_read waits for the recorded calls,
@@ -622,7 +650,10 @@ int lmpc_profile_read(lmpc_handle *h, double avg_ms[3]);
  * Variational handles (is_avi) with n <= 8 simple bounds run a chain of register-resident kernels in front of the
  * generic one: "avi_tiers" (default 1; 0 = the generic kernel alone), "avi_tiers_first" (-1 = default: 3 up to n = 6,
  * else 2; 1 .. 3 = straight-line tiers of the pass over the whole batch; 0 = the complete lane kernel over the whole
- * batch), "avi_waves" (generic kernel: wavefronts per CU, default 16).  Results identical either way.
+ * batch), "avi_waves" (generic kernel: wavefronts per CU, default 16), "avi_chain_groups" (default 0 = no cap; g > 0
+ * caps the workgroups of all three launches: rounded up to a multiple of 16 for the register kernels, down to a
+ * multiple of 64 -- 64 at least -- for the generic kernel behind a list; small values make every wavefront walk
+ * several tiles).  Results identical either way.
  * hipGraph capture of calls on one handle: the work-list and ticket counters alternate between two sets, each call
  * clearing the set of the next one -- capture an EVEN number of calls per handle. */
 int lmpc_set_option(lmpc_handle *h, const char *name, int value);

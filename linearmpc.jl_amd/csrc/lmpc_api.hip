@@ -1185,6 +1185,22 @@ long long lmpc_work_list_read(lmpc_handle *h, int32_t *counts, int32_t *list, lo
     return h->snapSegCap;
 }
 
+int lmpc_avi_launch_info(const lmpc_handle *h, int32_t *out, int max) {
+    if (!h || !out || max < 0) return LMPC_ERR_BADARG;
+    long long k = h->aviRecN < LMPC_AVI_INFO_KEPT ? h->aviRecN : LMPC_AVI_INFO_KEPT;
+    if (k > max) k = max;
+    for (long long q = 0; q < k; q++)                      // the k most recent entries of the ring, oldest first
+        std::memcpy(out + q * LMPC_AVI_INFO_WORDS, h->aviRec[(h->aviRecN - k + q) % LMPC_AVI_INFO_KEPT],
+                    sizeof(int32_t) * LMPC_AVI_INFO_WORDS);
+    return (int)k;
+}
+
+long long lmpc_avi_list_read(lmpc_handle *h, int which, int32_t *counts, int32_t *list, long long list_words) {
+    if (!h || !counts || which < 0 || which > 1) return LMPC_ERR_BADARG;
+    LMPC_ENTER_DEVICE(h);
+    return avi_list_read(h, which, counts, list, list_words);
+}
+
 const char *lmpc_kernel_name(const lmpc_handle *h) {
     if (!h) return "";
     if (h->avi) return h->kname.c_str();          // "avi" / "avi+prox"
@@ -1319,6 +1335,7 @@ int lmpc_set_option(lmpc_handle *h, const char *name, int value) {
     if (std::strcmp(name, "region_lockfree") == 0) { h->regW1 = value != 0; return LMPC_OK; }
     if (std::strcmp(name, "region_blocks") == 0) { h->regBlocks = value < 0 ? 0 : (value > 16 ? 16 : value); return LMPC_OK; }
     if (std::strcmp(name, "avi_waves") == 0) { h->aviWaves = value < 0 ? 0 : (value > 32 ? 32 : value); return LMPC_OK; }
+    if (std::strcmp(name, "avi_chain_groups") == 0) { h->aviChainGroups = value < 0 ? 0 : value; return LMPC_OK; }
     if (std::strcmp(name, "qp_tiers") == 0) {
         h->qpTiers = value < 0 ? 0 : (value > 2 ? 2 : value);
         h->qpAbCalls = 0; h->qpAbNsPer[0] = h->qpAbNsPer[1] = -1.0; h->qpAbPending[0] = h->qpAbPending[1] = false; h->qpAbCnt[0] = h->qpAbCnt[1] = 0;   // (measure again)
@@ -1327,7 +1344,7 @@ int lmpc_set_option(lmpc_handle *h, const char *name, int value) {
     if (std::strcmp(name, "list_snapshot") == 0) {
         // (tests: what a front pass left on the work list, lmpc_work_list_read; the buffer for the lists the handle
         // holds now, a larger batch grows it)
-        h->listSnapshot = value != 0; h->snapSegCap = 0;
+        h->listSnapshot = value != 0; h->snapSegCap = 0; h->aviSnapSeg[0] = h->aviSnapSeg[1] = 0;
         if (!h->listSnapshot || h->listCap <= 0) return LMPC_OK;
         LMPC_ENTER_DEVICE(h);
         return ensure_snapshot(h, h->listCap);

@@ -147,6 +147,52 @@ static int avi_ensure_lists(lmpc_handle *h, int64_t nprob, hipStream_t st) {
     return LMPC_OK;
 }
 
+// what a launch of the chain enqueued, for lmpc_avi_launch_info (include/lmpc_hip.h lists the words)
+static void avi_record(lmpc_handle *h, int stage, int n, int k, int list, int ldsc, int prox, long long grid, size_t lds,
+                       int occ, long long nprob, long long seg_cap) {
+    const auto sat = [](long long v) { return (int32_t)(v < 0x7fffffffll ? v : 0x7fffffffll); };
+    const int32_t rec[LMPC_AVI_INFO_WORDS] = {
+        (int32_t)((h->aviRecN + 1) & 0x7fffffff), stage, n, k, list, ldsc, prox, sat(grid), sat((long long)lds), occ, sat(nprob),
+        sat(seg_cap)};
+    for (int q = 0; q < LMPC_AVI_INFO_WORDS; q++) h->aviRec[h->aviRecN % LMPC_AVI_INFO_KEPT][q] = rec[q];
+    h->aviRecN++;
+}
+
+// option "list_snapshot": room for both lists of the chain as they are allocated now, made ready before the call
+// enqueues anything ...
+static int avi_snapshot_prepare(lmpc_handle *h) {
+    const size_t words = (size_t)kShards * kCountStride + (size_t)kShards * (size_t)avi_seg_cap(h->aviListCap);
+    if (words <= h->aviSnapWords) return LMPC_OK;
+    (void)hipFree(h->dAviSnap); h->dAviSnap = nullptr; h->aviSnapWords = 0;
+    HIP_TRY(h, hipMalloc(&h->dAviSnap, sizeof(int32_t) * 2 * words));
+    h->aviSnapWords = words;
+    return LMPC_OK;
+}
+// ... and the copy of one list, enqueued right after the launch that filled it
+static int avi_snapshot(lmpc_handle *h, int which, const int32_t *count, const int32_t *list, long long seg_cap, hipStream_t st) {
+    int32_t *dst = h->dAviSnap + (size_t)which * h->aviSnapWords;
+    HIP_TRY(h, hipMemcpyAsync(dst, count, sizeof(int32_t) * kShards * kCountStride, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(h, hipMemcpyAsync(dst + (size_t)kShards * kCountStride, list, sizeof(int32_t) * kShards * (size_t)seg_cap,
+                              hipMemcpyDeviceToDevice, st));
+    h->aviSnapSeg[which] = seg_cap;
+    return LMPC_OK;
+}
+
+long long avi_list_read(lmpc_handle *h, int which, int32_t *counts, int32_t *list, long long list_words) {
+    if (!h->dAviSnap || h->aviSnapSeg[which] <= 0) return 0;
+    const long long seg = h->aviSnapSeg[which], need = (long long)kShards * seg;
+    if (list && list_words < need) return fail(h, LMPC_ERR_BADARG, "lmpc_avi_list_read: list_words is smaller than 64 x seg_cap");
+    const int32_t *src = h->dAviSnap + (size_t)which * h->aviSnapWords;
+    hipError_t e = hipDeviceSynchronize();
+    int32_t cnt[kShards * kCountStride];
+    if (e == hipSuccess) e = hipMemcpy(cnt, src, sizeof(cnt), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && list)
+        e = hipMemcpy(list, src + (size_t)kShards * kCountStride, sizeof(int32_t) * (size_t)need, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(h, LMPC_ERR_HIP, std::string("lmpc_avi_list_read: ") + hipGetErrorString(e));
+    for (int s = 0; s < kShards; s++) counts[s] = cnt[s * kCountStride];
+    return seg;
+}
+
 // the generic kernel's grid for `tiles` tiles of 64 problems -- one wavefront per workgroup, resident wavefronts bounded
 // by the scratch a slab takes (at most 1 GiB in all), a multiple of kShards behind a work list -- and its slabs
 static int avi_ensure_slabs(lmpc_handle *h, long long tiles, bool listed, hipStream_t st, long long *grid_out) {
@@ -156,6 +202,7 @@ static int avi_ensure_slabs(lmpc_handle *h, long long tiles, bool listed, hipStr
     const long long fit = (long long)(((size_t)1 << 30) / (sizeof(double) * slabR + sizeof(int32_t) * slabI));
     grid = std::min(grid, std::max(1ll, fit));
     grid = std::min(grid, tiles);
+    if (h->aviChainGroups > 0) grid = std::min<long long>(grid, h->aviChainGroups);      // ("avi_chain_groups")
     if (listed) grid = std::max<long long>(kShards, (grid / kShards) * kShards);      // (fit >= kShards: slabs of small problems)
     if (grid > h->aviSlabs) {
         // (grows with the largest batch seen; stream-ordered work of earlier calls on this handle finishes first)
@@ -189,11 +236,20 @@ int launch_avi(lmpc_handle *h, int64_t nprob, const double *theta, double *x, in
                uint64_t *active, const uint64_t *warm, hipStream_t st) {
     if (!x || !flag) return fail(h, LMPC_ERR_BADARG, "lmpc: the variational-inequality kernel needs x and exitflag arrays");
     const long long tiles = (nprob + 63) / 64;
+    if (h->listSnapshot) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
+            (void)hipGetLastError();
+            return fail(h, LMPC_ERR_UNSUPPORTED, "lmpc: \"list_snapshot\" 1 does not work inside a stream capture");
+        }
+        h->aviSnapSeg[0] = h->aviSnapSeg[1] = 0;       // (a call without the chain leaves no list)
+    }
     if (!avi_use_tiers(h, nprob, warm))
         return avi_generic(h, nprob, tiles, theta, x, flag, iters, active, warm, nullptr, nullptr, 0, nullptr, st);
     // chain: tiers over the whole batch -> all n tiers on its list -> the generic kernel on that one's list
     const int rc0 = avi_ensure_lists(h, nprob, st);
     if (rc0 != LMPC_OK) return rc0;
+    if (h->listSnapshot) { const int rcs = avi_snapshot_prepare(h); if (rcs != LMPC_OK) return rcs; }
     // tiers of the first pass: three finish 93 % of the reference's game problem at 3 wavefronts per SIMD (n <= 6)
     const int kfirst = h->aviTiersFirst >= 0 ? h->aviTiersFirst : (h->aviTiersN <= 6 ? 3 : 2);
     for (int s = 0; s < 2; s++)
@@ -209,15 +265,22 @@ int launch_avi(lmpc_handle *h, int64_t nprob, const double *theta, double *x, in
         long long g = (long long)h->numCU * occ;
         const long long need = (tiles + 3) / 4;
         if (g > need) g = need;
+        if (h->aviChainGroups > 0 && g > h->aviChainGroups) g = h->aviChainGroups;      // ("avi_chain_groups")
         g = ((g + 15) / 16) * 16;
         return (unsigned)g;
     };
-    int rc = launch_avi_tiers(h, true, kfirst, grid_for(h->aviTiersOcc[0]), st, theta, x, flag, iters, active, nullptr,
-                              nullptr, h->dAviList[0], cnt0, cnt1, seg, (long long)nprob, nullptr);
+    AviLaunchShape sh;
+    const unsigned g0 = grid_for(h->aviTiersOcc[0]), g1 = grid_for(h->aviTiersOcc[1]);
+    int rc = launch_avi_tiers(h, true, kfirst, g0, st, theta, x, flag, iters, active, nullptr,
+                              nullptr, h->dAviList[0], cnt0, cnt1, seg, (long long)nprob, nullptr, &sh);
     if (rc != LMPC_OK) return rc;
-    rc = launch_avi_tiers(h, false, 0, grid_for(h->aviTiersOcc[1]), st, theta, x, flag, iters, active, h->dAviList[0], cnt0,
-                          h->dAviList[1], cnt1, nullptr, seg, (long long)nprob, nullptr);
+    avi_record(h, sh.stage, sh.n, sh.k, sh.list, 0, 0, g0, sh.lds, h->aviTiersOcc[0], nprob, seg);
+    if (h->listSnapshot) { rc = avi_snapshot(h, 0, cnt0, h->dAviList[0], seg, st); if (rc != LMPC_OK) return rc; }
+    rc = launch_avi_tiers(h, false, 0, g1, st, theta, x, flag, iters, active, h->dAviList[0], cnt0,
+                          h->dAviList[1], cnt1, nullptr, seg, (long long)nprob, nullptr, &sh);
     if (rc != LMPC_OK) return rc;
+    avi_record(h, sh.stage, sh.n, sh.k, sh.list, 0, 0, g1, sh.lds, h->aviTiersOcc[1], nprob, seg);
+    if (h->listSnapshot) { rc = avi_snapshot(h, 1, cnt1, h->dAviList[1], seg, st); if (rc != LMPC_OK) return rc; }
     return avi_generic(h, nprob, std::min<long long>(tiles, (long long)h->numCU * 4), theta, x, flag, iters, active, nullptr,
                        h->dAviList[1], cnt1, seg, cnt0, st);
 }
@@ -244,6 +307,9 @@ static int avi_generic(lmpc_handle *h, int64_t nprob, long long tiles, const dou
     }
 #undef LMPC_AVI_GO
     HIP_TRY(h, hipGetLastError());
+    const bool ldsc = packBytes <= kAviLdsPack;
+    avi_record(h, LMPC_AVI_SLAB, 0, 0, list != nullptr, ldsc, h->P.prox ? 1 : 0, grid, ldsc ? packBytes : 0,
+               h->aviWaves > 0 ? h->aviWaves : 16, nprob, seg_cap);
     return LMPC_OK;
 }
 
@@ -270,6 +336,8 @@ void avi_release(lmpc_handle *h, bool pack_too) {
     if (h->dAviList[1]) { (void)hipFree(h->dAviList[1]); h->dAviList[1] = nullptr; }
     if (h->dAviCnt) { (void)hipFree(h->dAviCnt); h->dAviCnt = nullptr; }
     h->aviListCap = 0;
+    if (h->dAviSnap) { (void)hipFree(h->dAviSnap); h->dAviSnap = nullptr; }
+    h->aviSnapWords = 0; h->aviSnapSeg[0] = h->aviSnapSeg[1] = 0;
     if (pack_too) {
         if (h->dCa) { (void)hipFree(h->dCa); h->dCa = nullptr; }
         if (h->dSa) { (void)hipFree(h->dSa); h->dSa = nullptr; }

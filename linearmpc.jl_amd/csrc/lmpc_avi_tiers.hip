@@ -11,7 +11,7 @@ namespace {
 template <int N, int KMAX, bool LIST>
 int go(lmpc_handle *h, unsigned grid, hipStream_t st, const double *theta, double *x, int32_t *flag, int32_t *iters,
        uint64_t *active, const int32_t *list_in, const int32_t *count_in, int32_t *list_out, int32_t *count_out,
-       int32_t *count_clear, long long seg_cap, long long nprob, int *occ) {
+       int32_t *count_clear, long long seg_cap, long long nprob, int *occ, AviLaunchShape *shape) {
     auto kern = avi_tiers_kernel<N, KMAX, LIST>;
     // the constants, then the four wavefronts' parked outputs (nout reals a lane)
     const size_t lds = sizeof(double) * ((size_t)AviSmallLds<N>::reals + 4 * (size_t)h->A.nout * 64);
@@ -24,18 +24,21 @@ int go(lmpc_handle *h, unsigned grid, hipStream_t st, const double *theta, doubl
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, h->A, h->dCa, theta, x, flag, iters, active, list_in, count_in,
                        list_out, count_out, count_clear, seg_cap, nprob);
     HIP_TRY(h, hipGetLastError());
+    if (shape) { shape->stage = LMPC_AVI_TIERS; shape->n = N; shape->k = KMAX; shape->list = LIST ? 1 : 0; shape->lds = lds; }
     return LMPC_OK;
 }
+// whole: the launch over the whole batch (LIST == false), else the one behind a list -- also what an occupancy query
+// is answered for: the instantiation the launch that follows will run
 template <int N>
 int go_lane(lmpc_handle *h, unsigned grid, hipStream_t st, const double *theta, double *x, int32_t *flag, int32_t *iters,
             uint64_t *active, const int32_t *list_in, const int32_t *count_in, int32_t *list_out, int32_t *count_out,
-            int32_t *count_clear, long long seg_cap, long long nprob, int *occ) {
+            int32_t *count_clear, long long seg_cap, long long nprob, int *occ, bool whole, AviLaunchShape *shape) {
     const size_t lds = sizeof(double) * (size_t)avi_lane_lds_reals<N>();
     if (lds > 48 * 1024) {
         HIP_TRY(h, hipFuncSetAttribute((const void *)avi_lane_kernel<N, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         HIP_TRY(h, hipFuncSetAttribute((const void *)avi_lane_kernel<N, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     }
-    const bool listed = list_in != nullptr || occ != nullptr;
+    const bool listed = !whole;
     const void *kern = listed ? (const void *)avi_lane_kernel<N, true> : (const void *)avi_lane_kernel<N, false>;
     if (occ) {
         int nb = 0;
@@ -50,6 +53,7 @@ int go_lane(lmpc_handle *h, unsigned grid, hipStream_t st, const double *theta, 
         hipLaunchKernelGGL((avi_lane_kernel<N, false>), dim3(grid), dim3(256), lds, st, h->A, h->dCa, theta, x, flag, iters, active,
                            list_in, count_in, list_out, count_out, count_clear, seg_cap, nprob);
     HIP_TRY(h, hipGetLastError());
+    if (shape) { shape->stage = LMPC_AVI_LANE; shape->n = N; shape->k = 0; shape->list = listed ? 1 : 0; shape->lds = lds; }
     return LMPC_OK;
 }
 }  // namespace
@@ -58,15 +62,16 @@ int go_lane(lmpc_handle *h, unsigned grid, hipStream_t st, const double *theta, 
 // over the whole batch); else the lane kernel on that pass's list.  occ != nullptr: only report the workgroups per CU the instantiation keeps resident.
 int launch_avi_tiers(lmpc_handle *h, bool first, int kfirst, unsigned grid, hipStream_t st, const double *theta, double *x,
                      int32_t *flag, int32_t *iters, uint64_t *active, const int32_t *list_in, const int32_t *count_in,
-                     int32_t *list_out, int32_t *count_out, int32_t *count_clear, long long seg_cap, long long nprob, int *occ) {
+                     int32_t *list_out, int32_t *count_out, int32_t *count_clear, long long seg_cap, long long nprob, int *occ,
+                     AviLaunchShape *shape) {
     const int n = h->A.n;
 #define LMPC_AT(N, K, L) go<N, K, L>(h, grid, st, theta, x, flag, iters, active, list_in, count_in, list_out, count_out, \
-                                     count_clear, seg_cap, nprob, occ)
+                                     count_clear, seg_cap, nprob, occ, shape)
 #define LMPC_AT_N(N)                                                         \
     case N:                                                                  \
         if (!first || kfirst <= 0)                                           \
             return go_lane<N>(h, grid, st, theta, x, flag, iters, active, list_in, count_in, list_out, count_out, \
-                              count_clear, seg_cap, nprob, occ);             \
+                              count_clear, seg_cap, nprob, occ, first, shape); \
         if (kfirst <= 1) return LMPC_AT(N, 1, false);                        \
         if (kfirst == 2 || N == 2) return LMPC_AT(N, 2, false);              \
         return LMPC_AT(N, (N < 3 ? N : 3), false);

@@ -162,6 +162,14 @@ struct lmpc_handle {
     int32_t *dAviList[2] = {nullptr, nullptr};   // the two work lists of the chain, kShards segments each
     int32_t *dAviCnt = nullptr;                  // ... their counters (two sets of kShards, kCountStride apart)
     int64_t aviListCap = 0;
+    int aviChainGroups = 0;     // tuning: cap on the workgroups of the chain's three launches ("avi_chain_groups", 0 = none)
+    // what launch_avi last enqueued (lmpc_avi_launch_info): a ring of the eight most recent launches of the chain
+    int32_t aviRec[LMPC_AVI_INFO_KEPT][LMPC_AVI_INFO_WORDS] = {};
+    long long aviRecN = 0;
+    // option "list_snapshot" on a variational handle: both counter sets and both lists copied aside (lmpc_avi_list_read)
+    int32_t *dAviSnap = nullptr;                 // two blocks of [kShards * kCountStride | kShards * seg_cap] words
+    size_t aviSnapWords = 0;                     // ... words of one block as allocated
+    long long aviSnapSeg[2] = {0, 0};            // ... seg_cap of the snapshot each block holds (0: none)
     lmpc::WaveLayout W{};
     double *dCw = nullptr;
     float *dCwf = nullptr;      // binary32 copy of the wave kernel's pack, built on the first f32 solve
@@ -420,9 +428,13 @@ void avi_fill_settings(lmpc_handle *h);
 int launch_avi(lmpc_handle *h, int64_t nprob, const double *theta, double *x, int32_t *flag, int32_t *iters,
                uint64_t *active, const uint64_t *warm, hipStream_t st);
 void avi_release(lmpc_handle *h, bool pack_too);
+long long avi_list_read(lmpc_handle *h, int which, int32_t *counts, int32_t *list, long long list_words);
+// what launch_avi_tiers enqueued, for the handle's record (lmpc_avi_launch_info)
+struct AviLaunchShape { int stage = 0, n = 0, k = 0, list = 0; size_t lds = 0; };
 int launch_avi_tiers(lmpc_handle *h, bool first, int kfirst, unsigned grid, hipStream_t st, const double *theta, double *x,
                      int32_t *flag, int32_t *iters, uint64_t *active, const int32_t *list_in, const int32_t *count_in,
-                     int32_t *list_out, int32_t *count_out, int32_t *count_clear, long long seg_cap, long long nprob, int *occ);
+                     int32_t *list_out, int32_t *count_out, int32_t *count_clear, long long seg_cap, long long nprob, int *occ,
+                     AviLaunchShape *shape = nullptr);
 
 // what a front pass's launcher enqueued, for the handle's record (lmpc_front_pass_info)
 struct FrontLaunch { int kind = 0, n = 0; long long grid = 0; size_t lds = 0; };

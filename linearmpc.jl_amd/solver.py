@@ -257,6 +257,40 @@ class BatchedQP:
             check(int(seg2) if seg2 < 0 else -1, self._h)
         return counts, lst
 
+    AVI_LAUNCH_FIELDS = ("seq", "stage", "N", "K", "LIST", "LDSC", "PROX", "grid", "lds", "occ", "nprob", "seg_cap")
+    AVI_TIERS, AVI_LANE, AVI_SLAB = 1, 2, 3
+    AVI_LAUNCHES_KEPT = 8
+
+    def avi_launch_info(self, since=0):
+        """The most recent launches of a variational handle's chain (lmpc_avi_launch_info; at most eight are kept: two
+        calls and more), oldest first: one dict per launch with its stage (AVI_TIERS avi_tiers_kernel<N, K, false>,
+        AVI_LANE avi_lane_kernel<N, LIST>, AVI_SLAB avi_kernel<LDSC, PROX>), the template arguments, grid, lds, the
+        occupancy value the grid was sized with, nprob and the lists' seg_cap (0: no list).  "seq" and `since` as in
+        wave_launch_info."""
+        W, K = len(self.AVI_LAUNCH_FIELDS), self.AVI_LAUNCHES_KEPT
+        out = (ctypes.c_int32 * (K * W))()
+        k = lib().lmpc_avi_launch_info(self._h, out, K)
+        if k < 0:
+            check(k, self._h)
+        recs = [dict(zip(self.AVI_LAUNCH_FIELDS, (int(v) for v in out[q * W:(q + 1) * W]))) for q in range(k)]
+        return [r for r in recs if r["seq"] > since]
+
+    def avi_list_read(self, which):
+        """What the chain's launch over the whole batch (which = 0) or its lane kernel (1) left on its work list in the
+        most recent call (lmpc_avi_list_read; needs set_option("list_snapshot", 1) before the call): (counts, list) as
+        work_list_read -- or None if that call made no list."""
+        counts = np.zeros(self.LIST_SHARDS, np.int32)
+        seg = lib().lmpc_avi_list_read(self._h, int(which), _ptr(counts), None, 0)
+        if seg < 0:
+            check(int(seg), self._h)
+        if seg == 0:
+            return None
+        lst = np.zeros((self.LIST_SHARDS, int(seg)), np.int32)
+        seg2 = lib().lmpc_avi_list_read(self._h, int(which), _ptr(counts), _ptr(lst), lst.size)
+        if seg2 != seg:
+            check(int(seg2) if seg2 < 0 else -1, self._h)
+        return counts, lst
+
     def ldp(self):
         """The constant pack the kernels use (row-major) -- what tests hand to the oracle."""
         out = dict(M=np.empty((self.m, self.n)), du=np.empty(self.m), dl=np.empty(self.m),

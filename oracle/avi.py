@@ -124,6 +124,52 @@ def solve_batch(p: AVI, theta, settings: Settings | None = None, warm=None):
     return X, ef, it, act
 
 
+@dataclass
+class Trace:
+    """What the solver loop of oracle_avi_solve_batch_trace saw on each point's path (one entry per point)."""
+    blocked: np.ndarray         # bool: some iteration saw a blocking multiplier (nblock > 0)
+    block_na: np.ndarray        # ... the smallest working-set size at which one did (-1: none)
+    nremove: np.ndarray         # calls of ldu_remove
+    rm_map: np.ndarray          # uint64: bit na (na - 1) / 2 + r for every ldu_remove at position r of na rows
+    singular: np.ndarray        # bool: a singular pivot was met, in ldu_add or in ldu_remove
+    broken: np.ndarray          # bool: the run ended on a row violated inside its own working set
+    max_na: np.ndarray          # the largest working-set size
+
+
+TRACE_WORDS = 8
+
+
+def rm_bit(na, r):
+    """Bit of Trace.rm_map for a removal at position r of a working set of na rows."""
+    return na * (na - 1) // 2 + r
+
+
+def solve_batch_trace(p: AVI, theta, settings: Settings | None = None, warm=None):
+    """solve_batch plus the trace of every point's path: (X, exitflag, iters, active, Trace).  The first four are
+    solve_batch's, bit for bit."""
+    L = _ldp.lib()
+    theta = np.ascontiguousarray(np.asarray(theta, np.float64).reshape(-1, p.nth))
+    N = theta.shape[0]
+    nw = active_words(p.m)
+    X = np.empty((N, p.nout)); ef = np.empty(N, np.int32); it = np.empty(N, np.int32)
+    act = np.zeros((N, nw), np.uint64)
+    tr = np.zeros((N, TRACE_WORDS), np.int64)
+    s = settings if settings is not None else default_settings()
+    wptr = None
+    if warm is not None:
+        warm = np.ascontiguousarray(np.asarray(warm, np.uint64).reshape(N, nw))
+        wptr = ctypes.c_void_p(warm.ctypes.data)
+    c = _cavi(p)
+    L.oracle_avi_solve_batch_trace.restype = None
+    vp = ctypes.c_void_p
+    L.oracle_avi_solve_batch_trace(ctypes.byref(c), ctypes.byref(s), ctypes.c_int64(N), vp(theta.ctypes.data), wptr,
+                                   vp(X.ctypes.data), vp(ef.ctypes.data), vp(it.ctypes.data), vp(act.ctypes.data),
+                                   vp(tr.ctypes.data))
+    trace = Trace(tr[:, 0] != 0, tr[:, 1].copy(), tr[:, 2].copy(), tr[:, 3].copy().view(np.uint64), tr[:, 4] != 0,
+                  tr[:, 5] != 0, tr[:, 6].copy())
+    return X, ef, it, act, trace
+
+
 def qp2prox(H, f, f_theta, A, bu, bl, W, sense, nout, eps, K=None):
     """The pack of the proximal-point mode (eps_prox > 0, H symmetric positive SEMIdefinite): the AVI pack of the
     regularised Hessian H + eps I plus what the outer iteration needs -- (H + eps I)^-1, the full-length affine map

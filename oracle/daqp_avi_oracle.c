@@ -92,7 +92,18 @@ typedef struct {
     int *WS;
     int32_t *sense;
     double soft_slack;
+    int64_t *tr;         /* trace of the solve in progress (oracle_avi_solve_batch_trace), NULL otherwise: TR_* words */
 } awork;
+
+/* words of a point's trace: what the final outputs do not tell about the path */
+#define TR_BLOCKED 0     /* 1 = some iteration saw a blocking multiplier (nblock > 0)                                */
+#define TR_BLOCK_NA 1    /* ... the smallest working-set size at which one did (-1: none)                            */
+#define TR_NREMOVE 2     /* calls of ldu_remove                                                                       */
+#define TR_RMMAP 3       /* bit na (na - 1) / 2 + r for every ldu_remove at position r of na rows (while the bit is < 64)     */
+#define TR_SINGULAR 4    /* 1 = a singular pivot was met, in ldu_add or in ldu_remove                                 */
+#define TR_BROKEN 5      /* 1 = the run ended on a row violated inside its own working set (EXIT_CYCLE)               */
+#define TR_MAXNA 6       /* the largest working-set size                                                              */
+#define TR_WORDS 8
 
 static awork *awork_new(int n, int m, int cap) {
     awork *w = (awork *)calloc(1, sizeof(awork));
@@ -146,9 +157,11 @@ static void ldu_add(awork *w, const oracle_avi *p, const avi_settings *s, int j)
     const int is_soft = (w->sense[j] & SENSE_SOFT) != 0;
     if (dnew < s->zero_tol || (!is_soft && na - w->nsoft_act >= w->n)) {
         w->D[na] = 0.0; w->Dinv[na] = 0.0; w->sing = na;
+        if (w->tr) w->tr[TR_SINGULAR] = 1;
     } else {
         w->D[na] = dnew; w->Dinv[na] = 1.0 / dnew;
     }
+    if (w->tr && na + 1 > w->tr[TR_MAXNA]) w->tr[TR_MAXNA] = na + 1;
     w->WS[na] = j; w->lam[na] = 0.0; w->ls[na] = 0.0;
     w->sense[j] |= SENSE_ACTIVE;
     w->nsoft_act += is_soft;
@@ -159,6 +172,11 @@ static void ldu_add(awork *w, const oracle_avi *p, const avi_settings *s, int j)
 static void ldu_remove(awork *w, const avi_settings *s, int r) {
     const int na = w->na, nup = na - r - 1;
     double alpha = w->D[r];
+    if (w->tr) {
+        const int bit = na * (na - 1) / 2 + r;
+        w->tr[TR_NREMOVE]++;
+        if (bit < 64) w->tr[TR_RMMAP] = (int64_t)((uint64_t)w->tr[TR_RMMAP] | ((uint64_t)1 << bit));
+    }
     for (int t = 0; t < nup; t++) {
         w->pv[t] = w->L[TRI(r + 1 + t) + r];
         w->qv[t] = w->Ut[TRI(r + 1 + t) + r];
@@ -178,6 +196,7 @@ static void ldu_remove(awork *w, const avi_settings *s, int r) {
         const double dbar = fma(alpha * pt, qt, dold);
         if (dbar < s->zero_tol) {
             w->D[i] = 0.0; w->Dinv[i] = 0.0; w->sing = i;
+            if (w->tr) w->tr[TR_SINGULAR] = 1;
             for (int q = i + 1; q < na - 1; q++) { w->D[q] = w->D[q + 1]; w->Dinv[q] = w->Dinv[q + 1]; }
             break;
         }
@@ -205,6 +224,7 @@ static int avi_solve_shift(awork *w, const oracle_avi *p, const avi_settings *s,
                            const uint64_t *warm, int32_t *iters, const double *xk, double eps) {
     const int n = p->n, m = p->m, nth = p->nth;
     int flag = EXIT_ITERLIMIT, iter = 1;
+    if (w->tr) { for (int q = 0; q < TR_WORDS; q++) w->tr[q] = 0; w->tr[TR_BLOCK_NA] = -1; }
     for (int j = 0; j < m; j++) {                               /* mpc_update_qp.c:1-10 */
         double sh = 0.0;
         for (int t = 0; t < nth; t++) sh = fma(p->Dth[(size_t)j * nth + t], theta[t], sh);
@@ -266,6 +286,10 @@ static int avi_solve_shift(awork *w, const oracle_avi *p, const avi_settings *s,
                 const double cand = -w->lam[i] / (w->ls[i] - w->lam[i]);
                 if (nblock == 0 || cand < alpha) { alpha = cand; rm = i; }
                 nblock++;
+            }
+            if (w->tr && nblock) {
+                if (!w->tr[TR_BLOCKED] || na < w->tr[TR_BLOCK_NA]) w->tr[TR_BLOCK_NA] = na;
+                w->tr[TR_BLOCKED] = 1;
             }
             /* the iterate now (from lam) and the target of this step (from lam*), soft slack at the target */
             double soft = 0.0;
@@ -353,11 +377,16 @@ static int avi_solve_shift(awork *w, const oracle_avi *p, const avi_settings *s,
                 nblock++;
             }
             if (nblock == 0) { flag = EXIT_INFEASIBLE; break; }
+            if (w->tr) {
+                if (!w->tr[TR_BLOCKED] || na < w->tr[TR_BLOCK_NA]) w->tr[TR_BLOCK_NA] = na;
+                w->tr[TR_BLOCKED] = 1;
+            }
             for (int i = 0; i < na; i++) w->lam[i] = fma(alpha, w->ls[i], w->lam[i]);
             ldu_remove(w, s, rm);
         }
     }
 done:
+    if (w->tr && flag == EXIT_CYCLE) w->tr[TR_BROKEN] = 1;
     if (iters) *iters = iter;
     return flag;
 }
@@ -385,8 +414,11 @@ static void avi_outputs(const awork *w, const oracle_avi *p, const double *theta
     }
 }
 
-void oracle_avi_solve_batch(const oracle_avi *p, const avi_settings *s, int64_t N, const double *theta,
-                            const uint64_t *warm, double *x, int32_t *exitflag, int32_t *iters, uint64_t *active) {
+/* oracle_avi_solve_batch with the path's trace: trace = N x TR_WORDS 64-bit words (NULL: none), written by the solver
+ * loop as it runs.  The other outputs are those of oracle_avi_solve_batch, bit for bit (the trace only observes). */
+void oracle_avi_solve_batch_trace(const oracle_avi *p, const avi_settings *s, int64_t N, const double *theta,
+                                  const uint64_t *warm, double *x, int32_t *exitflag, int32_t *iters, uint64_t *active,
+                                  int64_t *trace) {
     int nsoft = 0;
     for (int j = 0; j < p->m; j++) nsoft += (p->sense[j] & SENSE_SOFT) ? 1 : 0;
     awork *w = awork_new(p->n, p->m, p->n + 1 + nsoft);
@@ -394,12 +426,18 @@ void oracle_avi_solve_batch(const oracle_avi *p, const avi_settings *s, int64_t 
     for (int64_t q = 0; q < N; q++) {
         const double *th = theta + q * p->nth;
         int32_t it = 0;
+        w->tr = trace ? trace + q * TR_WORDS : NULL;
         const int ef = avi_solve(w, p, s, th, warm ? warm + q * nwords : NULL, &it);
         avi_outputs(w, p, th, x + q * p->nout, active ? active + q * nwords : NULL, nwords);
         exitflag[q] = ef;
         if (iters) iters[q] = it;
     }
     awork_free(w);
+}
+
+void oracle_avi_solve_batch(const oracle_avi *p, const avi_settings *s, int64_t N, const double *theta,
+                            const uint64_t *warm, double *x, int32_t *exitflag, int32_t *iters, uint64_t *active) {
+    oracle_avi_solve_batch_trace(p, s, N, theta, warm, x, exitflag, iters, active, NULL);
 }
 
 /* Closed loop, as oracle_simulate (daqp_ldp_oracle.c) with the AVI solve: theta = [x; r; uprev], u = first nu outputs,
