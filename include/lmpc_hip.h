@@ -529,6 +529,21 @@ int lmpc_wave_launch_info(const lmpc_handle *h, int32_t *out, int max);
 #define LMPC_ROW_INFO_WORDS 20
 int lmpc_row_launch_info(const lmpc_handle *h, int32_t *out, int max);
 
+/* The one-launch kernel (fast_kernel / fast_kernel_multi): the handle's most recent launch of it, LMPC_FAST_INFO_WORDS
+ * words; returns 1, 0 if the handle never launched it (< 0: error).  Host memory only, written when the launch is
+ * enqueued.  Words:
+ *    [0] running number of the launch in the handle's life (1, 2, ...)
+ *    [1] form: 0 plain, 1 gather (the generated controller's call), 2 several batches in one launch
+ *    [2] 1 = staged write-out: x and the exit flags of a workgroup's tiles are kept in LDS and stored once, as whole
+ *        lines, at the workgroup's end (one output, no iters / active array, no gather, a static split, and LDS that
+ *        keeps the shape's workgroups per CU; by default only under "in_flight" >= 2, see "fast_stage"); 0 = stored where found
+ *    [3] tiles of 64 problems a workgroup's queue holds   [4] streaming wavefronts per workgroup
+ *    [5] LDS-DMA ring depth (0 = records through registers)   [6] workgroups per batch (grid x)   [7] batches (grid y)
+ *    [8] dynamic LDS bytes per workgroup   [9] tiles per workgroup handed out through tickets ("fast_dyn"; 0 = static)
+ * For tests and benchmark reports. */
+#define LMPC_FAST_INFO_WORDS 10
+int lmpc_fast_launch_info(const lmpc_handle *h, int32_t *out);
+
 /* The same for the pass that runs IN FRONT of an iterating kernel and fills its work list (the screening pass or the
  * tiers pass, qp_tiers_kernel): the handle's four most recent front-pass launches, OLDEST first, LMPC_FRONT_INFO_WORDS
  * words each; returns how many (< 0: error).  Host memory only, written when the launch is enqueued.  A call without a
@@ -609,7 +624,9 @@ int lmpc_profile_read(lmpc_handle *h, double avg_ms[3]);
  * (m == ms == n <= 5, up to 16 parameters -- 8 for n = 5 --, cold start) are solved by ONE kernel that streams the batch and
  * runs the iterations underneath (0 = the two-kernel form below); "fast_nstr" 1..4 = streaming wavefronts per
  * workgroup of that kernel (default 3; 4 suits several batches in flight), "fast_tiles" = tiles of 64 problems per workgroup
- * (default: one resident round of workgroups; 28 suits three 10^6-point batches in flight); "lane_straight" (default 1) =
+ * (default: one resident round of workgroups; 28 suits three 10^6-point batches in flight); "fast_stage" (default -1 =
+ * where it applies -- see lmpc_fast_launch_info -- with "in_flight" >= 2; 1 = wherever it applies; 0 = never) = that kernel
+ * keeps x and the exit flags of a workgroup's tiles in LDS and stores them once, as whole lines; "lane_straight" (default 1) =
  * straight-line first tier in the boxed iterating kernels.  "screen" (default 1) = run cold-start batches through the streaming
  * screening pass before the iterating kernel; 0 = iterating kernel only.  "screen_wave" (default 1) = the same pass in
  * front of the wavefront kernel (binary64 problems without binary rows and without initially active rows, 1..32

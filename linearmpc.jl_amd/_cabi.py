@@ -32,7 +32,7 @@ SYMBOLS = (
     "lmpc_solve_batch_multi", "lmpc_solve_batch_multi_device", "lmpc_multi_last_error", "lmpc_free_multi",
     "lmpc_pin_host", "lmpc_unpin_host", "lmpc_release_scratch", "lmpc_check",
     "lmpc_distinct_active_sets_device", "lmpc_distinct_active_sets_overflowed", "lmpc_wave_stats", "lmpc_wave_launch_info",
-    "lmpc_row_launch_info", "lmpc_front_pass_info", "lmpc_work_list_read", "lmpc_avi_launch_info", "lmpc_avi_list_read",
+    "lmpc_row_launch_info", "lmpc_fast_launch_info", "lmpc_front_pass_info", "lmpc_work_list_read", "lmpc_avi_launch_info", "lmpc_avi_list_read",
     "lmpc_setup_ex", "lmpc_is_avi", "lmpc_get_avi", "lmpc_transform_avi", "lmpc_multi_set_option", "lmpc_discover_regions_device", "lmpc_reserve", "lmpc_get_prox",
     "lmpc_explicit_default_opts", "lmpc_explicit_build_ldp", "lmpc_explicit_build", "lmpc_explicit_info",
     "lmpc_explicit_region", "lmpc_explicit_blob", "lmpc_explicit_training", "lmpc_explicit_locate_host",
@@ -249,6 +249,9 @@ def lib():
     if hasattr(L, "lmpc_row_launch_info"):
         L.lmpc_row_launch_info.argtypes = [vp, vp, i32]
         L.lmpc_row_launch_info.restype = i32
+    if hasattr(L, "lmpc_fast_launch_info"):
+        L.lmpc_fast_launch_info.argtypes = [vp, vp]
+        L.lmpc_fast_launch_info.restype = i32
     if hasattr(L, "lmpc_front_pass_info"):
         L.lmpc_front_pass_info.argtypes = [vp, vp, i32]
         L.lmpc_front_pass_info.restype = i32

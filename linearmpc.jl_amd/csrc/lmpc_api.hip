@@ -1160,6 +1160,13 @@ int lmpc_row_launch_info(const lmpc_handle *h, int32_t *out, int max) {
     return (int)k;
 }
 
+int lmpc_fast_launch_info(const lmpc_handle *h, int32_t *out) {
+    if (!h || !out) return LMPC_ERR_BADARG;
+    if (h->fastRecN == 0) return 0;
+    std::memcpy(out, h->fastRec, sizeof(int32_t) * LMPC_FAST_INFO_WORDS);
+    return 1;
+}
+
 int lmpc_front_pass_info(const lmpc_handle *h, int32_t *out, int max) {
     if (!h || !out || max < 0) return LMPC_ERR_BADARG;
     long long k = h->frontRecN < 4 ? h->frontRecN : 4;
@@ -1305,11 +1312,13 @@ int lmpc_set_option(lmpc_handle *h, const char *name, int value) {
     if (std::strcmp(name, "fast_nstr") == 0) { h->fastNstr = value; return LMPC_OK; }
     if (std::strcmp(name, "fast_dma") == 0) { h->fastDma = value; return LMPC_OK; }
     if (std::strcmp(name, "fast_dyn") == 0) { h->fastDyn = value; return LMPC_OK; }
+    if (std::strcmp(name, "fast_stage") == 0) { h->fastStage = value < 0 ? -1 : (value != 0); return LMPC_OK; }
     if (std::strcmp(name, "in_flight") == 0) {
         // hint: how many independent batches the caller keeps in flight on this GPU (one handle and stream each).
         // From two on a call no longer owns the chip: the one-launch kernel then runs with all four wavefronts of
         // a workgroup streaming and 28 tiles per workgroup, the iterating kernel with 64-lane workgroups
         // (same-box sweeps, three 1e6-point batches in flight: 17.1 us/step at the stand-alone shape, 15.0 with this)
+        h->inFlight = value >= 2 ? value : 1;
         h->fastNstr = value >= 2 ? 4 : 0;
         h->fastTiles = value >= 2 ? 28 : 0;
         h->laneBlock = value >= 2 ? 64 : 0;

@@ -24,6 +24,29 @@ bool fast_covers(const lmpc_handle *h) {
            h->S.iter_limit > kmax + 1 && h->S.cycle_tol >= kmax + 1;
 }
 
+// Staged write-out (fast_staged_kernel / fast_staged_kernel_multi): x and the flags of a workgroup's tiles wait in LDS
+// for one store of whole lines.  By default only with several batches in flight ("in_flight" >= 2), where it is worth
+// 11 % of a step (14.75 -> 13.07 us, profiles/fast_whole_lines.md); "fast_stage" 1 takes it wherever it applies, 0
+// never.  (A call issued alone measured 20.7 us with "fast_stage" 1 against 22.6 by default, one job: a candidate for the
+// default, which the whole suite would then have to be run on.)
+static bool fast_stage_wanted(const lmpc_handle *h) { return h->fastStage > 0 || (h->fastStage < 0 && h->inFlight >= 2); }
+// It is taken only where the extra 9 bytes per problem leave the shape the workgroups per CU it runs at -- four with
+// four streaming wavefronts (the batches-in-flight shape), else the kFastGridWaves the default grid is sized for, or
+// the fewer that fit unstaged.
+static bool fast_stage_fits(size_t plain, size_t staged, int nstr) {
+    auto fit = [](size_t b) { const size_t k = kFastCuLds / b; return (int)(k > LMPC_FAST_WAVES ? LMPC_FAST_WAVES : k); };
+    const int want = nstr == 4 ? LMPC_FAST_WAVES : kFastGridWaves;
+    const int need = fit(plain) < want ? fit(plain) : want;
+    return fit(staged) >= need;
+}
+// what was enqueued, for lmpc_fast_launch_info (include/lmpc_hip.h lists the words)
+static void fast_record(lmpc_handle *h, int form, bool stage, int Rq, int nstr, int dk, unsigned grid, int nb, size_t lds, int D) {
+    h->fastRecN++;
+    int32_t *r = h->fastRec;
+    r[0] = (int32_t)(h->fastRecN & 0x7fffffff); r[1] = form; r[2] = stage ? 1 : 0; r[3] = Rq; r[4] = nstr; r[5] = dk;
+    r[6] = (int32_t)grid; r[7] = nb; r[8] = (int32_t)lds; r[9] = D;
+}
+
 template <int NTHMAX, int NT, int N, bool GATHER>
 static int launch_fast_t(lmpc_handle *h, int64_t nprob, const double *theta, double *x, int32_t *flag, int32_t *iters,
                          uint64_t *active, hipStream_t st) {
@@ -74,7 +97,12 @@ static int launch_fast_t(lmpc_handle *h, int64_t nprob, const double *theta, dou
     // 16-byte pieces: a batch that does not start on a 16-byte boundary (a view into a larger array) or whose tiles
     // are not multiples of 16 bytes takes its records through registers
     if ((reinterpret_cast<uintptr_t>(theta) & 15u) != 0 || (fast_tile_bytes(NT) & 15u) != 0) dk = 0;
-    const size_t lds = dk ? fast_lds_bytes_dma(N, Rq, NTHMAX, NT, nstr, dk) : fast_lds_bytes(N, Rq, NTHMAX);
+    const size_t ldsPlain = dk ? fast_lds_bytes_dma(N, Rq, NTHMAX, NT, nstr, dk) : fast_lds_bytes(N, Rq, NTHMAX);
+    // staged write-out: one output, no optional output, records from a buffer, a static split ("fast_stage" 0: never)
+    bool stage = !GATHER && D == 0 && h->L.nout == 1 && !iters && !active && fast_stage_wanted(h);
+    const size_t ldsStage = dk ? fast_lds_bytes_dma(N, Rq, NTHMAX, NT, nstr, dk, true) : fast_lds_bytes(N, Rq, NTHMAX, true);
+    if (stage && !fast_stage_fits(ldsPlain, ldsStage, nstr)) stage = false;
+    const size_t lds = stage ? ldsStage : ldsPlain;
     int32_t *ctrNow = nullptr, *ctrNext = nullptr;
     if (D) {
         if (!h->dFastCtr) {
@@ -86,8 +114,10 @@ static int launch_fast_t(lmpc_handle *h, int64_t nprob, const double *theta, dou
         h->fastCtrSet ^= 1;
     }
     auto kern = fast_kernel<NTHMAX, NT, N, GATHER>;
+    auto kernStaged = fast_staged_kernel<NTHMAX, NT, N>;
     if (lds > 48 * 1024)
-        HIP_TRY(h, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        HIP_TRY(h, hipFuncSetAttribute(stage ? (const void *)kernStaged : (const void *)kern,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     if (!h->dFastErr) {
 #ifdef LMPC_FAST_TRACE
         const size_t eb = 64 + sizeof(long long) * 8 * 4 * 65536;
@@ -104,10 +134,15 @@ static int launch_fast_t(lmpc_handle *h, int64_t nprob, const double *theta, dou
         HIP_TRY(h, hipHostGetDevicePointer(reinterpret_cast<void **>(&h->dFastErr), hp, 0));
 #endif
     }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, h->L, h->dC, theta, x, flag, iters,
-                       active, (long long)nprob, Rq, nstr, h->dFastErr, h->fastSpinLimit > 0 ? h->fastSpinLimit - 1 : kFastSpinLimit,
-                       dk, Rs, Dcap, ctrNow, ctrNext);
+    const int spin = h->fastSpinLimit > 0 ? h->fastSpinLimit - 1 : kFastSpinLimit;
+    if (stage)
+        hipLaunchKernelGGL(kernStaged, dim3(grid), dim3(256), lds, st, h->L, h->dC, theta, x, flag, (long long)nprob, Rq, nstr,
+                           h->dFastErr, spin, dk);
+    else
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, h->L, h->dC, theta, x, flag, iters, active, (long long)nprob, Rq,
+                           nstr, h->dFastErr, spin, dk, Rs, Dcap, ctrNow, ctrNext);
     HIP_TRY(h, hipGetLastError());
+    fast_record(h, GATHER ? 1 : 0, stage, Rq, nstr, dk, grid, 1, lds, D);
 #ifdef LMPC_FAST_TRACE
     if (const char *f = std::getenv("LMPC_FAST_TRACE_FILE")) {
         std::vector<long long> tr((size_t)grid * 4 * 8);
@@ -142,8 +177,12 @@ static int launch_fast_multi_t(lmpc_handle *h, int nb, int64_t nprob, const doub
         B.theta[b] = theta[b]; B.x[b] = x[b]; B.flag[b] = flag[b];
         if ((reinterpret_cast<uintptr_t>(theta[b]) & 15u) != 0) dk = 0;
     }
-    const size_t lds = dk ? fast_lds_bytes_dma(N, R, NTHMAX, NT, nstr, dk) : fast_lds_bytes(N, R, NTHMAX);
-    auto kern = fast_kernel_multi<NTHMAX, NT, N>;
+    const size_t ldsPlain = dk ? fast_lds_bytes_dma(N, R, NTHMAX, NT, nstr, dk) : fast_lds_bytes(N, R, NTHMAX);
+    const size_t ldsStage = dk ? fast_lds_bytes_dma(N, R, NTHMAX, NT, nstr, dk, true) : fast_lds_bytes(N, R, NTHMAX, true);
+    // (x and the flags alone, a static split: staged unless the output has several columns or the LDS does not allow it)
+    const bool stage = h->L.nout == 1 && fast_stage_wanted(h) && fast_stage_fits(ldsPlain, ldsStage, nstr);
+    const size_t lds = stage ? ldsStage : ldsPlain;
+    auto kern = stage ? fast_staged_kernel_multi<NTHMAX, NT, N> : fast_kernel_multi<NTHMAX, NT, N>;
     if (lds > 48 * 1024)
         HIP_TRY(h, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     if (!h->dFastErr) {
@@ -156,6 +195,7 @@ static int launch_fast_multi_t(lmpc_handle *h, int nb, int64_t nprob, const doub
     hipLaunchKernelGGL(kern, dim3(grid, (unsigned)nb), dim3(256), lds, st, h->L, h->dC, B, (long long)nprob, R, nstr, h->dFastErr,
                        h->fastSpinLimit > 0 ? h->fastSpinLimit - 1 : kFastSpinLimit, dk);
     HIP_TRY(h, hipGetLastError());
+    fast_record(h, 2, stage, R, nstr, dk, grid, nb, lds, 0);
     return LMPC_OK;
 }
 

@@ -20,6 +20,11 @@
 // reserved slot to be written (slots start at -1; a producer writes its slots right after reserving them).
 // Every wait is bounded by a spin limit that raises an error flag instead of hanging.
 //
+// Outputs: a call with one output per problem and no iters / active array (the plain and the several-batches launch
+// on a static split; by default only under the hint "in_flight" >= 2, see launch_fast_t) keeps x and the exit flags of a
+// workgroup's tiles in LDS and stores them once, as whole lines, at the workgroup's end (fast_staged_kernel, see fast_body); every
+// other call stores them where they are found -- the streaming wavefront its finished lanes, the solving lanes theirs.
+//
 // Results are those of the two-launch form bit for bit: the screening test, the tiers and lane_loop are the
 // same code or the same fma chains.
 //
@@ -83,15 +88,22 @@ __host__ __device__ constexpr int fast_scr_doubles(int N, int NTHMAX) { return (
 #define LMPC_FAST_PAY 256
 #endif
 constexpr int kFastPay = LMPC_FAST_PAY;
-__host__ __device__ constexpr size_t fast_lds_bytes(int N, int R, int NTHMAX) {
+// (stage: the staged write-out below -- the hand-over loses its x-shift column, x and the flags of the workgroup's
+// R tiles are kept behind the queue: 8 + 1 bytes per problem)
+__host__ __device__ constexpr size_t fast_lds_bytes(int N, int R, int NTHMAX, bool stage = false) {
     return sizeof(double) * (size_t)(((N * N + N * (N + 1) / 2 + 2 * N + 1) & ~1) + fast_scr_doubles(N, NTHMAX) +
-                                     (size_t)kFastPay * (N + 1)) +
-           sizeof(int32_t) * ((size_t)R * 64 + 4);
+                                     (size_t)kFastPay * (N + (stage ? 0 : 1))) +
+           sizeof(int32_t) * ((size_t)R * 64 + 4) + (stage ? (size_t)R * 64 * (sizeof(double) + 1) : 0);
 }
 // ... plus the streaming wavefronts' LDS-DMA rings behind it (dk slots of one tile per streaming wavefront)
-__host__ __device__ constexpr size_t fast_lds_bytes_dma(int N, int R, int NTHMAX, int NT, int nstr, int dk) {
-    return fast_lds_bytes(N, R, NTHMAX) + (size_t)dk * nstr * fast_tile_bytes(NT);
+__host__ __device__ constexpr size_t fast_lds_bytes_dma(int N, int R, int NTHMAX, int NT, int nstr, int dk, bool stage = false) {
+    return fast_lds_bytes(N, R, NTHMAX, stage) + (size_t)dk * nstr * fast_tile_bytes(NT);
 }
+// LDS of one CU (gfx950) and the headline shapes' budget with the staged write-out: four workgroups per CU at the
+// in-flight shape (28 tiles, four streaming wavefronts, registers), three at the stand-alone one (21 tiles, rings of two)
+constexpr size_t kFastCuLds = 160 * 1024;
+static_assert(4 * fast_lds_bytes(5, 28, 8, true) <= kFastCuLds, "in-flight shape: four staged workgroups per CU");
+static_assert(3 * fast_lds_bytes_dma(5, 21, 8, 7, 3, 2, true) <= kFastCuLds, "stand-alone shape: three staged workgroups per CU");
 
 // The generic loop of lane_kernel (lane_loop) for a lane the straight-line tiers did not finish -- about one problem
 // in 10^6 of an iterating batch -- as a function of its own.  Inlined, its working set (LaneState<N, N>: ~60 registers
@@ -144,7 +156,7 @@ __device__ __attribute__((noinline)) FastFallback<N> fast_fallback(const FastLoo
 // are written once, by whichever of the two finishes the problem -- after its own reads, so the in/out array needs
 // no copy.
 // (the kernel's body: shared by the one-batch launch and the several-batches launch below)
-template <int NTHMAX, int NT, int N, bool GATHER = false>
+template <int NTHMAX, int NT, int N, bool GATHER = false, bool STAGE = false>
 __device__ __forceinline__ void fast_body(
     const PackLayout &P, const double *__restrict__ C, const double *__restrict__ theta,
     double *__restrict__ X, int32_t *__restrict__ exitflag, int32_t *__restrict__ iters,
@@ -155,9 +167,22 @@ __device__ __forceinline__ void fast_body(
     extern __shared__ __align__(16) double lds[];
     double *sconst = lds;                                      // M, G, du0, dl0 (as in the pack, as lane_kernel keeps them)
     double *sScr = sconst + ((nconst + 1) & ~1);               // screening constants (see fast_scr_doubles)
+    // STAGED WRITE-OUT (STAGE: the body of fast_staged_kernel / fast_staged_kernel_multi, kernels of their own so that
+    // fast_kernel and fast_kernel_multi are compiled exactly as without it -- as a runtime argument of those the flag cost
+    // every caller scalar registers through the solving pass and a call issued alone 1 us; the host launches the staged
+    // kernels for one output, no iters / active, no gather, a static split): x and the flag of every problem of the workgroup's tiles live in LDS (sX, sF: slot = problem - first
+    // problem of the workgroup) until the workgroup's end, and are stored ONCE, as whole consecutive lines, by all 256
+    // threads.  Unstaged, a line of X is written in part by the streaming wavefront (its finished lanes) and again in
+    // part, a workgroup's life later, by the solving lanes: two partial writes of a line that has left the L2 in between.
+    constexpr bool stage = STAGE;
+    constexpr int payw = stage ? N : N + 1;                        // (staged: the x shift is handed over in sX)
     double *sPay = sScr + fast_scr_doubles(N, NTHMAX);         // (b_0 .. b_{N-1}, x shift) of the first kFastPay queue positions
-    int32_t *ring = reinterpret_cast<int32_t *>(sPay + (size_t)kFastPay * (N + 1));
+    // (the flags at a compile-time offset and x right behind ctrl: no address of its own to keep in a scalar register)
+    signed char *sF = reinterpret_cast<signed char *>(sPay + (size_t)kFastPay * payw);  // staged: exit flags of the R tiles' problems
+    int32_t *ring = reinterpret_cast<int32_t *>(sF + (stage ? R * 64 : 0));
     int *ctrl = reinterpret_cast<int *>(ring + R * 64);        // [0] write index, [1] read index, [2] producers done
+    double *sX = reinterpret_cast<double *>(ctrl + 4);         // staged: x (a queued problem's x shift until it is solved)
+    char *dma0 = reinterpret_cast<char *>(sX + (stage ? R * 64 : 0));                  // the LDS-DMA rings, if any
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nth = P.nth;
@@ -307,12 +332,24 @@ __device__ __forceinline__ void fast_body(
             // orders this store in front of the solving lane's final one (issued after the publish, the
             // provisional flag could land last and leave a solved problem at -8) --, queued ones the provisional
             // EXIT_UNFINISHED that the solving lane overwrites: should a bounded wait below ever run out, no caller reads a stale flag as success (the
-            // reference asserts exitflag >= 1, utils.jl:46); an unmasked store of whole lines, as screen_kernel's
+            // reference asserts exitflag >= 1, utils.jl:46); an unmasked store of whole lines, as screen_kernel's.
+            // Staged: both go to the problem's LDS slot instead -- a hard lane's slot holds its x SHIFT until the solving
+            // lane replaces it with x -- and nothing is stored to memory here.  The release / acquire argument around
+            // the provisional flag does not apply on that path: a slot is written by this lane, then (behind the ring's
+            // release / acquire) by the solving lane, and read after the workgroup's closing barrier.
+            if (stage) {
+                if (valid) {
+                    const int slot = (int)(tile - t0) * 64 + lane;
+                    sX[slot] = hard ? sh : 0.0 + sh;
+                    sF[slot] = (signed char)(hard ? EXIT_UNFINISHED : EXIT_OPTIMAL);
+                }
+            } else {
 #ifdef LMPC_FAST_NT_STORES
             if (valid) __builtin_nontemporal_store(hard ? EXIT_UNFINISHED : EXIT_OPTIMAL, &exitflag[pid]);
 #else
             if (valid) exitflag[pid] = hard ? EXIT_UNFINISHED : EXIT_OPTIMAL;
 #endif
+            }
             if (mask != 0ull) {
                 int base = 0;
                 if (lane == 0) base = __hip_atomic_fetch_add(&ctrl[0], __popcll(mask), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -320,16 +357,16 @@ __device__ __forceinline__ void fast_body(
                 if (hard) {
                     const int pos = base + __popcll(mask & ((1ull << lane) - 1ull));
                     if (pos < kFastPay) {
-                        double *pay = sPay + pos * (N + 1);
+                        double *pay = sPay + pos * payw;
 #pragma unroll
                         for (int j = 0; j < N; j++) pay[j] = bq[j];
-                        pay[N] = sh;
+                        if (!stage) pay[N] = sh;
                     }
                     // (release: the payload is in LDS before the index that announces it)
                     __hip_atomic_store(&ring[pos], (int32_t)(pid - base0), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
                 }
             }
-            if (valid && !hard) {
+            if (!stage && valid && !hard) {
                 if (P.nout == 1) {
 #ifdef LMPC_FAST_NT_STORES
                     __builtin_nontemporal_store(0.0 + sh, &X[pid]);
@@ -359,7 +396,7 @@ __device__ __forceinline__ void fast_body(
             constexpr int PIECES = (int)((TB + 1023) / 1024);
             constexpr unsigned LASTB = TB - (PIECES - 1) * 1024u;            // bytes of the last piece (16 per lane)
             typedef const double __attribute__((address_space(3))) *lds_cdp;
-            char *dring = reinterpret_cast<char *>(ctrl + 4) + (size_t)role * dk * TB;
+            char *dring = dma0 + (size_t)role * dk * TB;
             const unsigned dbase = (unsigned)(size_t)(lds_cdp) reinterpret_cast<double *>(dring);
             const char *tbytes = reinterpret_cast<const char *>(theta);
             // whole tiles only: the batch's last, partial tile (one per call) takes the register path below
@@ -554,11 +591,12 @@ __device__ __forceinline__ void fast_body(
 #pragma unroll
         for (int j = 0; j < N; j++) b[j] = 0.0;
         if (handed) {
-            const double *pay = sPay + (start + (mine ? lane : 0)) * (N + 1);
+            const double *pay = sPay + (start + (mine ? lane : 0)) * payw;
 #pragma unroll
             for (int j = 0; j < N; j++) b[j] = pay[j];
-            sh0 = pay[N];
+            if (!stage) sh0 = pay[N];
         }
+        // (staged: the x shift of EVERY queued problem waits in its sX slot and is read where x is formed, below)
         if (__any(mine && !handed)) {
             double th0[NT];
             load_record(pid, th0);
@@ -573,10 +611,12 @@ __device__ __forceinline__ void fast_body(
                 for (int t = 0; t < NT; t++) acc = __builtin_fma(dj[j * NTHMAX + t], th0[t], acc);
                 b[j] = handed ? b[j] : acc;
             }
-            const double *xk = C + P.oXthP;
+            if constexpr (!stage) {                            // (staged: the shift is in the slot, nothing to re-form)
+                const double *xk = C + P.oXthP;
 #pragma unroll
-            for (int t = 0; t < NT; t++) sh1 = __builtin_fma(xk[t], th0[t], sh1);
-            sh0 = handed ? sh0 : sh1;
+                for (int t = 0; t < NT; t++) sh1 = __builtin_fma(xk[t], th0[t], sh1);
+                sh0 = handed ? sh0 : sh1;
+            }
         }
 #ifdef LMPC_FAST_TRACE
         if (npass == 1) { if (lane == 0) trc[4] = (long long)(b[0] != 12345.678 ? wall_clock64() : 0); }
@@ -607,7 +647,14 @@ __device__ __forceinline__ void fast_body(
             flag = r.flag; iter = r.iter; act = r.act; low = r.low;
         }
 #endif
-        if (mine) {
+        if (mine && stage) {
+            double xs = 0.0;
+#pragma unroll
+            for (int c = 0; c < N; c++) xs = __builtin_fma(C[P.oRout + c], u[c], xs);
+            const unsigned slot = (unsigned)rel;               // (the static split's queue entries ARE slots)
+            sX[slot] = xs + sX[slot];                          // the slot held the x shift the streaming lane left
+            sF[slot] = (signed char)flag;                      // (exit flags are -8 ... 2)
+        } else if (mine) {
             if (P.nout == 1) {
                 double xs = 0.0;
 #pragma unroll
@@ -625,6 +672,18 @@ __device__ __forceinline__ void fast_body(
 #ifdef LMPC_FAST_PRIO
         __builtin_amdgcn_s_setprio(0);
 #endif
+    }
+    // Staged write-out: every wavefront of the workgroup gets here -- the two bounded-wait exits above leave the loop,
+    // they do not return -- and the workgroup's contiguous range of X and of exitflag is stored from LDS, consecutive
+    // lanes to consecutive elements (no more alignment asked than of the unstaged stores).  A problem a spent wait
+    // left unsolved keeps its provisional EXIT_UNFINISHED (and its x shift as x), as on the unstaged path.
+    if (stage) {
+        __syncthreads();
+        const long long g0 = t0 * 64;
+        const int cnt = (int)((t1 * 64 < nprob ? t1 * 64 : nprob) - g0);
+        // (nontemporal: written once, read by nobody on the device; 13.94 against 14.11 us per step, three batches in flight)
+        for (int i = tid; i < cnt; i += 256) __builtin_nontemporal_store(sX[i], &X[g0 + i]);
+        for (int i = tid; i < cnt; i += 256) __builtin_nontemporal_store((int32_t)sF[i], &exitflag[g0 + i]);
     }
     LMPC_TRC(6);
 #ifdef LMPC_FAST_TRACE
@@ -645,6 +704,16 @@ __global__ __launch_bounds__(256, LMPC_FAST_WAVES) void fast_kernel(
                                      tctr_next);
 }
 
+// The staged write-out's kernel (see STAGE in fast_body): x and exitflag alone, one output, a static split of R tiles.
+template <int NTHMAX, int NT, int N>
+__global__ __launch_bounds__(256, LMPC_FAST_WAVES) void fast_staged_kernel(
+    const PackLayout P, const double *__restrict__ C, const double *__restrict__ theta,
+    double *__restrict__ X, int32_t *__restrict__ exitflag, long long nprob, int R, int nstr, int32_t *__restrict__ errflag,
+    int spinLimit, int dk) {
+    fast_body<NTHMAX, NT, N, false, true>(P, C, theta, X, exitflag, nullptr, nullptr, nprob, R, nstr, errflag, spinLimit, dk, R, 0,
+                                          nullptr, nullptr);
+}
+
 // SEVERAL batches of the same size in ONE launch (lmpc_solve_batches_device): blockIdx.y picks the batch, its buffers
 // come from a table in the kernel arguments.  A launch of the one-batch kernel lives 22 us for a 13 us stream: the
 // solving tail, the spread of the streams' ends over the XCDs and the ramp are paid per launch.  Here the workgroups of
@@ -663,6 +732,14 @@ __global__ __launch_bounds__(256, LMPC_FAST_WAVES) void fast_kernel_multi(
     const int b = blockIdx.y;
     fast_body<NTHMAX, NT, N, false>(P, C, B.theta[b], B.x[b], B.flag[b], nullptr, nullptr, nprob, R, nstr, errflag, spinLimit, dk, R, 0,
                                     nullptr, nullptr);
+}
+template <int NTHMAX, int NT, int N>
+__global__ __launch_bounds__(256, LMPC_FAST_WAVES) void fast_staged_kernel_multi(
+    const PackLayout P, const double *__restrict__ C, const FastBatches B, long long nprob, int R, int nstr,
+    int32_t *__restrict__ errflag, int spinLimit, int dk) {
+    const int b = blockIdx.y;
+    fast_body<NTHMAX, NT, N, false, true>(P, C, B.theta[b], B.x[b], B.flag[b], nullptr, nullptr, nprob, R, nstr, errflag, spinLimit, dk,
+                                          R, 0, nullptr, nullptr);
 }
 
 }  // namespace lmpc

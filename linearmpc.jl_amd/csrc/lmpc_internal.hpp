@@ -143,6 +143,12 @@ struct lmpc_handle {
     int fastDma = -1;           // tuning: LDS-DMA ring depth of its streaming wavefronts (-1 = default, 0 = registers, 2, 3)
     int32_t *dFastErr = nullptr;   // raised by that kernel if one of its bounded waits ran out (never expected):
     volatile int32_t *hFastErr = nullptr;   // ... a word of pinned host memory, dFastErr its device address
+    int fastStage = -1;            // tuning: staged write-out of that kernel ("fast_stage"): 0 never, 1 wherever it applies,
+                                   // -1 = where it applies with several batches in flight ("in_flight" >= 2)
+    int inFlight = 1;              // the caller's hint "in_flight"
+    // what launch_fast_t / launch_fast_multi_t last enqueued (lmpc_fast_launch_info) and how many launches the handle has made
+    int32_t fastRec[LMPC_FAST_INFO_WORDS] = {};
+    long long fastRecN = 0;
     int fastSpinLimit = 0;         // test hook ("fast_spin_limit"): k > 0 = the kernel's waits give up after k - 1 polls
     // affine variational inequality (non-symmetric H, is_avi): its own kernel, pack and scratch (lmpc_avi.hip)
     bool avi = false;

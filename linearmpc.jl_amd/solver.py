@@ -222,6 +222,20 @@ class BatchedQP:
         recs = [dict(zip(self.ROW_LAUNCH_FIELDS, (int(v) for v in out[q * W:(q + 1) * W]))) for q in range(k)]
         return [r for r in recs if r["seq"] > since]
 
+    FAST_LAUNCH_FIELDS = ("seq", "form", "staged", "tiles", "nstr", "dma", "grid", "batches", "lds", "dyn")
+    FAST_PLAIN, FAST_GATHER, FAST_MULTI = 0, 1, 2
+
+    def fast_launch_info(self):
+        """The handle's most recent launch of the one-launch kernel (lmpc_fast_launch_info) as a dict: "seq" numbers
+        the launches of the handle's life from 1, "form" is FAST_PLAIN / FAST_GATHER / FAST_MULTI, "staged" 1 if x and
+        the exit flags were kept in LDS and stored once per workgroup, then the launch shape (tiles per workgroup,
+        streaming wavefronts, ring depth, grid, batches, LDS bytes, ticket tiles).  None if there was no such launch."""
+        out = (ctypes.c_int32 * len(self.FAST_LAUNCH_FIELDS))()
+        k = lib().lmpc_fast_launch_info(self._h, out)
+        if k < 0:
+            check(k, self._h)
+        return dict(zip(self.FAST_LAUNCH_FIELDS, (int(v) for v in out))) if k else None
+
     FRONT_PASS_FIELDS = ("seq", "kind", "N", "grid", "lds", "nprob", "seg_cap", "walker")
     FRONT_SCREEN, FRONT_TIERS = 1, 2
     WALK_LANE, WALK_WAVE, WALK_ROW = 1, 2, 3
