@@ -604,6 +604,11 @@ int lmpc_avi_launch_info(const lmpc_handle *h, int32_t *out, int max);
  * list (the slab kernel alone).  A call made inside a stream capture is refused with the option on. */
 long long lmpc_avi_list_read(lmpc_handle *h, int which, int32_t *counts, int32_t *list, long long list_words);
 
+/* Device and pinned-host blocks that the library's handles and explicit controllers hold at this moment, in the whole
+ * process (the copies of a host-pointer call's arrays, which live for that call only, are not counted).  The same
+ * before a handle is set up and after it is freed.  For tests. */
+int64_t lmpc_debug_live_blocks(void);
+
 /* Device time per lmpc_solve_batch* call, measured with HIP events recorded on the launch
  * stream (switch on with lmpc_profile(h, 1); timing-only events, hipEventDisableSystemFence: a default event's
  * system-scope cache writeback added ~1.7 us to a 24 us call that rocprofv3's kernel trace does not see).  lmpc_profile_read waits for the recorded calls,

@@ -33,6 +33,7 @@ SYMBOLS = (
     "lmpc_pin_host", "lmpc_unpin_host", "lmpc_release_scratch", "lmpc_check",
     "lmpc_distinct_active_sets_device", "lmpc_distinct_active_sets_overflowed", "lmpc_wave_stats", "lmpc_wave_launch_info",
     "lmpc_row_launch_info", "lmpc_fast_launch_info", "lmpc_front_pass_info", "lmpc_work_list_read", "lmpc_avi_launch_info", "lmpc_avi_list_read",
+    "lmpc_debug_live_blocks",
     "lmpc_setup_ex", "lmpc_is_avi", "lmpc_get_avi", "lmpc_transform_avi", "lmpc_multi_set_option", "lmpc_discover_regions_device", "lmpc_reserve", "lmpc_get_prox",
     "lmpc_explicit_default_opts", "lmpc_explicit_build_ldp", "lmpc_explicit_build", "lmpc_explicit_info",
     "lmpc_explicit_region", "lmpc_explicit_blob", "lmpc_explicit_training", "lmpc_explicit_locate_host",
@@ -261,6 +262,9 @@ def lib():
     if hasattr(L, "lmpc_avi_list_read"):
         L.lmpc_avi_list_read.argtypes = [vp, i32, vp, vp, ctypes.c_longlong]
         L.lmpc_avi_list_read.restype = ctypes.c_longlong
+    if hasattr(L, "lmpc_debug_live_blocks"):
+        L.lmpc_debug_live_blocks.argtypes = []
+        L.lmpc_debug_live_blocks.restype = ctypes.c_int64
     if hasattr(L, "lmpc_work_list_read"):
         L.lmpc_work_list_read.argtypes = [vp, vp, vp, ctypes.c_longlong]
         L.lmpc_work_list_read.restype = ctypes.c_longlong

@@ -171,9 +171,9 @@ int finalize_handle(lmpc_handle *h) {
         std::memcpy(&wb[Wl.oRout], P.Rout.data(), sizeof(double) * P.Rout.size());
         std::memcpy(&wb[Wl.ox0], P.x0.data(), sizeof(double) * P.x0.size());
         if (P.nout * P.nth) std::memcpy(&wb[Wl.oXth], P.Xth.data(), sizeof(double) * P.Xth.size());
-        HIP_TRY(h, hipMalloc(&h->dCw, sizeof(double) * wb.size()));
+        HIP_TRY(h, h->dCw.reserve(wb.size()));
         HIP_TRY(h, hipMemcpy(h->dCw, wb.data(), sizeof(double) * wb.size(), hipMemcpyHostToDevice));
-        HIP_TRY(h, hipMalloc(&h->dSw, sizeof(int32_t) * P.m));
+        HIP_TRY(h, h->dSw.reserve(P.m));
         HIP_TRY(h, hipMemcpy(h->dSw, P.sense.data(), sizeof(int32_t) * P.m, hipMemcpyHostToDevice));
     }
     fill_layout(h);
@@ -201,7 +201,7 @@ int finalize_handle(lmpc_handle *h) {
             buf[L.ox0 + k] = P.x0[k];
             for (int t = 0; t < P.nth; t++) buf[L.oXthP + (size_t)k * L.nthp + t] = P.Xth[(size_t)k * P.nth + t];
         }
-        HIP_TRY(h, hipMalloc(&h->dC, sizeof(double) * h->nC));
+        HIP_TRY(h, h->dC.reserve(h->nC));
         HIP_TRY(h, hipMemcpy(h->dC, buf.data(), sizeof(double) * h->nC, hipMemcpyHostToDevice));
         h->screenPackOnly = true;
         return LMPC_OK;
@@ -235,7 +235,7 @@ int finalize_handle(lmpc_handle *h) {
         for (int k = 0; k < P.nout; k++)
             for (int t = 0; t < P.nth; t++) buf[L.oXthP + k * L.nthp + t] = P.Xth[(size_t)k * P.nth + t];
     }
-    HIP_TRY(h, hipMalloc(&h->dC, sizeof(double) * (h->nC ? h->nC : 1)));
+    HIP_TRY(h, h->dC.reserve(h->nC ? h->nC : 1));
     HIP_TRY(h, hipMemcpy(h->dC, buf.data(), sizeof(double) * h->nC, hipMemcpyHostToDevice));
     return LMPC_OK;
 }
@@ -356,7 +356,7 @@ int ensure_f32(lmpc_handle *h) {
     for (size_t i = 0; i < P.Rout.size(); i++) wb[Wl.oRout + i] = (float)P.Rout[i];
     for (size_t i = 0; i < P.x0.size(); i++) wb[Wl.ox0 + i] = (float)P.x0[i];
     for (size_t i = 0; i < P.Xth.size(); i++) wb[Wl.oXth + i] = (float)P.Xth[i];
-    HIP_TRY(h, hipMalloc(&h->dCwf, sizeof(float) * wb.size()));
+    HIP_TRY(h, h->dCwf.reserve(wb.size()));
     HIP_TRY(h, hipMemcpy(h->dCwf, wb.data(), sizeof(float) * wb.size(), hipMemcpyHostToDevice));
     return LMPC_OK;
 }
@@ -378,13 +378,11 @@ bool wave_screens(const lmpc_handle *h, int64_t nprob) {
 
 int ensure_lists(lmpc_handle *h, int64_t nprob, hipStream_t st) {
     if (nprob <= h->listCap) return LMPC_OK;
-    hipFree(h->dList); hipFree(h->dCount); hipFree(h->dList2); hipFree(h->dList3);
-    h->dList = h->dCount = h->dList2 = h->dList3 = nullptr; h->listCap = 0;
     const size_t segCap = (size_t)lane_seg_cap(nprob);
-    HIP_TRY(h, hipMalloc(&h->dList, sizeof(int32_t) * segCap * kShards));
-    HIP_TRY(h, hipMalloc(&h->dCount, sizeof(int32_t) * 3 * kShards * kCountStride));   // two alternating sets + the parked list's
+    HIP_TRY(h, reserve_group(h->listCap, nprob, sized(h->dList, segCap * kShards),
+                             sized(h->dCount, (size_t)3 * kShards * kCountStride),   // two alternating sets + the parked list's
+                             sized(h->dList2, 0), sized(h->dList3, 0)));             // (launch_sim_run allocates these two)
     HIP_TRY(h, hipMemsetAsync(h->dCount, 0, sizeof(int32_t) * 3 * kShards * kCountStride, st));
-    h->listCap = nprob;
     h->countSet = 0;
     return LMPC_OK;
 }
@@ -406,11 +404,7 @@ WaveList work_list(const int32_t *list, const int32_t *count, int32_t *count_nex
 // what a front pass enqueued, for lmpc_front_pass_info (include/lmpc_hip.h lists the words)
 void front_record(lmpc_handle *h, const FrontLaunch &fl, int64_t nprob, int walker) {
     const auto sat = [](long long v) { return (int32_t)(v < 0x7fffffffll ? v : 0x7fffffffll); };
-    const int32_t rec[LMPC_FRONT_INFO_WORDS] = {
-        (int32_t)((h->frontRecN + 1) & 0x7fffffff), fl.kind, fl.n, sat(fl.grid), sat((long long)fl.lds), sat((long long)nprob),
-        sat(lane_seg_cap(nprob)), walker};
-    for (int q = 0; q < LMPC_FRONT_INFO_WORDS; q++) h->frontRec[h->frontRecN & 3][q] = rec[q];
-    h->frontRecN++;
+    h->frontRec.push({0, fl.kind, fl.n, sat(fl.grid), sat((long long)fl.lds), sat((long long)nprob), sat(lane_seg_cap(nprob)), walker});
 }
 
 int ensure_snapshot(lmpc_handle *h, int64_t nprob);
@@ -427,10 +421,9 @@ int snapshot_prepare(lmpc_handle *h, int64_t nprob, hipStream_t st) {
 }
 int ensure_snapshot(lmpc_handle *h, int64_t nprob) {
     const size_t words = (size_t)kShards * kCountStride + (size_t)kShards * (size_t)lane_seg_cap(nprob);
-    if (words <= h->snapCap) return LMPC_OK;
-    (void)hipFree(h->dSnap); h->dSnap = nullptr; h->snapCap = 0; h->snapSegCap = 0;
-    HIP_TRY(h, hipMalloc(&h->dSnap, sizeof(int32_t) * words));
-    h->snapCap = words;
+    if (words <= h->dSnap.size()) return LMPC_OK;
+    h->snapSegCap = 0;
+    HIP_TRY(h, h->dSnap.reserve(words));
     return LMPC_OK;
 }
 
@@ -588,10 +581,10 @@ int wave_probe(lmpc_handle *h, const double *theta, int64_t nprob, hipStream_t s
         if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) { (void)hipGetLastError(); return LMPC_OK; }
     }
     h->waveProbed = true;
-    double *px = nullptr;
-    int32_t *pf = nullptr;
-    HIP_TRY(h, hipMalloc(&px, sizeof(double) * (size_t)kProbe * h->P.nout));
-    if (hipMalloc(&pf, sizeof(int32_t) * (size_t)kProbe) != hipSuccess) { hipFree(px); return fail(h, LMPC_ERR_HIP, "lmpc: probe scratch"); }
+    DevBuf<double> px;
+    DevBuf<int32_t> pf;
+    HIP_TRY(h, px.reserve((size_t)kProbe * h->P.nout));
+    if (pf.reserve((size_t)kProbe) != hipSuccess) return fail(h, LMPC_ERR_HIP, "lmpc: probe scratch");
     int rc = LMPC_OK;
     {
         // the probe is a plain cold solve: closed-loop fusion, kept factors and profiling stay out of it
@@ -616,7 +609,6 @@ int wave_probe(lmpc_handle *h, const double *theta, int64_t nprob, hipStream_t s
     } else if (rc == LMPC_OK) {
         (void)hipStreamSynchronize(st);
     }
-    (void)hipFree(px); (void)hipFree(pf);
     return rc;
 }
 
@@ -629,8 +621,8 @@ int launch_sim_run(lmpc_handle *h, int64_t nprob, const double *theta, uint64_t 
     next_count_set(h, &cnt_now, &cnt_next);
     h->asyncCntNow = cnt_now; h->asyncCntNext = cnt_next;
     const long long segCap = lane_seg_cap(nprob);
-    if (!h->dList2) HIP_TRY(h, hipMalloc(&h->dList2, sizeof(int32_t) * (size_t)lane_seg_cap(h->listCap) * kShards));
-    if (!h->dList3) HIP_TRY(h, hipMalloc(&h->dList3, sizeof(int32_t) * (size_t)lane_seg_cap(h->listCap) * kShards));
+    HIP_TRY(h, h->dList2.reserve((size_t)lane_seg_cap(h->listCap) * kShards));
+    HIP_TRY(h, h->dList3.reserve((size_t)lane_seg_cap(h->listCap) * kShards));
     int32_t *parkCnt = h->dCount + 2 * (size_t)kShards * kCountStride;
     // first round: every scenario; later rounds: the scenarios of the round before's list, compacted
     const int32_t *lin = h->asyncListIn, *cin = h->asyncCntIn;
@@ -792,14 +784,10 @@ int ensure_sim(lmpc_handle *h, int64_t N) {
     if (N <= h->simCap) return LMPC_OK;
     const int nu = h->P.nout;
     const size_t w = (size_t)h->P.words();
-    hipFree(h->simTheta); hipFree(h->simTheta2); hipFree(h->simU); hipFree(h->simFlag); hipFree(h->simAct); hipFree(h->simFG); hipFree(h->simK);
-    h->simTheta = h->simTheta2 = h->simU = h->simFG = nullptr; h->simFlag = nullptr; h->simAct = nullptr; h->simK = nullptr; h->simCap = 0;
-    HIP_TRY(h, hipMalloc(&h->simTheta, sizeof(double) * (size_t)N * (h->P.nth ? h->P.nth : 1)));
-    HIP_TRY(h, hipMalloc(&h->simU, sizeof(double) * (size_t)N * (nu ? nu : 1)));
-    HIP_TRY(h, hipMalloc(&h->simFlag, sizeof(int32_t) * (size_t)N));
-    HIP_TRY(h, hipMalloc(&h->simAct, sizeof(uint64_t) * (size_t)N * w));
-    HIP_TRY(h, hipMalloc(&h->simFG, sizeof(double) * (32 * 32 + 32 * 64)));
-    h->simCap = N;
+    HIP_TRY(h, reserve_group(h->simCap, N, sized(h->simTheta, (size_t)N * (h->P.nth ? h->P.nth : 1)),
+                             sized(h->simU, (size_t)N * (nu ? nu : 1)), sized(h->simFlag, (size_t)N),
+                             sized(h->simAct, (size_t)N * w), sized(h->simFG, 32 * 32 + 32 * 64),
+                             sized(h->simTheta2, 0), sized(h->simK, 0)));           // (allocated by their first user)
     return LMPC_OK;
 }
 
@@ -1111,15 +1099,12 @@ int lmpc_solve_one(lmpc_handle *h, const double *theta, double *x) {
     if (!h->oneHost) LMPC_NEED_DEVICE(h);
     LMPC_ENTER_DEVICE(h);
     if (!h->oneHost) {
-        char *hp = nullptr;
-        HIP_TRY(h, hipHostMalloc(reinterpret_cast<void **>(&hp), oF + 4096, hipHostMallocMapped));
-        std::memset(hp, 0, oF + 4096);
-        if (hipHostGetDevicePointer(reinterpret_cast<void **>(&h->oneDev), hp, 0) != hipSuccess ||
-            hipStreamCreateWithFlags(&h->oneStream, hipStreamNonBlocking) != hipSuccess) {
-            (void)hipHostFree(hp); h->oneDev = nullptr; h->oneStream = nullptr;
+        if (h->oneHost.reserve(oF + 4096) != hipSuccess || hipStreamCreateWithFlags(&h->oneStream, hipStreamNonBlocking) != hipSuccess) {
+            h->oneHost.reset(); h->oneStream = nullptr;
             return fail(h, LMPC_ERR_HIP, "lmpc_solve_one: mapped record / stream");
         }
-        h->oneHost = hp;
+        std::memset(h->oneHost, 0, oF + 4096);
+        h->oneDev = h->oneHost.dev();
     }
     if (nth) std::memcpy(h->oneHost, theta, sizeof(double) * nth);
     int32_t *hflag = reinterpret_cast<int32_t *>(h->oneHost + oF);
@@ -1144,36 +1129,22 @@ int lmpc_wave_stats(lmpc_handle *h, unsigned long long out[5]) {
 
 int lmpc_wave_launch_info(const lmpc_handle *h, int32_t *out, int max) {
     if (!h || !out || max < 0) return LMPC_ERR_BADARG;
-    long long k = h->waveRecN < 4 ? h->waveRecN : 4;
-    if (k > max) k = max;
-    for (long long q = 0; q < k; q++)                      // the k most recent entries of the ring, oldest first
-        std::memcpy(out + q * LMPC_WAVE_INFO_WORDS, h->waveRec[(h->waveRecN - k + q) & 3], sizeof(int32_t) * LMPC_WAVE_INFO_WORDS);
-    return (int)k;
+    return h->waveRec.read(out, max);
 }
 
 int lmpc_row_launch_info(const lmpc_handle *h, int32_t *out, int max) {
     if (!h || !out || max < 0) return LMPC_ERR_BADARG;
-    long long k = h->rowRecN < 4 ? h->rowRecN : 4;
-    if (k > max) k = max;
-    for (long long q = 0; q < k; q++)                      // the k most recent entries of the ring, oldest first
-        std::memcpy(out + q * LMPC_ROW_INFO_WORDS, h->rowRec[(h->rowRecN - k + q) & 3], sizeof(int32_t) * LMPC_ROW_INFO_WORDS);
-    return (int)k;
+    return h->rowRec.read(out, max);
 }
 
 int lmpc_fast_launch_info(const lmpc_handle *h, int32_t *out) {
     if (!h || !out) return LMPC_ERR_BADARG;
-    if (h->fastRecN == 0) return 0;
-    std::memcpy(out, h->fastRec, sizeof(int32_t) * LMPC_FAST_INFO_WORDS);
-    return 1;
+    return h->fastRec.read(out, 1);
 }
 
 int lmpc_front_pass_info(const lmpc_handle *h, int32_t *out, int max) {
     if (!h || !out || max < 0) return LMPC_ERR_BADARG;
-    long long k = h->frontRecN < 4 ? h->frontRecN : 4;
-    if (k > max) k = max;
-    for (long long q = 0; q < k; q++)                      // the k most recent entries of the ring, oldest first
-        std::memcpy(out + q * LMPC_FRONT_INFO_WORDS, h->frontRec[(h->frontRecN - k + q) & 3], sizeof(int32_t) * LMPC_FRONT_INFO_WORDS);
-    return (int)k;
+    return h->frontRec.read(out, max);
 }
 
 long long lmpc_work_list_read(lmpc_handle *h, int32_t *counts, int32_t *list, long long list_words) {
@@ -1194,12 +1165,7 @@ long long lmpc_work_list_read(lmpc_handle *h, int32_t *counts, int32_t *list, lo
 
 int lmpc_avi_launch_info(const lmpc_handle *h, int32_t *out, int max) {
     if (!h || !out || max < 0) return LMPC_ERR_BADARG;
-    long long k = h->aviRecN < LMPC_AVI_INFO_KEPT ? h->aviRecN : LMPC_AVI_INFO_KEPT;
-    if (k > max) k = max;
-    for (long long q = 0; q < k; q++)                      // the k most recent entries of the ring, oldest first
-        std::memcpy(out + q * LMPC_AVI_INFO_WORDS, h->aviRec[(h->aviRecN - k + q) % LMPC_AVI_INFO_KEPT],
-                    sizeof(int32_t) * LMPC_AVI_INFO_WORDS);
-    return (int)k;
+    return h->aviRec.read(out, max);
 }
 
 long long lmpc_avi_list_read(lmpc_handle *h, int which, int32_t *counts, int32_t *list, long long list_words) {
@@ -1290,7 +1256,7 @@ int lmpc_set_option(lmpc_handle *h, const char *name, int value) {
         if (c > full) c = full;
         h->W.cap = c; h->W.ldc = c | 1;
         h->W.keepStride = 2 * 64 + c * (c - 1) / 2;
-        hipFree(h->dKeepR); hipFree(h->dKeepI); h->dKeepR = nullptr; h->dKeepI = nullptr; h->keepCap = 0;
+        h->dKeepR.reset(); h->dKeepI.reset(); h->keepCap = 0;
         return LMPC_OK;
     }
     if (std::strcmp(name, "wave_packed") == 0) { h->wavePacked = value < 0 ? -1 : (value ? 1 : 0); return LMPC_OK; }
@@ -1388,11 +1354,10 @@ int lmpc_reserve(lmpc_handle *h, int64_t N, void *stream) {
         // kernel's first dispatch on a queue still costs after the code is loaded (4 ms measured on pendulum N = 50:
         // the queue's scratch memory for the kernel's spills) is paid here and not in the first solve
         h->waveWarmed = true;
-        double *pt = nullptr;
-        int32_t *pf = nullptr;
+        DevBuf<double> pt;
+        DevBuf<int32_t> pf;
         const size_t nr = (size_t)h->P.nth + (size_t)h->P.nout + 2;
-        if (hipMalloc(&pt, sizeof(double) * nr) != hipSuccess) { (void)hipGetLastError(); return LMPC_OK; }
-        if (hipMalloc(&pf, sizeof(int32_t) * 4) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(pt); return LMPC_OK; }
+        if (pt.reserve(nr) != hipSuccess || pf.reserve(4) != hipSuccess) { (void)hipGetLastError(); return LMPC_OK; }
         int rc = LMPC_OK;
         if (hipMemsetAsync(pt, 0, sizeof(double) * nr, st) == hipSuccess) {
             const Restore<bool> noProf(h->prof, false);        // (not a batch: no events, no probe)
@@ -1401,7 +1366,6 @@ int lmpc_reserve(lmpc_handle *h, int64_t N, void *stream) {
             (void)hipStreamSynchronize(st);
         }
         (void)hipGetLastError();
-        (void)hipFree(pt); (void)hipFree(pf);
         return rc;
     }
     if (will_screen(h, N)) return ensure_lists(h, N, st);
@@ -1413,20 +1377,7 @@ int lmpc_release_scratch(lmpc_handle *h) {
     lmpc::DeviceScope scope;
     if (scope.enter(h->device) != hipSuccess) return fail(h, LMPC_ERR_HIP, "lmpc_release_scratch: hipSetDevice");
     (void)hipDeviceSynchronize();
-    auto rel = [](auto *&p) { if (p) { (void)hipFree(p); p = nullptr; } };
-    rel(h->sTheta); rel(h->sX); rel(h->sFlag); rel(h->sIter); rel(h->sAct); rel(h->sWarm); h->sCap = 0;
-    rel(h->dList); rel(h->dList2); rel(h->dList3); rel(h->dCount); h->listCap = 0; h->countSet = 0;
-    rel(h->dSnap); h->snapCap = 0; h->snapSegCap = 0;
-    rel(h->simTheta); rel(h->simTheta2); rel(h->simU); rel(h->simFG); rel(h->simFlag); rel(h->simAct); rel(h->simK); h->simCap = 0;
-    rel(h->ccTheta); rel(h->ccAct); rel(h->ccFlag); h->ccCap = 0; h->ccWarmN = -1;
-    rel(h->ccStage); rel(h->ccStageFlag); h->ccStageCap = 0; h->ccStagePer = 0;
-    rel(h->ccObsScratch); h->ccObsCap = 0;
-    rel(h->scnC); rel(h->scnScr); h->scnCCap = h->scnScrCap = 0;
-    rel(h->dOvfList); h->ovfCap = 0; rel(h->dOvfList1); h->ovfCap1 = 0; rel(h->dBigR); rel(h->dBigI);
-    rel(h->dBnbR); rel(h->dBnbI); h->bnbBytesR = h->bnbBytesI = 0;
-    rel(h->dRowBnb); h->rowBnbBytes = 0;
-    rel(h->dKeepR); rel(h->dKeepI); h->keepCap = 0;
-    avi_release(h, false);
+    reset_all(static_cast<lmpc_scratch &>(*h));
     return check_fast_err(h);
 }
 
@@ -1443,35 +1394,23 @@ void lmpc_free(lmpc_handle *h) {
     if (!h) return;
     lmpc::DeviceScope scope;
     if (h->dC || h->dCw || h->dCa || h->sTheta) scope.enter(h->device);
-    avi_release(h, true);
-    for (auto &ev : h->events) { hipEventDestroy(ev.a); if (ev.mid) hipEventDestroy(ev.mid); hipEventDestroy(ev.b); }
-    for (auto &e : h->eventPool) hipEventDestroy(e);
-    hipFree(h->dC); hipFree(h->sTheta); hipFree(h->sX); hipFree(h->sFlag); hipFree(h->sIter);
-    hipFree(h->sAct); hipFree(h->sWarm); hipFree(h->dList); hipFree(h->dList2); hipFree(h->dList3); hipFree(h->dCount); hipFree(h->dCw); hipFree(h->dCwf); hipFree(h->dSw); hipFree(h->dQueue);
-    hipFree(h->dOvfList); hipFree(h->dOvfCount); hipFree(h->dBigR); hipFree(h->dBigI); hipFree(h->dRegTable); hipFree(h->dRegW1); hipFree(h->dQpScan); hipFree(h->dFastCtr);
-    hipFree(h->dRowBnb); hipFree(h->dSnap);
-    hipFree(h->dBnbR); hipFree(h->dBnbI); hipFree(h->dKeepR); hipFree(h->dKeepI); hipFree(h->dOvfList1);
-    if (h->hStat) hipHostFree(const_cast<unsigned long long *>(h->hStat));
-    if (h->hRegOut) hipHostFree(h->hRegOut);
-    for (int v = 0; v < 2; v++) for (int e = 0; e < 2; e++) if (h->qpAbEv[v][e]) hipEventDestroy(h->qpAbEv[v][e]);
-    if (h->oneHost) hipHostFree(h->oneHost);
-    if (h->ccMapHost) hipHostFree(h->ccMapHost);
-    if (h->oneStream) hipStreamDestroy(h->oneStream);
-    hipFree(h->dStat);
-    hipFree(h->simTheta); hipFree(h->simTheta2); hipFree(h->simU); hipFree(h->simFG); hipFree(h->simFlag); hipFree(h->simAct); hipFree(h->simK);
-    hipFree(h->ccT2S); hipFree(h->ccTheta); hipFree(h->ccAct); hipFree(h->ccFlag); hipFree(h->obsC);
-    hipFree(h->ccStage); hipFree(h->ccStageFlag); hipFree(h->ccObsScratch); hipFree(h->scnC); hipFree(h->scnScr);
-    if (h->hFastErr) {
-        if (*h->hFastErr != 0) std::fprintf(stderr, "lmpc_free: unreported error word %d of the one-launch kernel\n", (int)*h->hFastErr);
-        hipHostFree(const_cast<int32_t *>(h->hFastErr));
-    } else hipFree(h->dFastErr);
-    for (auto &e : h->pipeEv) hipEventDestroy(e);
-    if (h->sUp) hipStreamDestroy(h->sUp);
-    if (h->sRun) hipStreamDestroy(h->sRun);
-    if (h->sDown) hipStreamDestroy(h->sDown);
     delete h;
 }
+
+int64_t lmpc_debug_live_blocks(void) { return lmpc::g_live_blocks.load(); }
 
 const char *lmpc_last_error(const lmpc_handle *h) { return h ? h->err.c_str() : g_setup_err.c_str(); }
 
 }  // extern "C"
+
+lmpc_handle::~lmpc_handle() {
+    for (auto &ev : events) { hipEventDestroy(ev.a); if (ev.mid) hipEventDestroy(ev.mid); hipEventDestroy(ev.b); }
+    for (auto &e : eventPool) hipEventDestroy(e);
+    for (int v = 0; v < 2; v++) for (int e = 0; e < 2; e++) if (qpAbEv[v][e]) hipEventDestroy(qpAbEv[v][e]);
+    if (oneStream) hipStreamDestroy(oneStream);
+    if (hFastErr && *hFastErr != 0) std::fprintf(stderr, "lmpc_free: unreported error word %d of the one-launch kernel\n", (int)*hFastErr);
+    for (auto &e : pipeEv) hipEventDestroy(e);
+    if (sUp) hipStreamDestroy(sUp);
+    if (sRun) hipStreamDestroy(sRun);
+    if (sDown) hipStreamDestroy(sDown);
+}

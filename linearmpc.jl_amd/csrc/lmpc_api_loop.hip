@@ -84,16 +84,17 @@ extern "C" {
 static int ensure_keep(lmpc_handle *h, int64_t N, hipStream_t st) {
     const size_t keepR = (size_t)h->W.keepStride, keepI = 5 * 64;
     if (N > h->keepCap) {
-        hipFree(h->dKeepR); hipFree(h->dKeepI); h->dKeepR = nullptr; h->dKeepI = nullptr; h->keepCap = 0;
+        h->dKeepR.reset(); h->dKeepI.reset(); h->keepCap = 0;
         // (17 GB for 1e6 scenarios at capacity 64: only while it is at most half of what the device has free --
         // beyond that the loop runs on masks rather than crowding out the caller)
         size_t freeB = 0, totalB = 0;
         const size_t needB = (sizeof(double) * keepR + sizeof(int32_t) * keepI) * (size_t)N;
         if (hipMemGetInfo(&freeB, &totalB) != hipSuccess) { freeB = 0; (void)hipGetLastError(); }
-        if (needB <= freeB / 2 &&
-            hipMalloc(&h->dKeepR, sizeof(double) * keepR * (size_t)N) == hipSuccess &&
-            hipMalloc(&h->dKeepI, sizeof(int32_t) * keepI * (size_t)N) == hipSuccess) h->keepCap = N;
-        else { hipFree(h->dKeepR); hipFree(h->dKeepI); h->dKeepR = nullptr; h->dKeepI = nullptr; (void)hipGetLastError(); }
+        // (no room, or an allocation that fails all the same: the group stays empty and the loop runs without it)
+        if (needB > freeB / 2 ||
+            reserve_group(h->keepCap, N, sized(h->dKeepR, sizeof(double) * keepR * (size_t)N),
+                          sized(h->dKeepI, keepI * (size_t)N)) != hipSuccess)
+            (void)hipGetLastError();
     }
     if (N <= h->keepCap) {
         // nothing kept yet: the size word of every scenario's state to -1
@@ -163,7 +164,7 @@ int lmpc_simulate_device(lmpc_handle *h, int64_t N, int T, int nx, int nr, int n
         h->asyncX = x; h->asyncR = r; h->asyncUp = nuprev > 0 ? uprev : nullptr;
         HIP_TRY(h, hipMemcpyAsync(h->dC + h->L.oFG, F, sizeof(double) * nx * nx, hipMemcpyHostToDevice, st));
         HIP_TRY(h, hipMemcpyAsync(h->dC + h->L.oFG + nx * nx, G, sizeof(double) * nx * nu, hipMemcpyHostToDevice, st));
-        if (!h->simK) HIP_TRY(h, hipMalloc(&h->simK, sizeof(int32_t) * (size_t)h->simCap));
+        HIP_TRY(h, h->simK.reserve((size_t)h->simCap));
         HIP_TRY(h, hipMemsetAsync(h->simK, 0, sizeof(int32_t) * (size_t)N, st));
         if (warm) HIP_TRY(h, hipMemsetAsync(h->simAct, 0, sizeof(uint64_t) * (size_t)N * (size_t)h->P.words(), st));   // first step is cold
         h->prof = false;
@@ -249,7 +250,7 @@ int lmpc_simulate_device(lmpc_handle *h, int64_t N, int T, int nx, int nr, int n
     if (!h->useWave && h->simFused && nu <= kMaxSimU) {
         HIP_TRY(h, hipMemcpyAsync(h->dC + h->L.oFG, F, sizeof(double) * nx * nx, hipMemcpyHostToDevice, st));
         HIP_TRY(h, hipMemcpyAsync(h->dC + h->L.oFG + nx * nx, G, sizeof(double) * nx * nu, hipMemcpyHostToDevice, st));
-        if (!h->simTheta2) HIP_TRY(h, hipMalloc(&h->simTheta2, sizeof(double) * (size_t)h->simCap * h->P.nth));
+        HIP_TRY(h, h->simTheta2.reserve((size_t)h->simCap * h->P.nth));
         double *cur = h->simTheta, *nxt = h->simTheta2;
         int rc = LMPC_OK;
         for (int k = 0; k < T && rc == LMPC_OK; k++) {
@@ -331,8 +332,8 @@ int lmpc_simulate_f32_device(lmpc_handle *h, int64_t N, int T, int nx, int nr, i
     if (rc != LMPC_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     { const int rce = api_ensure_sim(h, N); if (rce != LMPC_OK) return rce; }
-    float *dTh = reinterpret_cast<float *>(h->simTheta), *dU = reinterpret_cast<float *>(h->simU),
-          *dFG = reinterpret_cast<float *>(h->simFG);
+    float *dTh = h->simTheta.as<float>(), *dU = h->simU.as<float>(),
+          *dFG = h->simFG.as<float>();
     std::vector<float> fg((size_t)nx * nx + (size_t)nx * nu);       // the plant rounded to binary32, like the pack
     for (int i = 0; i < nx * nx; i++) fg[i] = (float)F[i];
     for (int i = 0; i < nx * nu; i++) fg[(size_t)nx * nx + i] = (float)G[i];
@@ -427,11 +428,10 @@ int lmpc_set_parameter_layout(lmpc_handle *h, const lmpc_param_layout *l) {
                                             std::to_string(h->P.nth));
     LMPC_NEED_DEVICE(h);
     LMPC_ENTER_DEVICE(h);
-    hipFree(h->ccT2S);
-    h->ccT2S = nullptr;
+    h->ccT2S.reset();
     if (l->n_preview_horizon > 0 && l->n_reference > 0) {
         const size_t cnt = (size_t)l->n_reference * l->n_reference * l->n_preview_horizon;
-        HIP_TRY(h, hipMalloc(&h->ccT2S, sizeof(double) * cnt));
+        HIP_TRY(h, h->ccT2S.reserve(cnt));
         HIP_TRY(h, hipMemcpy(h->ccT2S, l->traj2setpoint, sizeof(double) * cnt, hipMemcpyHostToDevice));
     }
     h->ccNx = l->n_state; h->ccNr = l->n_reference; h->ccNd = l->n_disturbance; h->ccNup = l->n_control_prev;
@@ -453,12 +453,9 @@ int lmpc_compute_control_device(lmpc_handle *h, int64_t N, double *control, cons
     hipStream_t st = (hipStream_t)stream;
     const size_t w = (size_t)h->P.words();
     if (N > h->ccCap) {
-        hipFree(h->ccTheta); hipFree(h->ccAct); hipFree(h->ccFlag);
-        h->ccTheta = nullptr; h->ccAct = nullptr; h->ccFlag = nullptr; h->ccCap = 0; h->ccWarmN = -1;
-        HIP_TRY(h, hipMalloc(&h->ccTheta, sizeof(double) * (size_t)N * (h->P.nth ? h->P.nth : 1)));
-        HIP_TRY(h, hipMalloc(&h->ccAct, sizeof(uint64_t) * (size_t)N * w));
-        HIP_TRY(h, hipMalloc(&h->ccFlag, sizeof(int32_t) * (size_t)N));
-        h->ccCap = N;
+        h->ccWarmN = -1;
+        HIP_TRY(h, reserve_group(h->ccCap, (int64_t)N, sized(h->ccTheta, (size_t)N * (h->P.nth ? h->P.nth : 1)),
+                                 sized(h->ccAct, (size_t)N * w), sized(h->ccFlag, (size_t)N)));
     }
     // lane / screening path without reference condensation: the screening kernel assembles theta from the
     // five arrays itself (GatherArgs) and hands the records of the problems that need iterations to the
@@ -511,16 +508,11 @@ int lmpc_compute_control(lmpc_handle *h, int64_t N, double *control, const doubl
         // block lives in MAPPED host memory, the kernels read the arguments and write control and flags straight
         // through it, the host waits once for the handle's own stream (seven blocking copies before: ~100 us a call)
         const size_t need = ((size_t)N * per * sizeof(double) + 63 & ~(size_t)63) + sizeof(int32_t) * (size_t)N + 4096;
-        if (need > h->ccMapBytes) {
-            if (h->ccMapHost) { (void)hipDeviceSynchronize(); (void)hipHostFree(h->ccMapHost); }
-            h->ccMapHost = h->ccMapDev = nullptr; h->ccMapBytes = 0;
-            char *hp = nullptr;
-            HIP_TRY(h, hipHostMalloc(reinterpret_cast<void **>(&hp), need, hipHostMallocMapped));
-            if (hipHostGetDevicePointer(reinterpret_cast<void **>(&h->ccMapDev), hp, 0) != hipSuccess) {
-                (void)hipHostFree(hp); h->ccMapDev = nullptr;
-                return fail(h, LMPC_ERR_HIP, "lmpc_compute_control: mapped block");
-            }
-            h->ccMapHost = hp; h->ccMapBytes = need;
+        if (need > h->ccMapHost.size()) {
+            if (h->ccMapHost) (void)hipDeviceSynchronize();
+            h->ccMapDev = nullptr;
+            if (h->ccMapHost.reserve(need) != hipSuccess) return fail(h, LMPC_ERR_HIP, "lmpc_compute_control: mapped block");
+            h->ccMapDev = h->ccMapHost.dev();
         }
         if (!h->oneStream) HIP_TRY(h, hipStreamCreateWithFlags(&h->oneStream, hipStreamNonBlocking));
         size_t off = 0;
@@ -548,11 +540,11 @@ int lmpc_compute_control(lmpc_handle *h, int64_t N, double *control, const doubl
         return LMPC_OK;
     }
     if (N > h->ccStageCap || per > h->ccStagePer) {
-        hipFree(h->ccStage); hipFree(h->ccStageFlag);       // (ccObsScratch is another entry point's buffer)
-        h->ccStage = nullptr; h->ccStageFlag = nullptr; h->ccStageCap = 0; h->ccStagePer = 0;
-        HIP_TRY(h, hipMalloc(&h->ccStage, sizeof(double) * (size_t)N * per));
-        HIP_TRY(h, hipMalloc(&h->ccStageFlag, sizeof(int32_t) * (size_t)N));
-        h->ccStageCap = N; h->ccStagePer = per;
+        // (a wider record regrows the group at the same N too: emptied here, so that capacity 0 never stands beside a
+        // block; ccObsScratch is another entry point's buffer)
+        h->ccStage.reset(); h->ccStageFlag.reset(); h->ccStageCap = 0; h->ccStagePer = 0;
+        HIP_TRY(h, reserve_group(h->ccStageCap, (int64_t)N, sized(h->ccStage, (size_t)N * per), sized(h->ccStageFlag, (size_t)N)));
+        h->ccStagePer = per;
     }
     Staging sg(h->ccStage);                            // carved from the handle's block: nothing is allocated per call
     auto up = [&](const double *src, size_t w) {
@@ -582,12 +574,7 @@ int lmpc_compute_control_observer_device(lmpc_handle *h, int64_t N, double *cont
     LMPC_NEED_DEVICE(h);
     LMPC_ENTER_DEVICE(h);
     const size_t per = (size_t)h->ccNx + h->ccNd;
-    if (N > h->ccObsCap) {
-        hipFree(h->ccObsScratch);
-        h->ccObsScratch = nullptr; h->ccObsCap = 0;
-        HIP_TRY(h, hipMalloc(&h->ccObsScratch, sizeof(double) * (size_t)N * (per ? per : 1)));
-        h->ccObsCap = N;
-    }
+    HIP_TRY(h, reserve_group(h->ccObsCap, (int64_t)N, sized(h->ccObsScratch, (size_t)N * (per ? per : 1))));
     double *st_ = h->ccObsScratch, *di_ = h->ccObsScratch + (size_t)N * h->ccNx;
     const long long total = (long long)N * (long long)per;
     if (total > 0) {
@@ -610,9 +597,8 @@ int lmpc_set_observer(lmpc_handle *h, const lmpc_observer *o) {
     const size_t nd_ = (size_t)o->n_state * (1 + o->n_state + o->n_control + o->n_disturbance);
     const size_t nm_ = (size_t)o->n_measurement * (1 + o->n_state + o->n_disturbance);
     const size_t nk_ = (size_t)o->n_measurement * o->n_state;
-    hipFree(h->obsC);
-    h->obsC = nullptr;
-    HIP_TRY(h, hipMalloc(&h->obsC, sizeof(double) * (nd_ + nm_ + nk_)));
+    h->obsC.reset();
+    HIP_TRY(h, h->obsC.reserve(nd_ + nm_ + nk_));
     HIP_TRY(h, hipMemcpy(h->obsC, o->plant_dynamics, sizeof(double) * nd_, hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(h->obsC + nd_, o->measurement_function, sizeof(double) * nm_, hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(h->obsC + nd_ + nm_, o->k_transpose, sizeof(double) * nk_, hipMemcpyHostToDevice));

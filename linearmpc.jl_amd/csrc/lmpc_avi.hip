@@ -102,7 +102,7 @@ int finalize_avi(lmpc_handle *h) {
         if (P.n * P.nth) std::memcpy(&buf[A.oXthf], P.Xthf.data(), sizeof(double) * P.Xthf.size());
         if (P.nout * P.nth) std::memcpy(&buf[A.oKth], P.Kth.data(), sizeof(double) * P.Kth.size());
     }
-    HIP_TRY(h, hipMalloc(&h->dCa, sizeof(double) * buf.size()));
+    HIP_TRY(h, h->dCa.reserve(buf.size()));
     HIP_TRY(h, hipMemcpy(h->dCa, buf.data(), sizeof(double) * buf.size(), hipMemcpyHostToDevice));
     // small box-constrained problem: the register-resident kernels in front of the generic one
     // (lmpc_avi_tiers_kernel.hpp: bounds only, rows of ML = s_j e_j', no row flags, no proximal-point iterations)
@@ -116,7 +116,7 @@ int finalize_avi(lmpc_handle *h) {
         }
         if (ok) { h->aviTiersN = P.n; h->kname = "avi_tiers<" + std::to_string(P.n) + ">|avi"; }
     }
-    HIP_TRY(h, hipMalloc(&h->dSa, sizeof(int32_t) * P.m));
+    HIP_TRY(h, h->dSa.reserve(P.m));
     HIP_TRY(h, hipMemcpy(h->dSa, P.sense.data(), sizeof(int32_t) * P.m, hipMemcpyHostToDevice));
     return LMPC_OK;
 }
@@ -136,14 +136,10 @@ static bool avi_use_tiers(const lmpc_handle *h, int64_t nprob, const uint64_t *w
 static int avi_ensure_lists(lmpc_handle *h, int64_t nprob, hipStream_t st) {
     if (nprob <= h->aviListCap) return LMPC_OK;
     if (h->dAviCnt) (void)hipStreamSynchronize(st);
-    hipFree(h->dAviList[0]); hipFree(h->dAviList[1]); hipFree(h->dAviCnt);
-    h->dAviList[0] = h->dAviList[1] = h->dAviCnt = nullptr; h->aviListCap = 0;
     const size_t seg = (size_t)avi_seg_cap(nprob);
-    HIP_TRY(h, hipMalloc(&h->dAviList[0], sizeof(int32_t) * seg * kShards));
-    HIP_TRY(h, hipMalloc(&h->dAviList[1], sizeof(int32_t) * seg * kShards));
-    HIP_TRY(h, hipMalloc(&h->dAviCnt, sizeof(int32_t) * 2 * kShards * kCountStride));
+    HIP_TRY(h, reserve_group(h->aviListCap, nprob, sized(h->dAviList[0], seg * kShards), sized(h->dAviList[1], seg * kShards),
+                             sized(h->dAviCnt, (size_t)2 * kShards * kCountStride)));
     HIP_TRY(h, hipMemsetAsync(h->dAviCnt, 0, sizeof(int32_t) * 2 * kShards * kCountStride, st));
-    h->aviListCap = nprob;
     return LMPC_OK;
 }
 
@@ -151,26 +147,19 @@ static int avi_ensure_lists(lmpc_handle *h, int64_t nprob, hipStream_t st) {
 static void avi_record(lmpc_handle *h, int stage, int n, int k, int list, int ldsc, int prox, long long grid, size_t lds,
                        int occ, long long nprob, long long seg_cap) {
     const auto sat = [](long long v) { return (int32_t)(v < 0x7fffffffll ? v : 0x7fffffffll); };
-    const int32_t rec[LMPC_AVI_INFO_WORDS] = {
-        (int32_t)((h->aviRecN + 1) & 0x7fffffff), stage, n, k, list, ldsc, prox, sat(grid), sat((long long)lds), occ, sat(nprob),
-        sat(seg_cap)};
-    for (int q = 0; q < LMPC_AVI_INFO_WORDS; q++) h->aviRec[h->aviRecN % LMPC_AVI_INFO_KEPT][q] = rec[q];
-    h->aviRecN++;
+    h->aviRec.push({0, stage, n, k, list, ldsc, prox, sat(grid), sat((long long)lds), occ, sat(nprob), sat(seg_cap)});
 }
 
 // option "list_snapshot": room for both lists of the chain as they are allocated now, made ready before the call
 // enqueues anything ...
 static int avi_snapshot_prepare(lmpc_handle *h) {
     const size_t words = (size_t)kShards * kCountStride + (size_t)kShards * (size_t)avi_seg_cap(h->aviListCap);
-    if (words <= h->aviSnapWords) return LMPC_OK;
-    (void)hipFree(h->dAviSnap); h->dAviSnap = nullptr; h->aviSnapWords = 0;
-    HIP_TRY(h, hipMalloc(&h->dAviSnap, sizeof(int32_t) * 2 * words));
-    h->aviSnapWords = words;
+    HIP_TRY(h, h->dAviSnap.reserve(2 * words));
     return LMPC_OK;
 }
 // ... and the copy of one list, enqueued right after the launch that filled it
 static int avi_snapshot(lmpc_handle *h, int which, const int32_t *count, const int32_t *list, long long seg_cap, hipStream_t st) {
-    int32_t *dst = h->dAviSnap + (size_t)which * h->aviSnapWords;
+    int32_t *dst = h->dAviSnap + (size_t)which * (h->dAviSnap.size() / 2);
     HIP_TRY(h, hipMemcpyAsync(dst, count, sizeof(int32_t) * kShards * kCountStride, hipMemcpyDeviceToDevice, st));
     HIP_TRY(h, hipMemcpyAsync(dst + (size_t)kShards * kCountStride, list, sizeof(int32_t) * kShards * (size_t)seg_cap,
                               hipMemcpyDeviceToDevice, st));
@@ -182,7 +171,7 @@ long long avi_list_read(lmpc_handle *h, int which, int32_t *counts, int32_t *lis
     if (!h->dAviSnap || h->aviSnapSeg[which] <= 0) return 0;
     const long long seg = h->aviSnapSeg[which], need = (long long)kShards * seg;
     if (list && list_words < need) return fail(h, LMPC_ERR_BADARG, "lmpc_avi_list_read: list_words is smaller than 64 x seg_cap");
-    const int32_t *src = h->dAviSnap + (size_t)which * h->aviSnapWords;
+    const int32_t *src = h->dAviSnap + (size_t)which * (h->dAviSnap.size() / 2);
     hipError_t e = hipDeviceSynchronize();
     int32_t cnt[kShards * kCountStride];
     if (e == hipSuccess) e = hipMemcpy(cnt, src, sizeof(cnt), hipMemcpyDeviceToHost);
@@ -206,11 +195,8 @@ static int avi_ensure_slabs(lmpc_handle *h, long long tiles, bool listed, hipStr
     if (listed) grid = std::max<long long>(kShards, (grid / kShards) * kShards);      // (fit >= kShards: slabs of small problems)
     if (grid > h->aviSlabs) {
         // (grows with the largest batch seen; stream-ordered work of earlier calls on this handle finishes first)
-        if (h->dAviR || h->dAviI) { (void)hipStreamSynchronize(st); hipFree(h->dAviR); hipFree(h->dAviI); }
-        h->dAviR = nullptr; h->dAviI = nullptr; h->aviSlabs = 0;
-        HIP_TRY(h, hipMalloc(&h->dAviR, sizeof(double) * slabR * (size_t)grid));
-        HIP_TRY(h, hipMalloc(&h->dAviI, sizeof(int32_t) * slabI * (size_t)grid));
-        h->aviSlabs = (int)grid;
+        if (h->dAviR || h->dAviI) (void)hipStreamSynchronize(st);
+        HIP_TRY(h, reserve_group(h->aviSlabs, (int)grid, sized(h->dAviR, slabR * (size_t)grid), sized(h->dAviI, slabI * (size_t)grid)));
     }
     *grid_out = grid;
     return LMPC_OK;
@@ -326,22 +312,6 @@ void avi_preload(lmpc_handle *h) {
                                        nullptr, nullptr, 0, 0, &h->aviTiersOcc[s]);
     }
     (void)hipGetLastError();
-}
-
-void avi_release(lmpc_handle *h, bool pack_too) {
-    if (h->dAviR) { (void)hipFree(h->dAviR); h->dAviR = nullptr; }
-    if (h->dAviI) { (void)hipFree(h->dAviI); h->dAviI = nullptr; }
-    h->aviSlabs = 0;
-    if (h->dAviList[0]) { (void)hipFree(h->dAviList[0]); h->dAviList[0] = nullptr; }
-    if (h->dAviList[1]) { (void)hipFree(h->dAviList[1]); h->dAviList[1] = nullptr; }
-    if (h->dAviCnt) { (void)hipFree(h->dAviCnt); h->dAviCnt = nullptr; }
-    h->aviListCap = 0;
-    if (h->dAviSnap) { (void)hipFree(h->dAviSnap); h->dAviSnap = nullptr; }
-    h->aviSnapWords = 0; h->aviSnapSeg[0] = h->aviSnapSeg[1] = 0;
-    if (pack_too) {
-        if (h->dCa) { (void)hipFree(h->dCa); h->dCa = nullptr; }
-        if (h->dSa) { (void)hipFree(h->dSa); h->dSa = nullptr; }
-    }
 }
 
 }  // namespace lmpc

@@ -13,25 +13,12 @@ namespace {
 
 constexpr int kBlock = 256;
 
-void release_scratch(lmpc_explicit *e) {
-    (void)hipFree(e->dList); (void)hipFree(e->dTheta); (void)hipFree(e->dX); (void)hipFree(e->dFlag);
-    e->dList = nullptr; e->dTheta = nullptr; e->dX = nullptr; e->dFlag = nullptr;
-    e->cap = 0;
-}
-
 int reserve(lmpc_explicit *e, int64_t N) {
-    if (!e->dCount) {
-        EXP_TRY(e, hipMalloc(&e->dCount, sizeof(int32_t)));
-        EXP_TRY(e, hipHostMalloc(reinterpret_cast<void **>(&e->hCount), sizeof(int32_t), hipHostMallocDefault));
-    }
-    if (N <= e->cap) return LMPC_OK;
-    release_scratch(e);
+    EXP_TRY(e, e->dCount.reserve(1));
+    EXP_TRY(e, e->hCount.reserve(1));
     const size_t n = (size_t)N;
-    EXP_TRY(e, hipMalloc(&e->dList, sizeof(int32_t) * n));
-    EXP_TRY(e, hipMalloc(&e->dTheta, sizeof(double) * n * (e->nth > 0 ? e->nth : 1)));
-    EXP_TRY(e, hipMalloc(&e->dX, sizeof(double) * n * e->nout));
-    EXP_TRY(e, hipMalloc(&e->dFlag, sizeof(int32_t) * n));
-    e->cap = N;
+    EXP_TRY(e, lmpc::reserve_group(e->cap, N, lmpc::sized(e->dList, n), lmpc::sized(e->dTheta, n * (e->nth > 0 ? e->nth : 1)),
+                                   lmpc::sized(e->dX, n * e->nout), lmpc::sized(e->dFlag, n)));
     return LMPC_OK;
 }
 
@@ -67,7 +54,7 @@ int lmpc_explicit_build(lmpc_explicit **out, lmpc_handle *h, int64_t N, const do
     if (rc == LMPC_OK) {
         lmpc::DeviceScope scope;
         hipError_t he = scope.enter(h->device);
-        if (he == hipSuccess) he = hipMalloc(&e->dBlob, sizeof(uint64_t) * e->blob.size());
+        if (he == hipSuccess) he = e->dBlob.reserve(e->blob.size());
         if (he == hipSuccess) he = hipMemcpy(e->dBlob, e->blob.data(), sizeof(uint64_t) * e->blob.size(), hipMemcpyHostToDevice);
         if (he != hipSuccess) {
             e->err = std::string("lmpc_explicit_build: upload of the table: ") + hipGetErrorString(he);
@@ -133,12 +120,12 @@ int lmpc_explicit_eval(lmpc_explicit *e, int64_t N, const double *theta, double 
     lmpc::DeviceScope scope;
     EXP_TRY(e, scope.enter(e->device));
     const size_t n = (size_t)N, nth = (size_t)e->nth, nout = (size_t)e->nout;
-    double *dth = nullptr, *dx = nullptr;
-    int32_t *df = nullptr, *dr = nullptr;
-    hipError_t he = hipMalloc(&dth, sizeof(double) * n * (nth > 0 ? nth : 1));
-    if (he == hipSuccess) he = hipMalloc(&dx, sizeof(double) * n * nout);
-    if (he == hipSuccess) he = hipMalloc(&df, sizeof(int32_t) * n);
-    if (he == hipSuccess) he = hipMalloc(&dr, sizeof(int32_t) * n);
+    lmpc::DevBuf<double> dth, dx;
+    lmpc::DevBuf<int32_t> df, dr;
+    hipError_t he = dth.reserve(n * (nth > 0 ? nth : 1));
+    if (he == hipSuccess) he = dx.reserve(n * nout);
+    if (he == hipSuccess) he = df.reserve(n);
+    if (he == hipSuccess) he = dr.reserve(n);
     if (he == hipSuccess && nth > 0) he = hipMemcpy(dth, theta, sizeof(double) * n * nth, hipMemcpyHostToDevice);
     int rc = LMPC_OK;
     if (he == hipSuccess) rc = lmpc_explicit_eval_device(e, N, dth, dx, df, dr, nullptr);
@@ -146,7 +133,6 @@ int lmpc_explicit_eval(lmpc_explicit *e, int64_t N, const double *theta, double 
     if (he == hipSuccess && rc == LMPC_OK) he = hipMemcpy(x, dx, sizeof(double) * n * nout, hipMemcpyDeviceToHost);
     if (he == hipSuccess && rc == LMPC_OK) he = hipMemcpy(exitflag, df, sizeof(int32_t) * n, hipMemcpyDeviceToHost);
     if (he == hipSuccess && rc == LMPC_OK && region) he = hipMemcpy(region, dr, sizeof(int32_t) * n, hipMemcpyDeviceToHost);
-    (void)hipFree(dth); (void)hipFree(dx); (void)hipFree(df); (void)hipFree(dr);
     if (rc != LMPC_OK) return rc;
     if (he != hipSuccess) return efail(e, LMPC_ERR_HIP, std::string("lmpc_explicit_eval: ") + hipGetErrorString(he));
     return lmpc_check(e->h) == LMPC_OK ? LMPC_OK : efail(e, LMPC_ERR_HIP, std::string("lmpc_explicit_eval: ") + lmpc_last_error(e->h));
@@ -154,16 +140,10 @@ int lmpc_explicit_eval(lmpc_explicit *e, int64_t N, const double *theta, double 
 
 void lmpc_explicit_free(lmpc_explicit *e) {
     if (!e) return;
+    lmpc::DeviceScope scope;
     if (e->dBlob || e->dCount || e->dList) {
-        lmpc::DeviceScope scope;
         (void)scope.enter(e->device >= 0 ? e->device : 0);
         (void)hipDeviceSynchronize();
-        release_scratch(e);
-        (void)hipFree(e->dBlob);
-        (void)hipFree(e->dCount);
-        (void)hipFree(e->simStep); (void)hipFree(e->simList2); (void)hipFree(e->simFlag);
-        (void)hipFree(e->simTheta); (void)hipFree(e->simU); (void)hipFree(e->simScr);
-        (void)hipHostFree(e->hCount);
     }
     delete e;
 }

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/lmpc_hip.h"
+#include "lmpc_internal.hpp"
 
 struct lmpc_explicit {
     int n = 0, m = 0, ms = 0, nth = 0, nout = 0, words = 0;
@@ -20,16 +21,17 @@ struct lmpc_explicit {
     // device side: the handle whose GPU holds the table and whose implicit path takes the unlocated points
     lmpc_handle *h = nullptr;
     int device = -1;
-    void *dBlob = nullptr;
-    int32_t *dList = nullptr, *dCount = nullptr, *dFlag = nullptr, *hCount = nullptr;
-    double *dTheta = nullptr, *dX = nullptr;
+    lmpc::DevBuf<uint64_t> dBlob;
+    lmpc::DevBuf<int32_t> dCount;               // the count word of the unlocated points ...
+    lmpc::PinnedBuf<int32_t> hCount;            // ... and where the host reads it
+    lmpc::DevBuf<int32_t> dList, dFlag;         // the fallback scratch: one group of `cap` points
+    lmpc::DevBuf<double> dTheta, dX;
     int64_t cap = 0;
     // scenario loop (lmpc_explicit_sim.hip): per-scenario step counters, the second work list, the lock-step form's
     // theta / u / flag, and [xhat | ulast] when the caller keeps none
-    int32_t *simStep = nullptr, *simList2 = nullptr, *simFlag = nullptr;
-    double *simTheta = nullptr, *simU = nullptr, *simScr = nullptr;
+    lmpc::DevBuf<int32_t> simStep, simList2, simFlag;
+    lmpc::DevBuf<double> simTheta, simU, simScr;
     int64_t simCap = 0, simLockCap = 0;
-    size_t simScrCap = 0;
 };
 
 // the text into the controller's error slot, the code handed back

@@ -44,13 +44,6 @@ std::string call_problem(lmpc_explicit *e, int64_t N, int T, const lmpc_scenario
     return msg;
 }
 
-template <class T>
-int grow(lmpc_explicit *e, T **p, size_t count) {
-    (void)hipFree(*p); *p = nullptr;
-    EXP_TRY(e, hipMalloc(reinterpret_cast<void **>(p), sizeof(T) * (count ? count : 1)));
-    return LMPC_OK;
-}
-
 // NT = 8 serves nth <= 8 with fewer than 8 states (a record of 8 states and nothing else takes NT = 16: the same
 // numbers, as the entries past nth are never read), so every instantiation that is built can be reached
 template <int NXT>
@@ -82,23 +75,13 @@ int run(lmpc_explicit *e, int64_t N, int T, const lmpc_scenario_sim *s, double *
     // scratch of the run: the dense fallback batch, the first list and the count word (shared with
     // lmpc_explicit_eval_device, which mode 1 never calls), the step counters and the second list, [xhat | ulast] when the caller keeps none
     { const int rc = explicit_reserve(e, N); if (rc != LMPC_OK) return rc; }
-    if (N > e->simCap) {
-        e->simCap = 0;
-        int rc = grow(e, &e->simStep, (size_t)N);
-        if (rc == LMPC_OK) rc = grow(e, &e->simList2, (size_t)N);
-        if (rc != LMPC_OK) return rc;
-        e->simCap = N;
-    }
-    if (mode == 0 && N > e->simLockCap) {
-        e->simLockCap = 0;
-        int rc = grow(e, &e->simTheta, (size_t)N * nth);
-        if (rc == LMPC_OK) rc = grow(e, &e->simU, (size_t)N * nu);
-        if (rc == LMPC_OK) rc = grow(e, &e->simFlag, (size_t)N);
-        if (rc != LMPC_OK) return rc;
-        e->simLockCap = N;
-    }
+    const auto atLeast1 = [](size_t count) { return count ? count : (size_t)1; };
+    EXP_TRY(e, reserve_group(e->simCap, N, sized(e->simStep, atLeast1((size_t)N)), sized(e->simList2, atLeast1((size_t)N))));
+    if (mode == 0)
+        EXP_TRY(e, reserve_group(e->simLockCap, N, sized(e->simTheta, atLeast1((size_t)N * nth)),
+                                 sized(e->simU, atLeast1((size_t)N * nu)), sized(e->simFlag, atLeast1((size_t)N))));
     ScnPre P; ScnPost B;
-    { const int rc = scn_begin(h, &e->simScr, &e->simScrCap, N, s, x, xhat, uprev, X_traj, flag_min, e->simTheta, e->simU, e->simFlag, st, P, B);
+    { const int rc = scn_begin(h, e->simScr, N, s, x, xhat, uprev, X_traj, flag_min, e->simTheta, e->simU, e->simFlag, st, P, B);
       if (rc != LMPC_OK) return efail(e, rc, lmpc_last_error(h)); }
     const bool wantCost = scn_want_cost(s);
     const int64_t *head = reinterpret_cast<const int64_t *>(e->blob.data());

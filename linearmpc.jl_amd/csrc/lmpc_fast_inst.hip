@@ -41,10 +41,29 @@ static bool fast_stage_fits(size_t plain, size_t staged, int nstr) {
 }
 // what was enqueued, for lmpc_fast_launch_info (include/lmpc_hip.h lists the words)
 static void fast_record(lmpc_handle *h, int form, bool stage, int Rq, int nstr, int dk, unsigned grid, int nb, size_t lds, int D) {
-    h->fastRecN++;
-    int32_t *r = h->fastRec;
-    r[0] = (int32_t)(h->fastRecN & 0x7fffffff); r[1] = form; r[2] = stage ? 1 : 0; r[3] = Rq; r[4] = nstr; r[5] = dk;
-    r[6] = (int32_t)grid; r[7] = nb; r[8] = (int32_t)lds; r[9] = D;
+    h->fastRec.push({0, form, stage ? 1 : 0, Rq, nstr, dk, (int32_t)grid, nb, (int32_t)lds, D});
+}
+
+// The kernel's error word, created with the handle's first launch or preload.  It lives in pinned host memory mapped
+// into the device: the kernel writes it in the (never expected) case that one of its bounded waits runs out, the host
+// reads it without a copy or a synchronisation at the handle's next call and in lmpc_check / lmpc_profile_read /
+// lmpc_release_scratch.  (-DLMPC_FAST_TRACE: a device block, the word in front of the kernel's trace.)
+static hipError_t fast_err_word(lmpc_handle *h, hipStream_t st) {
+    if (h->dFastErr) return hipSuccess;
+#ifdef LMPC_FAST_TRACE
+    const size_t eb = 64 + sizeof(long long) * 8 * 4 * 65536;
+    hipError_t e = h->dFastTrace.reserve(eb / sizeof(int32_t));
+    if (e == hipSuccess) e = hipMemsetAsync(h->dFastTrace, 0, eb, st);
+    if (e == hipSuccess) h->dFastErr = h->dFastTrace;
+    return e;
+#else
+    (void)st;
+    const hipError_t e = h->hFastErr.reserve(64 / sizeof(int32_t));
+    if (e != hipSuccess) return e;
+    *h->hFastErr = 0;
+    h->dFastErr = const_cast<int32_t *>(h->hFastErr.dev());
+    return hipSuccess;
+#endif
 }
 
 template <int NTHMAX, int NT, int N, bool GATHER>
@@ -106,7 +125,7 @@ static int launch_fast_t(lmpc_handle *h, int64_t nprob, const double *theta, dou
     int32_t *ctrNow = nullptr, *ctrNext = nullptr;
     if (D) {
         if (!h->dFastCtr) {
-            HIP_TRY(h, hipMalloc(&h->dFastCtr, sizeof(int32_t) * 2 * kFastCtrs * 32));
+            HIP_TRY(h, h->dFastCtr.reserve(2 * kFastCtrs * 32));
             HIP_TRY(h, hipMemsetAsync(h->dFastCtr, 0, sizeof(int32_t) * 2 * kFastCtrs * 32, st));
         }
         ctrNow = h->dFastCtr + (size_t)h->fastCtrSet * kFastCtrs * 32;
@@ -118,22 +137,7 @@ static int launch_fast_t(lmpc_handle *h, int64_t nprob, const double *theta, dou
     if (lds > 48 * 1024)
         HIP_TRY(h, hipFuncSetAttribute(stage ? (const void *)kernStaged : (const void *)kern,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (!h->dFastErr) {
-#ifdef LMPC_FAST_TRACE
-        const size_t eb = 64 + sizeof(long long) * 8 * 4 * 65536;
-        HIP_TRY(h, hipMalloc(&h->dFastErr, eb));
-        HIP_TRY(h, hipMemsetAsync(h->dFastErr, 0, eb, st));
-#else
-        // the kernel's error word lives in pinned host memory mapped into the device: the kernel writes it in the
-        // (never expected) case that one of its bounded waits runs out, the host reads it without a copy or a
-        // synchronisation at the handle's next call and in lmpc_check / lmpc_profile_read / lmpc_release_scratch
-        int32_t *hp = nullptr;
-        HIP_TRY(h, hipHostMalloc(reinterpret_cast<void **>(&hp), 64, hipHostMallocMapped));
-        *hp = 0;
-        h->hFastErr = hp;
-        HIP_TRY(h, hipHostGetDevicePointer(reinterpret_cast<void **>(&h->dFastErr), hp, 0));
-#endif
-    }
+    HIP_TRY(h, fast_err_word(h, st));
     const int spin = h->fastSpinLimit > 0 ? h->fastSpinLimit - 1 : kFastSpinLimit;
     if (stage)
         hipLaunchKernelGGL(kernStaged, dim3(grid), dim3(256), lds, st, h->L, h->dC, theta, x, flag, (long long)nprob, Rq, nstr,
@@ -185,13 +189,7 @@ static int launch_fast_multi_t(lmpc_handle *h, int nb, int64_t nprob, const doub
     auto kern = stage ? fast_staged_kernel_multi<NTHMAX, NT, N> : fast_kernel_multi<NTHMAX, NT, N>;
     if (lds > 48 * 1024)
         HIP_TRY(h, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (!h->dFastErr) {
-        int32_t *hp = nullptr;
-        HIP_TRY(h, hipHostMalloc(reinterpret_cast<void **>(&hp), 64, hipHostMallocMapped));
-        *hp = 0;
-        h->hFastErr = hp;
-        HIP_TRY(h, hipHostGetDevicePointer(reinterpret_cast<void **>(&h->dFastErr), hp, 0));
-    }
+    HIP_TRY(h, fast_err_word(h, st));
     hipLaunchKernelGGL(kern, dim3(grid, (unsigned)nb), dim3(256), lds, st, h->L, h->dC, B, (long long)nprob, R, nstr, h->dFastErr,
                        h->fastSpinLimit > 0 ? h->fastSpinLimit - 1 : kFastSpinLimit, dk);
     HIP_TRY(h, hipGetLastError());
@@ -247,17 +245,10 @@ void fast_preload(lmpc_handle *h) {
     hipFuncAttributes fa;
     (void)hipFuncGetAttributes(&fa, (const void *)fast_kernel<8, 7, 5, false>);
     // ... and what the kernel's first launch on this handle would allocate: its ticket counters, its error word
-    if (h && !h->dFastCtr && hipMalloc(&h->dFastCtr, sizeof(int32_t) * 2 * kFastCtrs * 32) == hipSuccess)
+    if (h && !h->dFastCtr && h->dFastCtr.reserve(2 * kFastCtrs * 32) == hipSuccess)
         (void)hipMemset(h->dFastCtr, 0, sizeof(int32_t) * 2 * kFastCtrs * 32);
 #ifndef LMPC_FAST_TRACE
-    if (h && !h->dFastErr) {
-        int32_t *hp = nullptr;
-        if (hipHostMalloc(reinterpret_cast<void **>(&hp), 64, hipHostMallocMapped) == hipSuccess) {
-            *hp = 0;
-            if (hipHostGetDevicePointer(reinterpret_cast<void **>(&h->dFastErr), hp, 0) == hipSuccess) h->hFastErr = hp;
-            else { (void)hipHostFree(hp); h->dFastErr = nullptr; }
-        }
-    }
+    if (h) (void)fast_err_word(h, nullptr);
 #endif
     (void)hipGetLastError();
 }

@@ -6,6 +6,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdint>
 #include <mutex>
 #include <string>
@@ -13,6 +14,7 @@
 #include <vector>
 
 #include "../../include/lmpc_hip.h"
+#include "lmpc_buffer.hpp"
 #include "lmpc_pack.hpp"
 #include "lmpc_wave_layout.hpp"
 
@@ -27,36 +29,122 @@ constexpr int64_t kProbe = 16384;       // points a fresh wavefront-kernel handl
 struct EventTriple { hipEvent_t a, mid, b; };
 // work-list mode of the wavefront kernel for one launch (list == nullptr: the whole batch)
 struct WaveList { const int32_t *list = nullptr, *count = nullptr; int32_t *count_next = nullptr; long long seg_cap = 0; };
+
+// The two allocation policies of lmpc::Buffer (lmpc_buffer.hpp) and the count of their live blocks (lmpc_debug_live_blocks)
+inline std::atomic<int64_t> g_live_blocks{0};
+struct DeviceAlloc {
+    static hipError_t allocate(void **p, void **dev, size_t bytes) {
+        const hipError_t e = hipMalloc(p, bytes);
+        if (e != hipSuccess) { *p = nullptr; return e; }
+        *dev = *p;
+        g_live_blocks++;
+        return hipSuccess;
+    }
+    static void release(void *p) { (void)hipFree(p); g_live_blocks--; }
+};
+// pinned host memory; with hipHostMallocMapped also its device address, and then both or nothing
+template <unsigned FLAGS>
+struct HostAlloc {
+    static hipError_t allocate(void **p, void **dev, size_t bytes) {
+        hipError_t e = hipHostMalloc(p, bytes, FLAGS);
+        if (e != hipSuccess) { *p = nullptr; return e; }
+        if (FLAGS & hipHostMallocMapped) {
+            e = hipHostGetDevicePointer(dev, *p, 0);
+            if (e != hipSuccess) { (void)hipHostFree(*p); *p = nullptr; return e; }
+        }
+        g_live_blocks++;
+        return hipSuccess;
+    }
+    static void release(void *p) { (void)hipHostFree(p); g_live_blocks--; }
+};
+template <class T> using DevBuf = Buffer<T, DeviceAlloc>;
+template <class T> using MappedBuf = Buffer<T, HostAlloc<hipHostMallocMapped>>;
+template <class T> using PinnedBuf = Buffer<T, HostAlloc<hipHostMallocDefault>>;
+using DevBytes = DevBuf<unsigned char>;       // a block whose element type varies with the call: as<R>()
 }  // namespace lmpc
 
-struct lmpc_handle {
+// What lmpc_release_scratch gives back: every buffer that grows with the batch, with its capacity and phase fields.
+// The function resets this struct as a whole, so a buffer declared here is released without being named anywhere else.
+struct lmpc_scratch {
+    template <class T> using DevBuf = lmpc::DevBuf<T>;
+    // staging for the host-pointer entry point (sWarm: allocated by the first warm call)
+    DevBuf<double> sTheta, sX;
+    DevBuf<int32_t> sFlag, sIter;
+    DevBuf<uint64_t> sAct, sWarm;
+    int64_t sCap = 0;
+    // work list of the problems the screening pass leaves for the iterating kernel
+    DevBuf<int32_t> dList, dCount;
+    DevBuf<int32_t> dList2, dList3;        // second work list of the scenario-asynchronous closed loop (lists alternate per round; lazy)
+    int64_t listCap = 0;        // batch size the list buffer was sized for
+    int countSet = 0;           // which of the two counter sets the next call uses
+    DevBuf<int32_t> dSnap;      // option "list_snapshot": [kShards * kCountStride counter words | kShards * seg_cap list words]
+    long long snapSegCap = 0;   // ... seg_cap of the snapshot it holds (0: none)
+    // the wavefront path's first-pass overflow list, and the slow path for working sets beyond the 64 lanes
+    // (lmpc_big_kernel.hpp): overflow list, per-thread scratch
+    DevBuf<int32_t> dOvfList1;
+    int64_t ovfCap1 = 0;
+    DevBuf<int32_t> dOvfList, dBigI;
+    lmpc::DevBytes dBigR;
+    int64_t ovfCap = 0;
+    // branch and bound: per-wavefront snapshots of a node's state, one slot per search depth (lmpc_wave_kernel.hpp)
+    lmpc::DevBytes dBnbR, dBnbI;
+    lmpc::DevBytes dRowBnb;     // ... of the row kernel's searches (lmpc_row_inst.hip)
+    // closed loop on the wavefront path: per-scenario working set + factor kept between two steps ("sim_keep_factor")
+    lmpc::DevBytes dKeepR;
+    DevBuf<int32_t> dKeepI;
+    int64_t keepCap = 0;
+    // variational handle: scratch slabs, the two work lists of the chain (kShards segments each) with their counters
+    // (two sets of kShards, kCountStride apart), the snapshot of both (two blocks of [kShards * kCountStride | kShards * seg_cap])
+    DevBuf<double> dAviR;
+    DevBuf<int32_t> dAviI;
+    int aviSlabs = 0;           // wavefront slabs of scratch allocated
+    DevBuf<int32_t> dAviList[2], dAviCnt;
+    int64_t aviListCap = 0;
+    DevBuf<int32_t> dAviSnap;
+    long long aviSnapSeg[2] = {0, 0};            // ... seg_cap of the snapshot each block holds (0: none)
+    // closed-loop simulation scratch (simTheta2, simK: allocated by their first user)
+    DevBuf<double> simTheta, simTheta2, simU, simFG;
+    DevBuf<int32_t> simK;               // per-scenario step counters
+    DevBuf<int32_t> simFlag;
+    DevBuf<uint64_t> simAct;
+    int64_t simCap = 0;
+    // generated-controller entry point (lmpc_compute_control*): scratch, warm-start state
+    DevBuf<double> ccTheta;
+    DevBuf<uint64_t> ccAct;
+    DevBuf<int32_t> ccFlag;
+    int64_t ccCap = 0, ccWarmN = -1;    // ccWarmN: batch size whose final working sets ccAct holds
+    DevBuf<double> ccObsScratch;        // lmpc_compute_control_observer: state and disturbance split from the observer state
+    int64_t ccObsCap = 0;
+    DevBuf<double> ccStage;             // host-pointer entry point: device copies of the five argument arrays
+    DevBuf<int32_t> ccStageFlag;
+    int64_t ccStageCap = 0;
+    size_t ccStagePer = 0;
+    // scenario loop (lmpc_scenario.hip): the run's constants (true plant, measurement, cost weights, constraint rows) and
+    // its per-run scratch (observer state the caller does not keep, previous control of the cost's du term)
+    DevBuf<double> scnC, scnScr;
+};
+
+struct lmpc_handle : lmpc_scratch {
+    template <class T> using DevBuf = lmpc::DevBuf<T>;
+    template <class T> using MappedBuf = lmpc::MappedBuf<T>;
+    ~lmpc_handle();             // events, streams, the unreported error word (lmpc_api.hip); the buffers free themselves
     lmpc::HostPack P;
     lmpc_settings S;
     int device = 0;
     int laneN = 0;              // lane-kernel instantiation (row stride of M/Rout on the device)
     lmpc::PackLayout L{};
-    double *dC = nullptr;       // constant pack on the GPU
+    DevBuf<double> dC;          // constant pack on the GPU
     size_t nC = 0;
     std::string err, kname;
     std::mutex errMu;           // `err` is written through fail() only: the host pipeline's upload thread and the caller's
                                 // thread can both fail on one handle; everything else of a handle is
                                 // single-caller state -- one thread at a time per handle, as for a DAQP workspace
-    // staging for the host-pointer entry point
-    double *sTheta = nullptr, *sX = nullptr;
-    int32_t *sFlag = nullptr, *sIter = nullptr;
-    uint64_t *sAct = nullptr, *sWarm = nullptr;
-    int64_t sCap = 0;
-    // ... and its three-stage pipeline: H2D copies, kernels, D2H copies on their own streams (lmpc_multi.hip)
+    // the host-pointer entry point's three-stage pipeline: H2D copies, kernels, D2H copies on their own streams (lmpc_multi.hip)
     hipStream_t sUp = nullptr, sRun = nullptr, sDown = nullptr;
     std::vector<hipEvent_t> pipeEv;
     int hostChunk = 32768;      // tuning: smallest (= last) chunk of the pipeline's schedule ("host_chunk")
     int hostRegister = 0;       // tuning: pin the caller's arrays in place for the call ("host_register"; see lmpc_multi.hip)
     int hostThreads = 1;        // tuning: pageable arrays: upload and download sides on separate host threads ("host_threads")
-    // work list of the problems the screening pass leaves for the iterating kernel
-    int32_t *dList = nullptr, *dCount = nullptr;
-    int32_t *dList2 = nullptr, *dList3 = nullptr;          // second work list of the scenario-asynchronous closed loop (lists alternate per round)
-    int64_t listCap = 0;        // batch size the list buffer was sized for
-    int countSet = 0;           // which of the two counter sets the next call uses
     bool screen = true;         // two-pass (screen + iterate) for cold starts; lmpc_set_option
     // general path: one QP per wavefront
     bool useWave = false;
@@ -66,14 +154,12 @@ struct lmpc_handle {
     lmpc::WaveSim waveSim{};    // scenario-asynchronous closed loop on the wavefront path (kstep == nullptr: off)
     int screenWave = 1;         // tuning: screening pass in front of the wavefront kernel where it applies ("screen_wave")
     bool screenPackOnly = false;   // the lane-style pack holds only what the screening pass reads (wave-only problem)
-    int32_t *dQueue = nullptr;
+    DevBuf<int32_t> dQueue;
     int waveOvfSet = 0;         // ... and which pair of overflow counters this CALL uses
     int waveTwoPass = -1;       // option "wave_two_pass": -1 auto, 0 off, 1 whenever the capacity allows
     int waveCap1 = 24;          // option "wave_cap1": working-set capacity of the first pass when "wave_two_pass" is 1
-    int32_t *dOvfList1 = nullptr;
-    int64_t ovfCap1 = 0;
-    unsigned long long *dStat = nullptr;             // working-set statistics of the wavefront kernel (device, cumulative)
-    volatile unsigned long long *hStat = nullptr;    // ... their copy in mapped host memory, written by every launch
+    DevBuf<unsigned long long> dStat;                // working-set statistics of the wavefront kernel (device, cumulative)
+    MappedBuf<volatile unsigned long long> hStat;    // ... their copy in mapped host memory, written by every launch
     unsigned long long *dStatHost = nullptr;         // ... and its device address
     bool waveProbed = false;    // a fresh handle's first large batch has been probed for its working-set sizes (wave_probe)
     int waveProbe = 1;          // option "wave_probe": 0 = never probe (first calls run in one pass until statistics exist)
@@ -82,45 +168,26 @@ struct lmpc_handle {
     int waveCtrSet = 0;         // which of the two (ticket, overflow) counter pairs the next wavefront-kernel launch uses
     // what launch_wave_cfg last enqueued (lmpc_wave_launch_info): a ring of the four most recent wavefront-kernel
     // launches, LMPC_WAVE_INFO_WORDS words each, and how many the handle has made in its life (host memory only)
-    int32_t waveRec[4][LMPC_WAVE_INFO_WORDS] = {};
-    long long waveRecN = 0;
+    lmpc::LaunchRing<LMPC_WAVE_INFO_WORDS, 4> waveRec;
     // ... and launch_row_shape (lmpc_row_launch_info): the four most recent row-kernel launches, counted apart
-    int32_t rowRec[4][LMPC_ROW_INFO_WORDS] = {};
-    long long rowRecN = 0;
+    lmpc::LaunchRing<LMPC_ROW_INFO_WORDS, 4> rowRec;
     // ... and of the front passes (lmpc_front_pass_info): the four most recent screening / tiers launches, counted apart
-    int32_t frontRec[4][LMPC_FRONT_INFO_WORDS] = {};
-    long long frontRecN = 0;
-    // option "list_snapshot": every front pass's counter set and work list copied aside for lmpc_work_list_read
+    lmpc::LaunchRing<LMPC_FRONT_INFO_WORDS, 4> frontRec;
+    // option "list_snapshot": every front pass's counter set and work list copied aside for lmpc_work_list_read (dSnap)
     int listSnapshot = 0;
-    int32_t *dSnap = nullptr;   // [kShards * kCountStride counter words | kShards * seg_cap list words]
-    size_t snapCap = 0;         // ... words allocated
-    long long snapSegCap = 0;   // ... seg_cap of the snapshot it holds (0: none)
-    int32_t *dRegTable = nullptr;  // hash table of lmpc_distinct_active_sets_device (lmpc_regions.hip): 16 control words + slots
+    DevBuf<int32_t> dRegTable;     // hash table of lmpc_distinct_active_sets_device (lmpc_regions.hip): 16 control words + slots
     int regCap = 0;
-    unsigned long long *dRegW1 = nullptr;   // one-word masks: key / count / first-index tables of regW1Cap slots each (clean
+    DevBuf<unsigned long long> dRegW1;      // one-word masks: key / count / first-index tables of regW1Cap slots each (clean
     int regW1Cap = 0;                       // between calls: the publishing kernel resets what it read)
     int regW1 = 1;                          // tuning: 0 = the ballot-loop kernels also for one-word masks ("region_lockfree")
     bool regOvStale = false;                // dRegTable[0] may hold the overflow word of a ballot-kernel call: the lock-free path clears it first
     int regBlocks = 0;          // tuning: workgroups per CU of the two-level distinct-mask reduction ("region_blocks", 0 = 1)
-    long long *hRegOut = nullptr;   // lmpc_discover_regions_device: result block in mapped host memory ...
-    long long *dRegOut = nullptr;   // ... and its device address; regOutWords = its size in 64-bit words
-    size_t regOutWords = 0;
-    // slow path for working sets beyond the 64 lanes (lmpc_big_kernel.hpp): overflow list + counter, per-thread scratch
+    MappedBuf<long long> hRegOut;   // lmpc_discover_regions_device: result block in mapped host memory ...
+    long long *dRegOut = nullptr;   // ... and its device address
+    // slow path for working sets beyond the 64 lanes (lmpc_big_kernel.hpp): the counters of its overflow lists
     int capFull = 0;            // n + 2 + #soft: the rows a working set of this problem can reach (one beyond the kernels' own n + 1 + #soft)
-    int32_t *dOvfList = nullptr, *dOvfCount = nullptr, *dBigI = nullptr;
-    void *dBigR = nullptr;
-    int64_t ovfCap = 0;
-    // branch and bound: per-wavefront snapshots of a node's state, one slot per search depth (lmpc_wave_kernel.hpp)
-    void *dBnbR = nullptr;
-    int32_t *dBnbI = nullptr;
-    size_t bnbBytesR = 0, bnbBytesI = 0;
-    void *dRowBnb = nullptr;    // ... of the row kernel's searches (lmpc_row_inst.hip)
-    size_t rowBnbBytes = 0;
-    // closed loop on the wavefront path: per-scenario working set + factor kept between two steps ("sim_keep_factor")
-    void *dKeepR = nullptr;
-    int32_t *dKeepI = nullptr;
-    int64_t keepCap = 0;
-    bool keepOn = false;
+    DevBuf<int32_t> dOvfCount;
+    bool keepOn = false;        // closed loop on the wavefront path: working set + factor kept between two steps (dKeepR, dKeepI)
     int simKeep = 1;
     bool raWarm = false;        // the run-ahead loop in progress is a warm one
     int simRunAhead = 1;        // scenario-asynchronous loop on the wavefront path: consecutive steps of a scenario inside the kernel
@@ -138,26 +205,23 @@ struct lmpc_handle {
     int fastTiles = 0;          // tuning: tiles of 64 problems per workgroup of that kernel (0 = 24)
     int fastNstr = 0;           // tuning: streaming wavefronts per workgroup of that kernel, 1..4 (0 = 3)
     int fastDyn = -1;           // tuning: tiles per workgroup of that kernel handed out through global tickets (-1 = default 4)
-    int32_t *dFastCtr = nullptr;   // ... their counters: two alternating sets of kFastCtrs, 128 bytes apart
+    DevBuf<int32_t> dFastCtr;      // ... their counters: two alternating sets of kFastCtrs, 128 bytes apart
     int fastCtrSet = 0;
     int fastDma = -1;           // tuning: LDS-DMA ring depth of its streaming wavefronts (-1 = default, 0 = registers, 2, 3)
     int32_t *dFastErr = nullptr;   // raised by that kernel if one of its bounded waits ran out (never expected):
-    volatile int32_t *hFastErr = nullptr;   // ... a word of pinned host memory, dFastErr its device address
+    MappedBuf<volatile int32_t> hFastErr;   // ... a word of pinned host memory, dFastErr its device address
+    DevBuf<int32_t> dFastTrace;    // (-DLMPC_FAST_TRACE builds: dFastErr is this device block, the error word in front of the trace)
     int fastStage = -1;            // tuning: staged write-out of that kernel ("fast_stage"): 0 never, 1 wherever it applies,
                                    // -1 = where it applies with several batches in flight ("in_flight" >= 2)
     int inFlight = 1;              // the caller's hint "in_flight"
     // what launch_fast_t / launch_fast_multi_t last enqueued (lmpc_fast_launch_info) and how many launches the handle has made
-    int32_t fastRec[LMPC_FAST_INFO_WORDS] = {};
-    long long fastRecN = 0;
+    lmpc::LaunchRing<LMPC_FAST_INFO_WORDS, 1> fastRec;
     int fastSpinLimit = 0;         // test hook ("fast_spin_limit"): k > 0 = the kernel's waits give up after k - 1 polls
     // affine variational inequality (non-symmetric H, is_avi): its own kernel, pack and scratch (lmpc_avi.hip)
     bool avi = false;
     lmpc::AviLayout A{};
-    double *dCa = nullptr;
-    int32_t *dSa = nullptr;
-    double *dAviR = nullptr;
-    int32_t *dAviI = nullptr;
-    int aviSlabs = 0;           // wavefront slabs of scratch allocated
+    DevBuf<double> dCa;
+    DevBuf<int32_t> dSa;
     int aviWaves = 0;           // tuning: wavefronts per CU of its grid ("avi_waves", 0 = 16)
     // ... small box-constrained problems: register-resident straight-line kernels in front of it (lmpc_avi_tiers_kernel.hpp)
     int aviTiersN = 0;          // n if the problem qualifies (2 .. 8), else 0
@@ -165,24 +229,14 @@ struct lmpc_handle {
     int aviTiersFirst = -1;     // tuning: tiers of the pass over the whole batch, 0 .. 3 ("avi_tiers_first"; -1: 3 up to n = 6, else 2;
                                 // 0: the lane kernel over the whole batch)
     int aviTiersOcc[2] = {0, 0};   // workgroups per CU the two instantiations keep resident (0 = not asked yet)
-    int32_t *dAviList[2] = {nullptr, nullptr};   // the two work lists of the chain, kShards segments each
-    int32_t *dAviCnt = nullptr;                  // ... their counters (two sets of kShards, kCountStride apart)
-    int64_t aviListCap = 0;
     int aviChainGroups = 0;     // tuning: cap on the workgroups of the chain's three launches ("avi_chain_groups", 0 = none)
     // what launch_avi last enqueued (lmpc_avi_launch_info): a ring of the eight most recent launches of the chain
-    int32_t aviRec[LMPC_AVI_INFO_KEPT][LMPC_AVI_INFO_WORDS] = {};
-    long long aviRecN = 0;
-    // option "list_snapshot" on a variational handle: both counter sets and both lists copied aside (lmpc_avi_list_read)
-    int32_t *dAviSnap = nullptr;                 // two blocks of [kShards * kCountStride | kShards * seg_cap] words
-    size_t aviSnapWords = 0;                     // ... words of one block as allocated
-    long long aviSnapSeg[2] = {0, 0};            // ... seg_cap of the snapshot each block holds (0: none)
+    lmpc::LaunchRing<LMPC_AVI_INFO_WORDS, LMPC_AVI_INFO_KEPT> aviRec;
     lmpc::WaveLayout W{};
-    double *dCw = nullptr;
-    float *dCwf = nullptr;      // binary32 copy of the wave kernel's pack, built on the first f32 solve
-    int32_t *dSw = nullptr;
+    DevBuf<double> dCw;
+    DevBuf<float> dCwf;         // binary32 copy of the wave kernel's pack, built on the first f32 solve
+    DevBuf<int32_t> dSw;
     int numCU = 256;
-    // closed-loop simulation scratch
-    double *simTheta = nullptr, *simTheta2 = nullptr, *simU = nullptr, *simFG = nullptr;
     int asyncPhase = 0, asyncT = 0;     // scenario-asynchronous closed loop: which half `launch` runs (0 = off)
     int32_t *asyncCntNow = nullptr, *asyncCntNext = nullptr;
     int32_t *asyncListOut = nullptr;    // ... the list the last streaming pass wrote (the iterating half reads it)
@@ -193,43 +247,27 @@ struct lmpc_handle {
     int asyncCap = 0;                   // ... steps a scenario may run ahead in this streaming pass
     bool asyncResetPark = false;        // ... this pass consumes the parked list: clear its counters afterwards
     long long asyncMaxIn = 0;           // ... its longest shard segment (sizes the grid)
-    int32_t *simK = nullptr;            // per-scenario step counters
     int simAsync = 1;           // tuning: scenario-asynchronous closed loop ("sim_async")
     int ccFused = 1;            // tuning: lmpc_compute_control assembles theta inside the screening kernel ("cc_fused")
     int simFused = 1;           // tuning: plant step inside the lane / screening kernels (lmpc_set_option "sim_fused")
-    int32_t *simFlag = nullptr;
-    uint64_t *simAct = nullptr;
-    int64_t simCap = 0;
-    // generated-controller entry point (lmpc_compute_control*): layout of theta, scratch, warm-start state
+    // generated-controller entry point (lmpc_compute_control*): layout of theta
     int ccNx = -1, ccNr = 0, ccNd = 0, ccNup = 0, ccNp = 0, ccNph = 0;
-    double *ccT2S = nullptr, *ccTheta = nullptr;
-    uint64_t *ccAct = nullptr;
-    int32_t *ccFlag = nullptr;
+    DevBuf<double> ccT2S;
     // generated observer (lmpc_set_observer): [MPC_PLANT_DYNAMICS | MPC_MEASUREMENT_FUNCTION | K_TRANSPOSE_OBSERVER]
-    double *obsC = nullptr;
+    DevBuf<double> obsC;
     int obsNx = 0, obsNu = 0, obsNd = 0, obsNy = 0;
-    double *ccObsScratch = nullptr;     // lmpc_compute_control_observer: state and disturbance split from the observer state
-    int64_t ccObsCap = 0;
-    // scenario loop (lmpc_scenario.hip): the run's constants (true plant, measurement, cost weights, constraint rows) and
-    // its per-run scratch (observer state the caller does not keep, previous control of the cost's du term)
-    double *scnC = nullptr, *scnScr = nullptr;
-    size_t scnCCap = 0, scnScrCap = 0;
-    double *ccStage = nullptr;          // host-pointer entry point: device copies of the five argument arrays
-    int32_t *ccStageFlag = nullptr;
-    int64_t ccStageCap = 0;
-    size_t ccStagePer = 0;
-    int64_t ccCap = 0, ccWarmN = -1;    // ccWarmN: batch size whose final working sets ccAct holds
     // lmpc_solve_one: ONE record in mapped host memory (theta in, x and flag out), its device address, its own stream
-    char *oneHost = nullptr, *oneDev = nullptr;
+    MappedBuf<char> oneHost;
+    char *oneDev = nullptr;
     hipStream_t oneStream = nullptr;
     // lmpc_compute_control with a handful of problems (the generated controller's one call per time step): its five
     // argument arrays and the flags in mapped host memory likewise
-    char *ccMapHost = nullptr, *ccMapDev = nullptr;
-    size_t ccMapBytes = 0;
+    MappedBuf<char> ccMapHost;
+    char *ccMapDev = nullptr;
     // small problems with many rows on the wavefront path: straight-line tiers, one problem per lane, in front of it
     // (lmpc_qp_tiers_kernel.hpp)
     bool qpTiersOk = false;     // the problem qualifies (n = 2 .. 12, m <= 64 hard or SOFT rows without other flags, nth <= 16)
-    double *dQpScan = nullptr;  // ... its scan pack (rows of M with their bounds), built with the first launch
+    DevBuf<double> dQpScan;     // ... its scan pack (rows of M with their bounds), built with the first launch
     int qpTiers = 1;            // "qp_tiers": 0 = screening pass + wavefront kernel as before, 2 = always the tiers pass, 1 (default) =
                                 // the tiers pass, and for large batches whichever of the two the handle has MEASURED faster
     // ... that measurement: one large call each way, timed by events that are read (without waiting) by later calls;
@@ -428,12 +466,11 @@ struct DeviceScope {
 };
 #define LMPC_ENTER_DEVICE(h) lmpc::DeviceScope lmpc_dev_scope__; HIP_TRY(h, lmpc_dev_scope__.enter((h)->device))
 
-// affine-variational-inequality mode (lmpc_avi.hip): pack upload, settings, launch, scratch release
+// affine-variational-inequality mode (lmpc_avi.hip): pack upload, settings, launch
 int finalize_avi(lmpc_handle *h);
 void avi_fill_settings(lmpc_handle *h);
 int launch_avi(lmpc_handle *h, int64_t nprob, const double *theta, double *x, int32_t *flag, int32_t *iters,
                uint64_t *active, const uint64_t *warm, hipStream_t st);
-void avi_release(lmpc_handle *h, bool pack_too);
 long long avi_list_read(lmpc_handle *h, int which, int32_t *counts, int32_t *list, long long list_words);
 // what launch_avi_tiers enqueued, for the handle's record (lmpc_avi_launch_info)
 struct AviLaunchShape { int stage = 0, n = 0, k = 0, list = 0; size_t lds = 0; };

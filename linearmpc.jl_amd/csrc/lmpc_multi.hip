@@ -78,20 +78,11 @@ struct PinScope {
 
 int ensure_staging(lmpc_handle *h, int64_t N, bool warm) {
     if (N <= h->sCap && (!warm || h->sWarm)) return LMPC_OK;
-    if (N > h->sCap) {
-        hipFree(h->sTheta); hipFree(h->sX); hipFree(h->sFlag); hipFree(h->sIter); hipFree(h->sAct); hipFree(h->sWarm);
-        h->sTheta = h->sX = nullptr; h->sFlag = h->sIter = nullptr; h->sAct = h->sWarm = nullptr;
-        h->sCap = 0;
-        const size_t w = (size_t)h->P.words();
-        HIP_TRY(h, hipMalloc(&h->sTheta, sizeof(double) * (size_t)N * (h->P.nth ? h->P.nth : 1)));
-        HIP_TRY(h, hipMalloc(&h->sX, sizeof(double) * (size_t)N * h->P.nout));
-        HIP_TRY(h, hipMalloc(&h->sFlag, sizeof(int32_t) * (size_t)N));
-        HIP_TRY(h, hipMalloc(&h->sIter, sizeof(int32_t) * (size_t)N));
-        HIP_TRY(h, hipMalloc(&h->sAct, sizeof(uint64_t) * (size_t)N * w));
-        h->sCap = N;
-    }
-    if (warm && !h->sWarm)
-        HIP_TRY(h, hipMalloc(&h->sWarm, sizeof(uint64_t) * (size_t)h->sCap * h->P.words()));
+    const size_t w = (size_t)h->P.words();
+    HIP_TRY(h, reserve_group(h->sCap, N, sized(h->sTheta, (size_t)N * (h->P.nth ? h->P.nth : 1)),
+                             sized(h->sX, (size_t)N * h->P.nout), sized(h->sFlag, (size_t)N), sized(h->sIter, (size_t)N),
+                             sized(h->sAct, (size_t)N * w), sized(h->sWarm, 0)));
+    if (warm) HIP_TRY(h, h->sWarm.reserve((size_t)h->sCap * w));
     return LMPC_OK;
 }
 
@@ -120,7 +111,7 @@ struct HostJob {
 
 int launch_chunk(lmpc_handle *h, size_t rs, int64_t n, int64_t off, bool warm) {
     const size_t nth = (size_t)h->P.nth, nout = (size_t)h->P.nout, w = (size_t)h->P.words();
-    char *dTh = reinterpret_cast<char *>(h->sTheta), *dX = reinterpret_cast<char *>(h->sX);
+    char *dTh = h->sTheta.as<char>(), *dX = h->sX.as<char>();
     if (rs == 8)
         return lmpc_solve_batch_device(h, n, reinterpret_cast<const double *>(dTh + rs * off * nth),
                                        reinterpret_cast<double *>(dX + rs * off * nout), h->sFlag + off, h->sIter + off,
@@ -199,7 +190,7 @@ int run_host_jobs(std::vector<HostJob> &jobs, size_t rs, lmpc_handle *errh, Host
         HIP_TRY(h, sc.enter(h->device));
         hipEvent_t evUp = h->pipeEv[2 * c], evRun = h->pipeEv[2 * c + 1];
         if (nth > 0)
-            HIP_TRY(h, hipMemcpyAsync(reinterpret_cast<char *>(h->sTheta) + rs * off * nth, j.theta + rs * off * nth,
+            HIP_TRY(h, hipMemcpyAsync(h->sTheta.as<char>() + rs * off * nth, j.theta + rs * off * nth,
                                       rs * n * nth, hipMemcpyHostToDevice, h->sUp));
         if (j.warm)
             HIP_TRY(h, hipMemcpyAsync(h->sWarm + off * w, j.warm + off * w, sizeof(uint64_t) * n * w,
@@ -220,7 +211,7 @@ int run_host_jobs(std::vector<HostJob> &jobs, size_t rs, lmpc_handle *errh, Host
         DeviceScope sc;
         HIP_TRY(h, sc.enter(h->device));
         HIP_TRY(h, hipStreamWaitEvent(h->sDown, h->pipeEv[2 * c + 1], 0));
-        HIP_TRY(h, hipMemcpyAsync(j.x + rs * off * nout, reinterpret_cast<char *>(h->sX) + rs * off * nout,
+        HIP_TRY(h, hipMemcpyAsync(j.x + rs * off * nout, h->sX.as<char>() + rs * off * nout,
                                   rs * n * nout, hipMemcpyDeviceToHost, h->sDown));
         HIP_TRY(h, hipMemcpyAsync(j.flag + off, h->sFlag + off, sizeof(int32_t) * n, hipMemcpyDeviceToHost, h->sDown));
         if (j.iters)

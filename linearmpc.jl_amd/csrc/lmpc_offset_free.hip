@@ -48,7 +48,7 @@ int run(lmpc_handle *h, int64_t N, int T, const lmpc_scenario_sim *s, const lmpc
     { const int rcu = upload_constants(h, hostC, K, st); if (rcu != LMPC_OK) return rcu; }
     const bool wantCost = scn_want_cost(s);
     ScnScratch scr;
-    { const int rcs = scn_scratch(h, &h->scnScr, &h->scnScrCap, N, s, xaug ? 0 : (size_t)na, scr); if (rcs != LMPC_OK) return rcs; }
+    { const int rcs = scn_scratch(h, h->scnScr, N, s, xaug ? 0 : (size_t)na, scr); if (rcs != LMPC_OK) return rcs; }
     if (!xaug) {                                       // set_state!(observer, x0): [x0; 0], observer.jl:74-90
         xaug = scr.state;
         hipLaunchKernelGGL(offset_free_init_kernel, dim3((unsigned)(((size_t)N * na + 255) / 256)), dim3(256), 0, st, xaug, x, nx,

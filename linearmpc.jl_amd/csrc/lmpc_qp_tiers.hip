@@ -28,13 +28,11 @@ int go(lmpc_handle *h, int64_t nprob, const double *theta, double *x, int32_t *f
         }
         // (the handle gets the pointer only once the pack is in place: a failed copy must not leave a buffer of garbage
         // that every later launch would take for the pack -- ADVICE round 4)
-        double *scan = nullptr;
-        HIP_TRY(h, hipMalloc(&scan, sizeof(double) * sp.size()));
-        if (hipMemcpy(scan, sp.data(), sizeof(double) * sp.size(), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(scan);
+        DevBuf<double> scan;
+        HIP_TRY(h, scan.reserve(sp.size()));
+        if (hipMemcpy(scan, sp.data(), sizeof(double) * sp.size(), hipMemcpyHostToDevice) != hipSuccess)
             return fail(h, LMPC_ERR_HIP, "lmpc: upload of the tiers pass's scan pack failed");
-        }
-        h->dQpScan = scan;
+        h->dQpScan = std::move(scan);
     }
     if (preload) {
         hipFuncAttributes fa;

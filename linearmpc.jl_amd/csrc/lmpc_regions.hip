@@ -334,14 +334,13 @@ static int distinct_w1(lmpc_handle *h, int64_t N, const uint64_t *active, const 
     int tcap = 64;
     while (tcap < 4 * (long long)capacity && tcap < (1 << 24)) tcap <<= 1;
     if (!h->dRegTable) {
-        HIP_TRY(h, hipMalloc(&h->dRegTable, sizeof(int32_t) * ((size_t)64 + 16)));
-        h->regCap = 64;
+        HIP_TRY(h, reserve_group(h->regCap, 64, sized(h->dRegTable, (size_t)64 + 16)));
         HIP_TRY(h, hipMemsetAsync(h->dRegTable, 0, sizeof(int32_t) * 16, st));
     }
     if (tcap != h->regW1Cap) {
-        if (h->dRegW1) { (void)hipStreamSynchronize(st); hipFree(h->dRegW1); }
-        h->dRegW1 = nullptr; h->regW1Cap = 0;
-        HIP_TRY(h, hipMalloc(&h->dRegW1, sizeof(unsigned long long) * 3 * (size_t)tcap));
+        if (h->dRegW1) (void)hipStreamSynchronize(st);
+        h->dRegW1.reset(); h->regW1Cap = 0;               // (sized for this capacity exactly: also a smaller one)
+        HIP_TRY(h, h->dRegW1.reserve(3 * (size_t)tcap));
         HIP_TRY(h, hipMemsetAsync(h->dRegW1, 0xff, sizeof(unsigned long long) * (size_t)tcap, st));                 // keys: empty
         HIP_TRY(h, hipMemsetAsync(h->dRegW1 + tcap, 0, sizeof(unsigned long long) * (size_t)tcap, st));             // counts
         HIP_TRY(h, hipMemsetAsync(h->dRegW1 + 2 * (size_t)tcap, 0x7f, sizeof(unsigned long long) * (size_t)tcap, st));   // first indices: large
@@ -382,11 +381,7 @@ int lmpc_distinct_active_sets_device(lmpc_handle *h, int64_t N, const uint64_t *
     if (use_w1(h, N)) return distinct_w1(h, N, active, exitflag, capacity, set_masks, set_count, set_first, n_sets, nullptr, st);
     int tcap = 64;
     while (tcap < 4 * (long long)capacity && tcap < (1 << 28)) tcap <<= 1;
-    if (tcap > h->regCap) {
-        hipFree(h->dRegTable); h->dRegTable = nullptr; h->regCap = 0;
-        HIP_TRY(h, hipMalloc(&h->dRegTable, sizeof(int32_t) * ((size_t)tcap + 16)));
-        h->regCap = tcap;
-    }
+    HIP_TRY(h, reserve_group(h->regCap, tcap, sized(h->dRegTable, (size_t)tcap + 16)));
     int32_t *table = h->dRegTable + 16, *overflow = h->dRegTable;
     HIP_TRY(h, hipMemsetAsync(h->dRegTable, 0, sizeof(int32_t) * 16, st));
     HIP_TRY(h, hipMemsetAsync(table, 0xff, sizeof(int32_t) * (size_t)tcap, st));
@@ -423,12 +418,11 @@ int lmpc_discover_regions_device(lmpc_handle *h, int64_t N, const double *theta,
     LMPC_ENTER_DEVICE(h);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const size_t need = 4 + (size_t)capacity * ((size_t)h->P.words() + 2);
-    if (need > h->regOutWords) {
-        if (h->hRegOut) { (void)hipStreamSynchronize(st); (void)hipHostFree(h->hRegOut); }
-        h->hRegOut = nullptr; h->dRegOut = nullptr; h->regOutWords = 0;
-        HIP_TRY(h, hipHostMalloc(reinterpret_cast<void **>(&h->hRegOut), sizeof(long long) * need, hipHostMallocMapped));
-        HIP_TRY(h, hipHostGetDevicePointer(reinterpret_cast<void **>(&h->dRegOut), h->hRegOut, 0));
-        h->regOutWords = need;
+    if (need > h->hRegOut.size()) {
+        if (h->hRegOut) (void)hipStreamSynchronize(st);
+        h->dRegOut = nullptr;
+        HIP_TRY(h, h->hRegOut.reserve(need));
+        h->dRegOut = h->hRegOut.dev();
     }
     h->hRegOut[0] = -1;                                   // "not published yet" until the kernel's last store
     int rc = N > 0 ? lmpc_solve_batch_device(h, N, theta, x, exitflag, nullptr, active, nullptr, stream) : LMPC_OK;

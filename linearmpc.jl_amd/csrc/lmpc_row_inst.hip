@@ -105,22 +105,18 @@ int launch_row_shape(lmpc_handle *h, const WaveArgs &a, const RowLaunch &rl, con
         // smaller grid before an allocation that crowds out the caller: launch_wave_cfg's rule)
         const size_t perRow = (size_t)bdepth * (sizeof(R) * (size_t)row_snap_reals(S, CAPP) + sizeof(int32_t) * (size_t)row_snap_ints(S));
         auto bytes = [&](long long gr) { return perRow * (size_t)gr * (size_t)rl.nwv * 4; };
-        if (bytes(grid) > h->rowBnbBytes) {
+        if (bytes(grid) > h->dRowBnb.size()) {
             size_t freeB = 0, totalB = 0;
             if (hipMemGetInfo(&freeB, &totalB) != hipSuccess) { freeB = 0; (void)hipGetLastError(); }
-            const size_t budget = (freeB + h->rowBnbBytes) / 2;
+            const size_t budget = (freeB + h->dRowBnb.size()) / 2;
             while (grid > 1 && bytes(grid) > budget) grid = (grid + 1) / 2;
             if (bytes(grid) > budget)
                 return fail(h, LMPC_ERR_HIP, "lmpc: not enough free device memory for the branch-and-bound snapshots");
-            if (bytes(grid) > h->rowBnbBytes) {
-                hipFree(h->dRowBnb); h->dRowBnb = nullptr; h->rowBnbBytes = 0;
-                HIP_TRY(h, hipMalloc(&h->dRowBnb, bytes(grid)));
-                h->rowBnbBytes = bytes(grid);
-            }
+            HIP_TRY(h, h->dRowBnb.reserve(bytes(grid)));
         }
         const size_t nrowsB = (size_t)grid * rl.nwv * 4;
-        bnbR = static_cast<R *>(h->dRowBnb);
-        bnbI = reinterpret_cast<int32_t *>(static_cast<char *>(h->dRowBnb) + sizeof(R) * nrowsB * bdepth * (size_t)row_snap_reals(S, CAPP));
+        bnbR = h->dRowBnb.as<R>();
+        bnbI = reinterpret_cast<int32_t *>(h->dRowBnb.get() + sizeof(R) * nrowsB * bdepth * (size_t)row_snap_reals(S, CAPP));
     }
     // counters: the wavefront kernel's own (launch_wave_cfg: two alternating sets, each launch clears the next one's)
     constexpr int kP1 = kShards * kCountStride;
@@ -146,9 +142,9 @@ int launch_row_shape(lmpc_handle *h, const WaveArgs &a, const RowLaunch &rl, con
     prm.P = Wl; prm.C = dC; prm.Sg = h->dSw; prm.theta = theta; prm.X = x; prm.exitflag = flag; prm.iters = iters;
     prm.active = active; prm.queue = queue; prm.qchunk = qchunk; prm.ps = rl.ps; prm.nprob = (long long)nprob;
     prm.list = wl.list; prm.count = wl.count; prm.count_next = wl.count_next; prm.seg_cap = wl.seg_cap;
-    prm.ovf_list = pass == 1 ? h->dOvfList1 : nullptr; prm.ovf_count = pass == 1 ? p1Count : nullptr;
+    prm.ovf_list = pass == 1 ? h->dOvfList1.get() : nullptr; prm.ovf_count = pass == 1 ? p1Count : nullptr;
     prm.queue_next = queueNext; prm.ovf_next = p2Next; prm.ovf_next1 = p1Next;
-    prm.stat = BNB ? nullptr : h->dStat; prm.stat_host = BNB ? nullptr : h->dStatHost;
+    prm.stat = BNB ? nullptr : h->dStat.get(); prm.stat_host = BNB ? nullptr : h->dStatHost;
     prm.bnb_r = bnbR; prm.bnb_i = bnbI; prm.bnb_depth = bdepth;
     prm.aux = rl.aux;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * rl.nwv), rl.lds, st, prm);
@@ -157,13 +153,12 @@ int launch_row_shape(lmpc_handle *h, const WaveArgs &a, const RowLaunch &rl, con
     // what was enqueued, for lmpc_row_launch_info (include/lmpc_hip.h lists the words)
     const auto sat = [](long long v) { return (int32_t)(v < 0x7fffffffll ? v : 0x7fffffffll); };
     const int32_t rec[LMPC_ROW_INFO_WORDS] = {
-        (int32_t)((h->rowRecN + 1) & 0x7fffffff), (int32_t)sizeof(R), S, NS, MS, CAPP, BNB ? 1 : 0, rl.nwv, blocks, (int32_t)grid,
+        0, (int32_t)sizeof(R), S, NS, MS, CAPP, BNB ? 1 : 0, rl.nwv, blocks, (int32_t)grid,
         rl.ps, (int32_t)rl.lds, rl.aux, pass, cap, qchunk, queue != nullptr ? 1 : 0, wl.list != nullptr ? 1 : 0,
-        sat((long long)nprob), BNB ? sat((long long)h->rowBnbBytes) : 0};
-    for (int q = 0; q < LMPC_ROW_INFO_WORDS; q++) h->rowRec[h->rowRecN & 3][q] = rec[q];
-    h->rowRecN++;
+        sat((long long)nprob), BNB ? sat((long long)h->dRowBnb.size()) : 0};
+    h->rowRec.push(rec);
     // ... and in the record of the front pass whose list this launch walks (lmpc_front_pass_info)
-    if (wl.list != nullptr && h->frontRecN > 0) h->frontRec[(h->frontRecN - 1) & 3][7] = LMPC_WALK_ROW;
+    if (int32_t *front = wl.list != nullptr ? h->frontRec.newest() : nullptr) front[7] = LMPC_WALK_ROW;
     return LMPC_OK;
 }
 

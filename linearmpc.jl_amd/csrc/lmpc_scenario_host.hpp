@@ -128,11 +128,7 @@ inline ScnConst pack_constants(std::vector<double> &v, int nx, int nu, int nd, i
 }
 
 inline int upload_constants(lmpc_handle *h, const std::vector<double> &v, ScnConst &K, hipStream_t st) {
-    if (v.size() > h->scnCCap) {
-        hipFree(h->scnC); h->scnC = nullptr; h->scnCCap = 0;
-        HIP_TRY(h, hipMalloc(&h->scnC, sizeof(double) * v.size()));
-        h->scnCCap = v.size();
-    }
+    HIP_TRY(h, h->scnC.reserve(v.size()));
     HIP_TRY(h, hipMemcpyAsync(h->scnC, v.data(), sizeof(double) * v.size(), hipMemcpyHostToDevice, st));
     K.c = h->scnC;
     return LMPC_OK;
@@ -142,19 +138,15 @@ inline int upload_constants(lmpc_handle *h, const std::vector<double> &v, ScnCon
 
 inline bool scn_want_cost(const lmpc_scenario_sim *s) { return s->cost && (s->cost_out || s->violation_out); }
 
-// The per-run scratch [observer state | ulast] in *buf (*cap doubles, grown to fit): stateW doubles per scenario of
+// The per-run scratch [observer state | ulast] in buf (grown to fit): stateW doubles per scenario of
 // observer state when the caller keeps none (else 0), the previous control of the cost's du term when the run needs it.
 struct ScnScratch { double *state, *ulast; };
-inline int scn_scratch(lmpc_handle *h, double **buf, size_t *cap, int64_t N, const lmpc_scenario_sim *s, size_t stateW, ScnScratch &out) {
+inline int scn_scratch(lmpc_handle *h, DevBuf<double> &buf, int64_t N, const lmpc_scenario_sim *s, size_t stateW, ScnScratch &out) {
     const size_t ulastW = scn_want_cost(s) && s->cost_out && s->cost->Rr ? (size_t)s->nu : 0;
     const size_t needScr = (size_t)N * (stateW + ulastW);
-    if (needScr > *cap) {
-        (void)hipFree(*buf); *buf = nullptr; *cap = 0;
-        HIP_TRY(h, hipMalloc(buf, sizeof(double) * needScr));
-        *cap = needScr;
-    }
-    out.state = stateW ? *buf : nullptr;
-    out.ulast = ulastW ? *buf + (size_t)N * stateW : nullptr;
+    HIP_TRY(h, buf.reserve(needScr));
+    out.state = stateW ? buf.get() : nullptr;
+    out.ulast = ulastW ? buf + (size_t)N * stateW : nullptr;
     return LMPC_OK;
 }
 
@@ -177,14 +169,14 @@ inline void scn_fill(const lmpc_handle *h, const lmpc_scenario_sim *s, int64_t N
     B.ulast = ulast; B.nx = s->nx; B.nu = s->nu; B.nd = s->nd; B.nup = s->nuprev; B.n = (long long)N;
 }
 
-// The start of a run whose observer is nx wide: the scratch in *buf, xhat <- x when the caller keeps no observer state
+// The start of a run whose observer is nx wide: the scratch in buf, xhat <- x when the caller keeps no observer state
 // (set_state!(mpc, x0), simulation.jl:92; the state then lives in the scratch), X_traj's first slice <- x, the records.
-inline int scn_begin(lmpc_handle *h, double **buf, size_t *cap, int64_t N, const lmpc_scenario_sim *s, double *x, double *xhat,
+inline int scn_begin(lmpc_handle *h, DevBuf<double> &buf, int64_t N, const lmpc_scenario_sim *s, double *x, double *xhat,
                      double *uprev, double *X_traj, int32_t *flag_min, double *theta, const double *u, const int32_t *flag,
                      hipStream_t st, ScnPre &A, ScnPost &B) {
     const size_t bytes = sizeof(double) * (size_t)N * s->nx;
     ScnScratch scr;
-    { const int rc = scn_scratch(h, buf, cap, N, s, s->use_observer && !xhat ? (size_t)s->nx : 0, scr); if (rc != LMPC_OK) return rc; }
+    { const int rc = scn_scratch(h, buf, N, s, s->use_observer && !xhat ? (size_t)s->nx : 0, scr); if (rc != LMPC_OK) return rc; }
     if (scr.state) {
         xhat = scr.state;
         HIP_TRY(h, hipMemcpyAsync(xhat, x, bytes, hipMemcpyDeviceToDevice, st));

@@ -39,7 +39,7 @@ int run(lmpc_handle *h, int64_t N, int T, const lmpc_scenario_sim *s, const lmpc
     U.plant_index = un->plant_index;
     { const int rcu = upload_constants(h, hostC, K, st); if (rcu != LMPC_OK) return rcu; }
     ScnPre A; ScnPost B;
-    { const int rcb = scn_begin(h, &h->scnScr, &h->scnScrCap, N, s, x, xhat, uprev, X_traj, flag_min, h->simTheta, h->simU, h->simFlag, st, A, B);
+    { const int rcb = scn_begin(h, h->scnScr, N, s, x, xhat, uprev, X_traj, flag_min, h->simTheta, h->simU, h->simFlag, st, A, B);
       if (rcb != LMPC_OK) return rcb; }
     const bool gauss = unc_gauss(U), wantCost = scn_want_cost(s);
     const unsigned grid = (unsigned)((N + 255) / 256);

@@ -19,10 +19,10 @@ int wave_reserve(lmpc_handle *h, int64_t nprob, hipStream_t st) { return wave_re
 // The ticket counter and the two sets of overflow counters (launch_wave_cfg describes their layout and protocol)
 int wave_scratch_counters(lmpc_handle *h, hipStream_t st) {
     constexpr int kP1 = kShards * kCountStride;
-    if (h->dQueue) return LMPC_OK;
-    if (!h->dOvfCount) HIP_TRY(h, hipMalloc(&h->dOvfCount, sizeof(int32_t) * (2 * kP1 + 64)));
+    if (h->dQueue && h->dOvfCount) return LMPC_OK;
+    HIP_TRY(h, h->dOvfCount.reserve(2 * kP1 + 64));
+    HIP_TRY(h, h->dQueue.reserve(64 / sizeof(int32_t)));
     HIP_TRY(h, hipMemsetAsync(h->dOvfCount, 0, sizeof(int32_t) * (2 * kP1 + 64), st));
-    HIP_TRY(h, hipMalloc(&h->dQueue, 64));
     HIP_TRY(h, hipMemsetAsync(h->dQueue, 0, 64, st));
     h->waveCtrSet = 0; h->waveOvfSet = 0;
     return LMPC_OK;
@@ -31,37 +31,27 @@ int wave_scratch_counters(lmpc_handle *h, hipStream_t st) {
 // working-set statistics: device counters + their mapped host copy
 int wave_scratch_stats(lmpc_handle *h, hipStream_t st) {
     if (h->hStat) return LMPC_OK;
-    unsigned long long *hp = nullptr;
-    HIP_TRY(h, hipHostMalloc(reinterpret_cast<void **>(&hp), 64, hipHostMallocMapped));
-    for (int q = 0; q < 8; q++) hp[q] = 0ull;
-    h->hStat = hp;
-    HIP_TRY(h, hipHostGetDevicePointer(reinterpret_cast<void **>(&h->dStatHost), hp, 0));
-    HIP_TRY(h, hipMalloc(&h->dStat, sizeof(unsigned long long) * 64 * 16));
+    // (the device block first: the mapped copy, which the test above and every reader go by, exists only with it)
+    HIP_TRY(h, h->dStat.reserve(64 * 16));
     HIP_TRY(h, hipMemsetAsync(h->dStat, 0, sizeof(unsigned long long) * 64 * 16, st));
+    HIP_TRY(h, h->hStat.reserve(8));
+    for (int q = 0; q < 8; q++) h->hStat[q] = 0ull;
+    h->dStatHost = const_cast<unsigned long long *>(h->hStat.dev());
     return LMPC_OK;
 }
 
 // the list of the points that outgrow a first pass
 int wave_scratch_list1(lmpc_handle *h, int64_t nprob) {
-    if (nprob <= h->ovfCap1) return LMPC_OK;
-    hipFree(h->dOvfList1); h->dOvfList1 = nullptr; h->ovfCap1 = 0;
-    HIP_TRY(h, hipMalloc(&h->dOvfList1, sizeof(int32_t) * (size_t)nprob));
-    h->ovfCap1 = nprob;
+    HIP_TRY(h, reserve_group(h->ovfCap1, nprob, sized(h->dOvfList1, (size_t)nprob)));
     return LMPC_OK;
 }
 
 // the slow path's list and its per-thread scratch (sized for binary64: the binary32 calls of the handle use the same slices)
 int wave_scratch_slow(lmpc_handle *h, int64_t nprob) {
-    if (nprob > h->ovfCap) {
-        hipFree(h->dOvfList); h->dOvfList = nullptr; h->ovfCap = 0;
-        HIP_TRY(h, hipMalloc(&h->dOvfList, sizeof(int32_t) * (size_t)nprob));
-        h->ovfCap = nprob;
-    }
-    if (!h->dBigR) {
-        const int bigCap = h->capFull < kBigCap ? h->capFull : kBigCap;
-        HIP_TRY(h, hipMalloc(&h->dBigR, sizeof(double) * (size_t)kBigThreads * (size_t)big_scratch_reals(h->W.n, h->W.m, bigCap)));
-        HIP_TRY(h, hipMalloc(&h->dBigI, sizeof(int32_t) * (size_t)kBigThreads * (size_t)big_scratch_ints(h->W.m, bigCap)));
-    }
+    HIP_TRY(h, reserve_group(h->ovfCap, nprob, sized(h->dOvfList, (size_t)nprob)));
+    const int bigCap = h->capFull < kBigCap ? h->capFull : kBigCap;
+    HIP_TRY(h, h->dBigR.reserve(sizeof(double) * (size_t)kBigThreads * (size_t)big_scratch_reals(h->W.n, h->W.m, bigCap)));
+    HIP_TRY(h, h->dBigI.reserve((size_t)kBigThreads * (size_t)big_scratch_ints(h->W.m, bigCap)));
     return LMPC_OK;
 }
 #endif

@@ -215,9 +215,9 @@ int launch_wave_cfg(lmpc_handle *h, const WaveArgs &a, const WaveConfig &cfg, co
         const size_t perWave = (size_t)(h->nBinary > 0 ? h->nBinary : 1) *
                                (sizeof(double) * (6 * 64 + (size_t)Wl.cap * (Wl.cap - 1) / 2) + sizeof(int32_t) * 5 * 64);
         size_t freeB = 0, totalB = 0;
-        if (perWave * (size_t)grid * cfg.nwv > h->bnbBytesR + h->bnbBytesI) {
+        if (perWave * (size_t)grid * cfg.nwv > h->dBnbR.size() + h->dBnbI.size()) {
             if (hipMemGetInfo(&freeB, &totalB) != hipSuccess) { freeB = 0; (void)hipGetLastError(); }
-            const size_t budget = (freeB + h->bnbBytesR + h->bnbBytesI) / 2;
+            const size_t budget = (freeB + h->dBnbR.size() + h->dBnbI.size()) / 2;
             while (grid > 1 && perWave * (size_t)grid * cfg.nwv > budget) grid = (grid + 1) / 2;
             if (perWave * (size_t)grid * cfg.nwv > budget)
                 return fail(h, LMPC_ERR_HIP, "lmpc: not enough free device memory for the branch-and-bound snapshots");
@@ -270,43 +270,34 @@ int launch_wave_cfg(lmpc_handle *h, const WaveArgs &a, const WaveConfig &cfg, co
         const size_t snapR = 6 * 64 + (size_t)Wl.cap * (Wl.cap - 1) / 2, snapI = 5 * 64;
         const size_t slots = (size_t)grid * cfg.nwv, depth = (size_t)(h->nBinary > 0 ? h->nBinary : 1);
         const size_t needR = sizeof(double) * slots * depth * snapR, needI = sizeof(int32_t) * slots * depth * snapI;
-        if (needR > h->bnbBytesR) {
-            hipFree(h->dBnbR); h->dBnbR = nullptr; h->bnbBytesR = 0;
-            HIP_TRY(h, hipMalloc(&h->dBnbR, needR));
-            h->bnbBytesR = needR;
-        }
-        if (needI > h->bnbBytesI) {
-            hipFree(h->dBnbI); h->dBnbI = nullptr; h->bnbBytesI = 0;
-            HIP_TRY(h, hipMalloc(&h->dBnbI, needI));
-            h->bnbBytesI = needI;
-        }
-        bnbR = static_cast<R *>(h->dBnbR);
-        bnbI = h->dBnbI;
+        HIP_TRY(h, h->dBnbR.reserve(needR));
+        HIP_TRY(h, h->dBnbI.reserve(needI));
+        bnbR = h->dBnbR.template as<R>();
+        bnbI = h->dBnbI.template as<int32_t>();
     } else if (h->keepOn && sizeof(R) == 8) {
         // closed loop (lmpc_simulate_device, step-synchronous): every scenario's final working set and factor stay on
         // the device between two steps, indexed by scenario
-        bnbR = static_cast<R *>(h->dKeepR);
+        bnbR = h->dKeepR.template as<R>();
         bnbI = h->dKeepI;
     }
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * cfg.nwv), cfg.lds, st, Wl, dC, h->dSw, theta, x, flag,
                        iters, active, warm, queue, qchunk, (long long)nprob, wl.list, wl.count, wl.count_next, wl.seg_cap,
-                       pass == 1 ? h->dOvfList1 : (big ? h->dOvfList : nullptr), pass == 1 ? p1Count : (big ? ovfCount : nullptr),
+                       pass == 1 ? h->dOvfList1.get() : (big ? h->dOvfList.get() : nullptr), pass == 1 ? p1Count : (big ? ovfCount : nullptr),
                        h->waveSim, bnbR, bnbI, BNB ? h->nBinary : (pass == 1 ? 1 : 0), queueNext, p2Next, p1Next,
-                       BNB ? nullptr : h->dStat, BNB ? nullptr : h->dStatHost);
+                       BNB ? nullptr : h->dStat.get(), BNB ? nullptr : h->dStatHost);
     h->waveCtrSet ^= 1;
     HIP_TRY(h, hipGetLastError());
     if (big) {
         hipLaunchKernelGGL(big_kernel<R>, dim3(kBigThreads / 64), dim3(64), 0, st, Wl, dC, h->dSw, theta, x, flag, iters,
-                           active, warm, h->dOvfList, ovfCount, static_cast<R *>(h->dBigR), h->dBigI, bigCap, h->waveSim);
+                           active, warm, h->dOvfList, ovfCount, h->dBigR.template as<R>(), h->dBigI, bigCap, h->waveSim);
         HIP_TRY(h, hipGetLastError());
     }
     // what was enqueued, for lmpc_wave_launch_info (include/lmpc_hip.h lists the words)
     const int32_t rec[LMPC_WAVE_INFO_WORDS] = {
-        (int32_t)((h->waveRecN + 1) & 0x7fffffff), (int32_t)sizeof(R), MR, LDSC, BNB ? 1 : 0, PACKED ? 1 : 0, NU, GRAM ? 1 : 0,
+        0, (int32_t)sizeof(R), MR, LDSC, BNB ? 1 : 0, PACKED ? 1 : 0, NU, GRAM ? 1 : 0,
         SIM ? 1 : 0, cfg.nwv, cfg.level, (int32_t)grid, qchunk, pass, Wl.cap, big ? 1 : 0, queue != nullptr ? 1 : 0,
         wl.list != nullptr ? 1 : 0, (int32_t)cfg.lds, (int32_t)(nprob < (int64_t)0x7fffffff ? nprob : (int64_t)0x7fffffff)};
-    for (int q = 0; q < LMPC_WAVE_INFO_WORDS; q++) h->waveRec[h->waveRecN & 3][q] = rec[q];
-    h->waveRecN++;
+    h->waveRec.push(rec);
     return LMPC_OK;
 }
 
