@@ -254,7 +254,7 @@ long long lane_seg_cap(long long nprob) {
 }
 
 template <int N, int MS, int MA, bool SIM, bool MULTI>
-int launch_lane(lmpc_handle *h, int B, size_t lds, int64_t nprob, const double *theta, double *x,
+int launch_lane(lmpc_handle *h, const PackLayout &L, int B, size_t lds, int64_t nprob, const double *theta, double *x,
                 int32_t *flag, int32_t *iters, uint64_t *active, const uint64_t *warm,
                 const int32_t *list, const int32_t *count, int32_t *count_next, hipStream_t st) {
     auto kern = lane_kernel<N, MS, MA, SIM, MULTI>;
@@ -283,14 +283,14 @@ int launch_lane(lmpc_handle *h, int B, size_t lds, int64_t nprob, const double *
     if (tierArg && h->laneStraight && h->L.imm_mask == 0ull && h->L.eq_mask == 0ull &&
         h->S.iter_limit > LMPC_FAST_KMAX + 1 && h->S.cycle_tol >= LMPC_FAST_KMAX + 1)
         tierArg = 2;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(B), lds, st, h->L, h->dC, theta, x, flag, iters, active,
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(B), lds, st, L, h->dC, theta, x, flag, iters, active,
                        warm, list, count, count_next, segCap, kShards, (long long)nprob, tierArg);
     HIP_TRY(h, hipGetLastError());
     return LMPC_OK;
 }
 
 template <int NTHMAX, int NT, int MODE>
-int launch_screen(lmpc_handle *h, int64_t nprob, const double *theta, double *x, int32_t *flag,
+int launch_screen(lmpc_handle *h, const PackLayout &L, int64_t nprob, const double *theta, double *x, int32_t *flag,
                   int32_t *iters, uint64_t *active, const uint64_t *warm, int32_t *count, hipStream_t st, FrontLaunch *fl) {
     const int B = 256;
     // several outputs per problem: room for the wave-private transpose of the outputs (plain mode)
@@ -298,7 +298,7 @@ int launch_screen(lmpc_handle *h, int64_t nprob, const double *theta, double *x,
     const long long ntiles = (nprob + B - 1) / B;
     const unsigned grid = (unsigned)((ntiles + kScreenTPB - 1) / kScreenTPB);
     const long long segCap = lane_seg_cap(nprob);
-    hipLaunchKernelGGL((screen_kernel<NTHMAX, NT, MODE>), dim3(grid), dim3(B), lds, st, h->L, h->dC, theta, x, flag,
+    hipLaunchKernelGGL((screen_kernel<NTHMAX, NT, MODE>), dim3(grid), dim3(B), lds, st, L, h->dC, theta, x, flag,
                        iters, active, warm, h->dList, count, segCap, kShards, (long long)nprob);
     HIP_TRY(h, hipGetLastError());
     if (fl) *fl = FrontLaunch{LMPC_FRONT_SCREEN, 0, (long long)grid, lds};
@@ -311,7 +311,7 @@ int launch_wave_t(lmpc_handle *h, const WaveArgs &a, const R *dC, int64_t nprob,
     if constexpr (sizeof(R) == 8) {
         // plain batched solve (no plant step to fuse, no kept factorisation, no run-ahead): the instantiations built
         // without the closed-loop machinery
-        if (!h->bnb && h->waveSim.FG == nullptr && !h->keepOn)
+        if (!h->bnb && !a.in_loop())
             return h->waveGram ? launch_wave_inst<R, false, true, false>(h, a, dC, nprob, theta, x, flag, iters, active, warm, st)
                                : launch_wave_inst<R, false, false, false>(h, a, dC, nprob, theta, x, flag, iters, active, warm, st);
     }
@@ -441,46 +441,47 @@ int list_snapshot(lmpc_handle *h, const int32_t *count, int64_t nprob, hipStream
 // The screening pass at the handle's column count (exact up to 16, padded beyond) in one of its modes: 0 plain, 1 closed
 // loop with the plant step fused in (SimFuse), 2 generated controller (GatherArgs), 3 several outputs, stored transposed
 template <int NTHMAX, int NT>
-int launch_screen_mode(lmpc_handle *h, int mode, int64_t nprob, const double *theta, double *x, int32_t *flag,
+int launch_screen_mode(lmpc_handle *h, const PackLayout &L, int mode, int64_t nprob, const double *theta, double *x, int32_t *flag,
                        int32_t *iters, uint64_t *active, const uint64_t *warm, int32_t *count, hipStream_t st, FrontLaunch *fl) {
     switch (mode) {
-        case 1: return launch_screen<NTHMAX, NT, 1>(h, nprob, theta, x, flag, iters, active, warm, count, st, fl);
-        case 2: return launch_screen<NTHMAX, NT, 2>(h, nprob, theta, x, flag, iters, active, warm, count, st, fl);
-        case 3: return launch_screen<NTHMAX, NT, 3>(h, nprob, theta, x, flag, iters, active, warm, count, st, fl);
-        default: return launch_screen<NTHMAX, NT, 0>(h, nprob, theta, x, flag, iters, active, warm, count, st, fl);
+        case 1: return launch_screen<NTHMAX, NT, 1>(h, L, nprob, theta, x, flag, iters, active, warm, count, st, fl);
+        case 2: return launch_screen<NTHMAX, NT, 2>(h, L, nprob, theta, x, flag, iters, active, warm, count, st, fl);
+        case 3: return launch_screen<NTHMAX, NT, 3>(h, L, nprob, theta, x, flag, iters, active, warm, count, st, fl);
+        default: return launch_screen<NTHMAX, NT, 0>(h, L, nprob, theta, x, flag, iters, active, warm, count, st, fl);
     }
 }
 
-int launch_screen_any(lmpc_handle *h, int mode, int64_t nprob, const double *theta, double *x, int32_t *flag,
+int launch_screen_any(lmpc_handle *h, const PackLayout &L, int mode, int64_t nprob, const double *theta, double *x, int32_t *flag,
                       int32_t *iters, uint64_t *active, const uint64_t *warm, int32_t *count, hipStream_t st,
                       FrontLaunch *fl = nullptr) {
-#define LMPC_SCR(NM, NT) case NT: return launch_screen_mode<NM, NT>(h, mode, nprob, theta, x, flag, iters, active, warm, count, st, fl);
+#define LMPC_SCR(NM, NT) case NT: return launch_screen_mode<NM, NT>(h, L, mode, nprob, theta, x, flag, iters, active, warm, count, st, fl);
     switch (h->P.nth <= 16 ? h->P.nth : 32) {
         LMPC_SCR(8, 1) LMPC_SCR(8, 2) LMPC_SCR(8, 3) LMPC_SCR(8, 4) LMPC_SCR(8, 5) LMPC_SCR(8, 6) LMPC_SCR(8, 7) LMPC_SCR(8, 8)
         LMPC_SCR(16, 9) LMPC_SCR(16, 10) LMPC_SCR(16, 11) LMPC_SCR(16, 12) LMPC_SCR(16, 13) LMPC_SCR(16, 14) LMPC_SCR(16, 15)
         LMPC_SCR(16, 16)
-        default: return launch_screen_mode<32, 32>(h, mode, nprob, theta, x, flag, iters, active, warm, count, st, fl);
+        default: return launch_screen_mode<32, 32>(h, L, mode, nprob, theta, x, flag, iters, active, warm, count, st, fl);
     }
 #undef LMPC_SCR
 }
 
 // wavefront-kernel handles: the streaming pass finishes what needs no iterations, the wavefront kernel walks the rest
-int launch_wave_screened(lmpc_handle *h, int64_t nprob, const double *theta, double *x, int32_t *flag,
+int launch_wave_screened(lmpc_handle *h, const LoopMode &mode, int64_t nprob, const double *theta, double *x, int32_t *flag,
                          int32_t *iters, uint64_t *active, const uint64_t *warm, hipStream_t st) {
     LMPC_TRY(ensure_lists(h, nprob, st));
     LMPC_TRY(snapshot_prepare(h, nprob, st));
     ProfBracket prof(h, st);
-    LMPC_TRY(prof.begin(h->prof));
+    LMPC_TRY(prof.begin(h->prof && mode.prof));
     int32_t *cnt_now, *cnt_next;
     next_count_set(h, &cnt_now, &cnt_next);
     // closed loop with the plant step fused in (lmpc_simulate_device), else several outputs stored transposed, else plain
-    const int mode = h->L.sim.FG != nullptr ? 1 : (h->P.nout > 1 && h->P.nout <= 16 ? 3 : 0);
+    const int smode = mode.sim.FG != nullptr ? 1 : (h->P.nout > 1 && h->P.nout <= 16 ? 3 : 0);
     FrontLaunch fl;
-    int rc = launch_screen_any(h, mode, nprob, theta, x, flag, iters, active, warm, cnt_now, st, &fl);
+    PackLayout tmp;
+    int rc = launch_screen_any(h, pack_layout(h, mode, tmp), smode, nprob, theta, x, flag, iters, active, warm, cnt_now, st, &fl);
     if (rc == LMPC_OK) { front_record(h, fl, nprob, LMPC_WALK_WAVE); rc = list_snapshot(h, cnt_now, nprob, st); }
     LMPC_TRY(prof.mid());
     if (rc == LMPC_OK)
-        rc = launch_wave(h, wave_args(h, work_list(h->dList, cnt_now, cnt_next, nprob)), nprob, theta, x, flag, iters, active, warm, st);
+        rc = launch_wave(h, wave_args(h, mode, work_list(h->dList, cnt_now, cnt_next, nprob)), nprob, theta, x, flag, iters, active, warm, st);
     return prof.end(rc);
 }
 
@@ -495,43 +496,43 @@ int qp_ab_choose(lmpc_handle *h, int64_t nprob, hipStream_t st, int *measure) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) { (void)hipGetLastError(); return 0; }
     for (int v = 0; v < 2; v++)
-        if (h->qpAbPending[v] && hipEventQuery(h->qpAbEv[v][1]) == hipSuccess) {
+        if (h->qpAb.pending[v] && hipEventQuery(h->qpAb.ev[v][1]) == hipSuccess) {
             float ms = 0.f;
-            if (hipEventElapsedTime(&ms, h->qpAbEv[v][0], h->qpAbEv[v][1]) == hipSuccess && h->qpAbN[v] > 0) {
+            if (hipEventElapsedTime(&ms, h->qpAb.ev[v][0], h->qpAb.ev[v][1]) == hipSuccess && h->qpAb.n[v] > 0) {
                 // the best of three samples per variant counts (a sample can hold unrelated queueing on the caller's stream)
-                const double ns = 1e6 * (double)ms / (double)h->qpAbN[v];
-                h->qpAbAcc[v] = (h->qpAbCnt[v] == 0 || ns < h->qpAbAcc[v]) ? ns : h->qpAbAcc[v];
-                h->qpAbCnt[v]++;
+                const double ns = 1e6 * (double)ms / (double)h->qpAb.n[v];
+                h->qpAb.acc[v] = (h->qpAb.cnt[v] == 0 || ns < h->qpAb.acc[v]) ? ns : h->qpAb.acc[v];
+                h->qpAb.cnt[v]++;
             }
-            h->qpAbPending[v] = false;
+            h->qpAb.pending[v] = false;
         }
-    if (h->qpAbCnt[0] >= 3 && h->qpAbCnt[1] >= 3) {
-        h->qpAbNsPer[0] = h->qpAbAcc[0]; h->qpAbNsPer[1] = h->qpAbAcc[1];
-        h->qpAbCnt[0] = h->qpAbCnt[1] = 0;
+    if (h->qpAb.cnt[0] >= 3 && h->qpAb.cnt[1] >= 3) {
+        h->qpAb.nsPer[0] = h->qpAb.acc[0]; h->qpAb.nsPer[1] = h->qpAb.acc[1];
+        h->qpAb.cnt[0] = h->qpAb.cnt[1] = 0;
     }
     (void)hipGetLastError();
-    const long long phase = h->qpAbCalls++ % 512;
+    const long long phase = h->qpAb.calls++ % 512;
     int variant;
-    if (phase < 6 && !h->qpAbPending[phase & 1]) {
+    if (phase < 6 && !h->qpAb.pending[phase & 1]) {
         variant = (int)(phase & 1);
         *measure = variant;
         for (int e = 0; e < 2; e++)
-            if (!h->qpAbEv[variant][e] && hipEventCreate(&h->qpAbEv[variant][e]) != hipSuccess) { *measure = -1; (void)hipGetLastError(); break; }
+            if (!h->qpAb.ev[variant][e] && hipEventCreate(&h->qpAb.ev[variant][e]) != hipSuccess) { *measure = -1; (void)hipGetLastError(); break; }
     } else {
-        variant = (h->qpAbNsPer[0] >= 0.0 && h->qpAbNsPer[1] >= 0.0 && h->qpAbNsPer[1] < h->qpAbNsPer[0]) ? 1 : 0;
+        variant = (h->qpAb.nsPer[0] >= 0.0 && h->qpAb.nsPer[1] >= 0.0 && h->qpAb.nsPer[1] < h->qpAb.nsPer[0]) ? 1 : 0;
     }
     return variant;
 }
 
 // ... the two event records around a call that is to be timed as variant `measure` (-1: none)
 int qp_ab_begin(lmpc_handle *h, int measure, hipStream_t st) {
-    if (measure >= 0) HIP_TRY(h, hipEventRecord(h->qpAbEv[measure][0], st));
+    if (measure >= 0) HIP_TRY(h, hipEventRecord(h->qpAb.ev[measure][0], st));
     return LMPC_OK;
 }
 int qp_ab_end(lmpc_handle *h, int measure, int rc, int64_t nprob, hipStream_t st) {
     if (measure >= 0 && rc == LMPC_OK) {
-        HIP_TRY(h, hipEventRecord(h->qpAbEv[measure][1], st));
-        h->qpAbN[measure] = nprob; h->qpAbPending[measure] = true;
+        HIP_TRY(h, hipEventRecord(h->qpAb.ev[measure][1], st));
+        h->qpAb.n[measure] = nprob; h->qpAb.pending[measure] = true;
     }
     return rc;
 }
@@ -539,18 +540,18 @@ int qp_ab_end(lmpc_handle *h, int measure, int rc, int64_t nprob, hipStream_t st
 // Small problems with many rows (lmpc_qp_tiers_kernel.hpp): the tiers pass over the whole batch -- it finishes what the
 // screening pass would and every problem on an append-only path, optimal or infeasible -- then the wavefront kernel on
 // its work list.  Cold plain binary64 solves in the n-chain form only.
-bool qp_tiers_applies(const lmpc_handle *h, int64_t nprob, const double *x, const int32_t *flag, const uint64_t *warm) {
+bool qp_tiers_applies(const lmpc_handle *h, const LoopMode &mode, int64_t nprob, const double *x, const int32_t *flag,
+                      const uint64_t *warm) {
     return h->qpTiersOk && h->qpTiers && h->useWave && !h->waveGram && !h->bnb && warm == nullptr && x != nullptr &&
-           flag != nullptr && h->asyncPhase == 0 && h->L.sim.FG == nullptr && h->waveSim.FG == nullptr && !h->keepOn &&
-           h->L.gat.state == nullptr && h->S.iter_limit > h->P.n + 2 && nprob < (int64_t)0x7fffffff && h->screen;
+           flag != nullptr && mode.plain() && h->S.iter_limit > h->P.n + 2 && nprob < (int64_t)0x7fffffff && h->screen;
 }
 
-int launch_wave_tiered(lmpc_handle *h, int64_t nprob, const double *theta, double *x, int32_t *flag, int32_t *iters,
-                       uint64_t *active, hipStream_t st) {
+int launch_wave_tiered(lmpc_handle *h, const LoopMode &mode, int64_t nprob, const double *theta, double *x, int32_t *flag,
+                       int32_t *iters, uint64_t *active, hipStream_t st) {
     LMPC_TRY(ensure_lists(h, nprob, st));
     LMPC_TRY(snapshot_prepare(h, nprob, st));
     ProfBracket prof(h, st);
-    LMPC_TRY(prof.begin(h->prof));
+    LMPC_TRY(prof.begin(h->prof && mode.prof));
     int32_t *cnt_now, *cnt_next;
     next_count_set(h, &cnt_now, &cnt_next);
     FrontLaunch fl;
@@ -558,7 +559,7 @@ int launch_wave_tiered(lmpc_handle *h, int64_t nprob, const double *theta, doubl
     if (rc == LMPC_OK) { front_record(h, fl, nprob, LMPC_WALK_WAVE); rc = list_snapshot(h, cnt_now, nprob, st); }
     LMPC_TRY(prof.mid());
     if (rc == LMPC_OK)
-        rc = launch_wave(h, wave_args(h, work_list(h->dList, cnt_now, cnt_next, nprob)), nprob, theta, x, flag, iters, active, nullptr, st);
+        rc = launch_wave(h, wave_args(h, mode, work_list(h->dList, cnt_now, cnt_next, nprob)), nprob, theta, x, flag, iters, active, nullptr, st);
     return prof.end(rc);
 }
 
@@ -585,18 +586,14 @@ int wave_probe(lmpc_handle *h, const double *theta, int64_t nprob, hipStream_t s
     DevBuf<int32_t> pf;
     HIP_TRY(h, px.reserve((size_t)kProbe * h->P.nout));
     if (pf.reserve((size_t)kProbe) != hipSuccess) return fail(h, LMPC_ERR_HIP, "lmpc: probe scratch");
-    int rc = LMPC_OK;
-    {
-        // the probe is a plain cold solve: closed-loop fusion, kept factors and profiling stay out of it
-        const Restore<SimFuse> noSim(h->L.sim, SimFuse{});
-        const Restore<WaveSim> noWaveSim(h->waveSim, WaveSim{});
-        const Restore<int> noPhase(h->asyncPhase, 0);
-        const Restore<bool> noKeep(h->keepOn, false), noProf(h->prof, false);
-        if (wave_screens(h, nprob)) rc = ensure_lists(h, nprob, st);          // (sized for the batch that follows, once)
-        if (rc == LMPC_OK)
-            rc = wave_screens(h, kProbe) ? launch_wave_screened(h, kProbe, theta, px, pf, nullptr, nullptr, nullptr, st)
-                                         : launch_wave(h, wave_args(h), kProbe, theta, px, pf, nullptr, nullptr, nullptr, st);
-    }
+    // the probe is a plain cold solve whatever the caller is in the middle of, without events; launched directly, so it
+    // cannot probe again
+    LoopMode plain;
+    plain.prof = false;
+    int rc = wave_screens(h, nprob) ? ensure_lists(h, nprob, st) : LMPC_OK;   // (sized for the batch that follows, once)
+    if (rc == LMPC_OK)
+        rc = wave_screens(h, kProbe) ? launch_wave_screened(h, plain, kProbe, theta, px, pf, nullptr, nullptr, nullptr, st)
+                                     : launch_wave(h, wave_args(h, plain), kProbe, theta, px, pf, nullptr, nullptr, nullptr, st);
     if (rc == LMPC_OK && h->dStat && h->hStat) {
         unsigned long long raw[64 * 16];
         if (hipMemcpyAsync(raw, h->dStat, sizeof(raw), hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess) {
@@ -615,29 +612,33 @@ int wave_probe(lmpc_handle *h, const double *theta, int64_t nprob, hipStream_t s
 // Scenario-asynchronous closed loop, streaming half (lmpc_simrun_kernel.hpp): every scenario -- first round -- or the
 // scenarios of the round before's list run ahead in registers to their next step that needs iterations; those go on
 // the work list the iterating half (lane kernel or wavefront kernel) consumes.
-int launch_sim_run(lmpc_handle *h, int64_t nprob, const double *theta, uint64_t *active, const uint64_t *warm, hipStream_t st) {
+int launch_sim_run(lmpc_handle *h, const LoopMode &mode, int64_t nprob, const double *theta, uint64_t *active, const uint64_t *warm,
+                   hipStream_t st) {
+    AsyncRound &ar = *mode.round;
     LMPC_TRY(ensure_lists(h, nprob, st));
     int32_t *cnt_now, *cnt_next;
     next_count_set(h, &cnt_now, &cnt_next);
-    h->asyncCntNow = cnt_now; h->asyncCntNext = cnt_next;
+    ar.cntNow = cnt_now; ar.cntNext = cnt_next;
     const long long segCap = lane_seg_cap(nprob);
     HIP_TRY(h, h->dList2.reserve((size_t)lane_seg_cap(h->listCap) * kShards));
     HIP_TRY(h, h->dList3.reserve((size_t)lane_seg_cap(h->listCap) * kShards));
     int32_t *parkCnt = h->dCount + 2 * (size_t)kShards * kCountStride;
     // first round: every scenario; later rounds: the scenarios of the round before's list, compacted
-    const int32_t *lin = h->asyncListIn, *cin = h->asyncCntIn;
+    const int32_t *lin = ar.listIn, *cin = ar.cntIn;
     int32_t *lout = (lin == h->dList) ? h->dList2 : h->dList;   // (the parked list as input: the work list is empty)
-    h->asyncListOut = lout;
-    const unsigned grid = lin ? (unsigned)(((h->asyncMaxIn + 255) / 256) * kShards) : (unsigned)((nprob + 255) / 256);
-    const SimFuse &Sf = h->L.sim;
-    const int nthp_ = h->L.nthp;
+    ar.listOut = lout;
+    const unsigned grid = lin ? (unsigned)(((ar.maxIn + 255) / 256) * kShards) : (unsigned)((nprob + 255) / 256);
+    PackLayout tmp;
+    const PackLayout &L = pack_layout(h, mode, tmp);
+    const SimFuse &Sf = L.sim;
+    const int nthp_ = L.nthp;
     const size_t mp_ = ((size_t)h->P.m + 7) & ~(size_t)7;
     const size_t ldsr = sizeof(double) * (mp_ * nthp_ + 2 * mp_ + (size_t)kMaxSimU * nthp_ + kMaxSimU + 64 + 8 * kMaxSimU);
     const bool small_ = h->simSmall && Sf.nx <= 4 && Sf.nu == 1 && h->P.m >= 1 && h->P.m <= 8 && h->P.nth <= 8;
-#define LMPC_SRUN_(NM, NT, SM) hipLaunchKernelGGL((sim_run_kernel<NM, NT, SM>), dim3(grid), dim3(256), ldsr, st, h->L, h->dC, \
-        const_cast<double *>(theta), Sf.kstep, h->asyncT, active, warm != nullptr ? 1 : 0, Sf.utraj, Sf.xtraj_base, \
-        Sf.flag_min, lout, cnt_now, segCap, kShards, (long long)nprob, lin, cin, h->asyncCap, h->dList3, parkCnt, \
-        h->asyncX, h->asyncR, h->asyncUp)
+#define LMPC_SRUN_(NM, NT, SM) hipLaunchKernelGGL((sim_run_kernel<NM, NT, SM>), dim3(grid), dim3(256), ldsr, st, L, h->dC, \
+        const_cast<double *>(theta), Sf.kstep, ar.T, active, warm != nullptr ? 1 : 0, Sf.utraj, Sf.xtraj_base, \
+        Sf.flag_min, lout, cnt_now, segCap, kShards, (long long)nprob, lin, cin, ar.cap, h->dList3, parkCnt, \
+        ar.x, ar.r, ar.up)
 #define LMPC_SRUN(NM, NT) do { if constexpr (NT <= 8) { if (small_) LMPC_SRUN_(NM, NT, true); else LMPC_SRUN_(NM, NT, false); } \
                             else LMPC_SRUN_(NM, NT, false); } while (0)
     switch (h->P.nth) {
@@ -652,36 +653,37 @@ int launch_sim_run(lmpc_handle *h, int64_t nprob, const double *theta, uint64_t 
 #undef LMPC_SRUN
 #undef LMPC_SRUN_
     HIP_TRY(h, hipGetLastError());
-    h->asyncX = h->asyncR = h->asyncUp = nullptr;       // only the first pass forms theta
-    if (h->asyncResetPark) HIP_TRY(h, hipMemsetAsync(parkCnt, 0, sizeof(int32_t) * kShards * kCountStride, st));
+    ar.x = ar.r = ar.up = nullptr;                      // only the first pass forms theta
+    if (ar.resetPark) HIP_TRY(h, hipMemsetAsync(parkCnt, 0, sizeof(int32_t) * kShards * kCountStride, st));
     return LMPC_OK;
 }
 
 // A batch on a wavefront-kernel handle: the tiers pass or the screening pass in front where they apply
-int launch_on_wave(lmpc_handle *h, int64_t nprob, const double *theta, double *x, int32_t *flag,
+int launch_on_wave(lmpc_handle *h, const LoopMode &mode, int64_t nprob, const double *theta, double *x, int32_t *flag,
                    int32_t *iters, uint64_t *active, const uint64_t *warm, hipStream_t st) {
     // scenario-asynchronous closed loop on the wavefront path: streaming half = sim_run_kernel on the handle's
     // screening pack, iterating half = the wavefront kernel on that pass's work list (it advances the scenarios
     // it solves, WaveSim)
-    if (h->asyncPhase == 1) return launch_sim_run(h, nprob, theta, active, warm, st);
-    if (h->asyncPhase == 2)
-        return launch_wave(h, wave_args(h, work_list(h->asyncListOut, h->asyncCntNow, h->asyncCntNext, nprob)), nprob, theta, x, flag,
+    if (const AsyncRound *ar = mode.round) {
+        if (ar->phase == 1) return launch_sim_run(h, mode, nprob, theta, active, warm, st);
+        return launch_wave(h, wave_args(h, mode, work_list(ar->listOut, ar->cntNow, ar->cntNext, nprob)), nprob, theta, x, flag,
                            iters, active, warm, st);
-    if (!h->waveProbed && h->L.sim.FG == nullptr && h->waveSim.FG == nullptr) LMPC_TRY(wave_probe(h, theta, nprob, st));
+    }
+    if (!h->waveProbed && mode.sim.FG == nullptr && mode.waveSim.FG == nullptr) LMPC_TRY(wave_probe(h, theta, nprob, st));
     auto screened_or_plain = [&]() {
-        return wave_screens(h, nprob) ? launch_wave_screened(h, nprob, theta, x, flag, iters, active, warm, st)
-                                      : launch_wave(h, wave_args(h), nprob, theta, x, flag, iters, active, warm, st);
+        return wave_screens(h, nprob) ? launch_wave_screened(h, mode, nprob, theta, x, flag, iters, active, warm, st)
+                                      : launch_wave(h, wave_args(h, mode), nprob, theta, x, flag, iters, active, warm, st);
     };
-    if (!qp_tiers_applies(h, nprob, x, flag, warm)) return screened_or_plain();
+    if (!qp_tiers_applies(h, mode, nprob, x, flag, warm)) return screened_or_plain();
     int measure = -1;
     const int variant = qp_ab_choose(h, nprob, st, &measure);
     LMPC_TRY(qp_ab_begin(h, measure, st));
-    const int rc = variant == 0 ? launch_wave_tiered(h, nprob, theta, x, flag, iters, active, st) : screened_or_plain();
+    const int rc = variant == 0 ? launch_wave_tiered(h, mode, nprob, theta, x, flag, iters, active, st) : screened_or_plain();
     return qp_ab_end(h, measure, rc, nprob, st);
 }
 
 // A batch on a lane-kernel handle: the one-launch kernel, or a front pass (screening, tiers, sim_run) and the lane kernel
-int launch_on_lanes(lmpc_handle *h, int64_t nprob, const double *theta, double *x, int32_t *flag,
+int launch_on_lanes(lmpc_handle *h, const LoopMode &mode, int64_t nprob, const double *theta, double *x, int32_t *flag,
                     int32_t *iters, uint64_t *active, const uint64_t *warm, hipStream_t st) {
     // block size: the one that keeps most wavefronts resident per CU under the 160 KiB LDS cap
     int bestB = 0, bestWaves = -1;
@@ -706,31 +708,34 @@ int launch_on_lanes(lmpc_handle *h, int64_t nprob, const double *theta, double *
     static_assert((kShards & (kShards - 1)) == 0, "the screening kernel masks the shard index");
     if (screened) LMPC_TRY(ensure_lists(h, nprob, st));
     ProfBracket prof(h, st);
-    LMPC_TRY(prof.begin(h->prof));
+    LMPC_TRY(prof.begin(h->prof && mode.prof));
     int rc = LMPC_OK;
     int ab_variant = 0, ab_measure = -1;          // (tiers pass on this path: measured like on the wavefront path)
-    const bool sim = h->L.sim.FG != nullptr;      // closed-loop instantiations (SimFuse), lmpc_simulate* only
-    const bool gather = !sim && h->L.gat.state != nullptr;   // generated-controller screening (GatherArgs)
+    const AsyncRound *const ar = mode.round;      // scenario-asynchronous closed loop: one of its two halves
+    PackLayout tmp;
+    const PackLayout &L = pack_layout(h, mode, tmp);
+    const bool sim = mode.sim.FG != nullptr;      // closed-loop instantiations (SimFuse), lmpc_simulate* only
+    const bool gather = !sim && mode.gat.state != nullptr;   // generated-controller screening (GatherArgs)
     const bool wide = !sim && !gather && h->P.nout > 1 && h->P.nout <= 16;   // several outputs: transposed stores
     const bool multi = !sim && h->P.nout > 1;                                  // ... and the iterating kernel's epilogue
     if (gather && !screened) return fail(h, LMPC_ERR_BADARG, "lmpc: gather mode needs the screening pass");
     // two counter sets used alternately: the iterating kernel of call k clears the set of call k+1
     int32_t *cnt_now = nullptr, *cnt_next = nullptr;
-    if (screened && h->asyncPhase == 2) {          // scenario-asynchronous closed loop, iterating half: the work
-        cnt_now = h->asyncCntNow;                  // list and its counters come from the sim_run pass before
-        cnt_next = h->asyncCntNext;
-    } else if (screened && h->asyncPhase == 1) {   // ... streaming half: sim_run_kernel instead of the screening pass
-        return launch_sim_run(h, nprob, theta, active, warm, st);
+    if (screened && ar && ar->phase == 2) {        // scenario-asynchronous closed loop, iterating half: the work
+        cnt_now = ar->cntNow;                      // list and its counters come from the sim_run pass before
+        cnt_next = ar->cntNext;
+    } else if (screened && ar) {                   // ... streaming half: sim_run_kernel instead of the screening pass
+        return launch_sim_run(h, mode, nprob, theta, active, warm, st);
     } else if (screened && !sim && warm == nullptr && (!gather || active == nullptr) && fast_covers(h)) {
         // small boxed problems, cold plain solve: ONE kernel streams the batch and solves what needs iterations
         // (lmpc_fast_kernel.hpp); no work list, no second launch
         // (an error word raised by an EARLIER call on this handle is reported here, before anything new is enqueued)
         rc = check_fast_err(h);
-        if (rc == LMPC_OK) rc = launch_fast(h, nprob, theta, x, flag, iters, active, st);
+        if (rc == LMPC_OK) rc = launch_fast(h, mode, nprob, theta, x, flag, iters, active, st);
         prof.skip_mid();     // one kernel: no event between "the two kernels" (each record is a packet the queue retires)
         return prof.end(rc);
-    } else if (screened && !sim && !gather && warm == nullptr && x != nullptr && flag != nullptr && h->qpTiersOk &&
-               h->qpTiers && h->P.ms < h->P.m && h->dCw != nullptr && h->S.iter_limit > h->P.n + 2 && h->asyncPhase == 0 &&
+    } else if (screened && mode.plain() && warm == nullptr && x != nullptr && flag != nullptr && h->qpTiersOk &&
+               h->qpTiers && h->P.ms < h->P.m && h->dCw != nullptr && h->S.iter_limit > h->P.n + 2 &&
                (ab_variant = qp_ab_choose(h, nprob, st, &ab_measure)) == 0) {
         // general rows on the lane path: the tiers pass (lmpc_qp_tiers_kernel.hpp) instead of the screening pass -- it
         // finishes every append-only path, the lane kernel walks the rest
@@ -745,19 +750,19 @@ int launch_on_lanes(lmpc_handle *h, int64_t nprob, const double *theta, double *
         LMPC_TRY(qp_ab_begin(h, ab_measure, st));
         next_count_set(h, &cnt_now, &cnt_next);
         FrontLaunch fl;
-        rc = launch_screen_any(h, sim ? 1 : (gather ? 2 : (wide ? 3 : 0)), nprob, theta, x, flag, iters, active, warm, cnt_now, st, &fl);
+        rc = launch_screen_any(h, L, sim ? 1 : (gather ? 2 : (wide ? 3 : 0)), nprob, theta, x, flag, iters, active, warm, cnt_now, st, &fl);
         if (rc == LMPC_OK) { front_record(h, fl, nprob, LMPC_WALK_LANE); rc = list_snapshot(h, cnt_now, nprob, st); }
     }
     LMPC_TRY(prof.mid());
-    const int32_t *list = screened ? (h->asyncPhase == 2 ? h->asyncListOut : h->dList) : nullptr;
+    const int32_t *list = screened ? (ar ? ar->listOut : h->dList) : nullptr;
     const int32_t *count = cnt_now;
     // problems whose constraints are exactly the n simple bounds (ms == m == n == N) get the
     // instantiation with the row scans unrolled and the working-set capacity cut to N
     const bool boxed = h->P.m == h->laneN && h->P.n == h->laneN && h->P.ms == h->P.m;
     if (rc == LMPC_OK) switch (h->laneN) {
-#define LMPC_LN(NN, MSS, MAA) (sim ? launch_lane<NN, MSS, MAA, true, false>(h, bestB, bestLds, nprob, theta, x, flag, iters, active, warm, list, count, cnt_next, st) \
-                               : (multi && NN <= 6) ? launch_lane<NN, MSS, MAA, false, (NN <= 6)>(h, bestB, bestLds, nprob, theta, x, flag, iters, active, warm, list, count, cnt_next, st) \
-                                   : launch_lane<NN, MSS, MAA, false, false>(h, bestB, bestLds, nprob, theta, x, flag, iters, active, warm, list, count, cnt_next, st))
+#define LMPC_LN(NN, MSS, MAA) (sim ? launch_lane<NN, MSS, MAA, true, false>(h, L, bestB, bestLds, nprob, theta, x, flag, iters, active, warm, list, count, cnt_next, st) \
+                               : (multi && NN <= 6) ? launch_lane<NN, MSS, MAA, false, (NN <= 6)>(h, L, bestB, bestLds, nprob, theta, x, flag, iters, active, warm, list, count, cnt_next, st) \
+                                   : launch_lane<NN, MSS, MAA, false, false>(h, L, bestB, bestLds, nprob, theta, x, flag, iters, active, warm, list, count, cnt_next, st))
 #define LMPC_CASE(NN) case NN: rc = boxed ? LMPC_LN(NN, NN, NN) : LMPC_LN(NN, 0, NN + 1); break;
         LMPC_CASE(2) LMPC_CASE(3) LMPC_CASE(4) LMPC_CASE(5) LMPC_CASE(6) LMPC_CASE(8) LMPC_CASE(10) LMPC_CASE(12)
 #undef LMPC_CASE
@@ -767,16 +772,16 @@ int launch_on_lanes(lmpc_handle *h, int64_t nprob, const double *theta, double *
     return prof.end(qp_ab_end(h, ab_measure, rc, nprob, st));
 }
 
-int launch(lmpc_handle *h, int64_t nprob, const double *theta, double *x, int32_t *flag,
+int launch(lmpc_handle *h, const LoopMode &mode, int64_t nprob, const double *theta, double *x, int32_t *flag,
            int32_t *iters, uint64_t *active, const uint64_t *warm, hipStream_t st) {
     if (h->avi) {
         // non-symmetric H (variational objective): its own kernel; timing events around the one launch
         ProfBracket prof(h, st);
-        LMPC_TRY(prof.begin(h->prof, false));
+        LMPC_TRY(prof.begin(h->prof && mode.prof, false));
         return prof.end(launch_avi(h, nprob, theta, x, flag, iters, active, warm, st));
     }
-    return h->useWave ? launch_on_wave(h, nprob, theta, x, flag, iters, active, warm, st)
-                      : launch_on_lanes(h, nprob, theta, x, flag, iters, active, warm, st);
+    return h->useWave ? launch_on_wave(h, mode, nprob, theta, x, flag, iters, active, warm, st)
+                      : launch_on_lanes(h, mode, nprob, theta, x, flag, iters, active, warm, st);
 }
 
 // scratch of the closed-loop entry points (binary64-sized; the binary32 loop uses the same buffers)
@@ -795,8 +800,8 @@ int ensure_sim(lmpc_handle *h, int64_t N) {
 
 // what the second API unit (lmpc_api_loop.hip: closed loop, generated controller, observer) needs of this one
 namespace lmpc {
-int api_launch(lmpc_handle *h, int64_t nprob, const double *theta, double *x, int32_t *flag, int32_t *iters, uint64_t *active,
-               const uint64_t *warm, hipStream_t st) { return launch(h, nprob, theta, x, flag, iters, active, warm, st); }
+int api_launch(lmpc_handle *h, const LoopMode &mode, int64_t nprob, const double *theta, double *x, int32_t *flag, int32_t *iters,
+               uint64_t *active, const uint64_t *warm, hipStream_t st) { return launch(h, mode, nprob, theta, x, flag, iters, active, warm, st); }
 int api_ensure_sim(lmpc_handle *h, int64_t N) { return ensure_sim(h, N); }
 int api_ensure_f32(lmpc_handle *h) { return ensure_f32(h); }
 bool api_will_screen(const lmpc_handle *h, int64_t nprob) { return will_screen(h, nprob); }
@@ -804,7 +809,7 @@ bool api_wave_screens(const lmpc_handle *h, int64_t nprob) { return wave_screens
 int api_wave_probe(lmpc_handle *h, const double *theta, int64_t nprob, hipStream_t st) { return wave_probe(h, theta, nprob, st); }
 int api_launch_wave_f32(lmpc_handle *h, const float *dC, int64_t nprob, const float *theta, float *x, int32_t *flag, int32_t *iters,
                         uint64_t *active, const uint64_t *warm, hipStream_t st) {
-    return launch_wave_t<float>(h, wave_args(h), dC, nprob, theta, x, flag, iters, active, warm, st);
+    return launch_wave_t<float>(h, wave_args(h, LoopMode{}), dC, nprob, theta, x, flag, iters, active, warm, st);
 }
 }  // namespace lmpc
 
@@ -842,12 +847,12 @@ static void preload_code(lmpc_handle *h) {
         if (h->qpTiersOk && (h->useWave || h->P.ms < h->P.m))
             (void)launch_qp_tiers(h, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, true);
         if (h->dCw && h->useWave) {
-            h->preloadOnly = true;
-            (void)launch_wave(h, wave_args(h), 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+            WaveArgs load = wave_args(h, LoopMode{});
+            load.preload = true;
+            (void)launch_wave(h, load, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
             // (hybrid problems are the ones solved in binary32 too -- lmpc_solve_batch_f32*: that unit and its pack as well)
             if (h->bnb && ensure_f32(h) == LMPC_OK)
-                (void)launch_wave_t<float>(h, wave_args(h), h->dCwf, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-            h->preloadOnly = false;
+                (void)launch_wave_t<float>(h, load, h->dCwf, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
         }
     }
     (void)hipGetLastError();
@@ -952,6 +957,11 @@ int lmpc_setup_ldp(lmpc_handle **out, int n, int m, int ms, int nth, int nout, c
     return LMPC_OK;
 }
 
+// an array of a pack into the caller's buffer, where the caller gave one
+static void cp(double *dst, const std::vector<double> &src) {
+    if (dst && !src.empty()) std::memcpy(dst, src.data(), sizeof(double) * src.size());
+}
+
 int lmpc_transform(int n, int m, int ms, int nth, int nout, const double *H, const double *f,
                    const double *f_theta, const double *A, const double *bu, const double *bl,
                    const double *W, const int32_t *sense, const double *Kfb, int nx, double *M,
@@ -960,18 +970,12 @@ int lmpc_transform(int n, int m, int ms, int nth, int nout, const double *H, con
     std::string err;
     int rc = qp_to_ldp(P, n, m, ms, nth, nout, H, f, f_theta, A, bu, bl, W, sense, Kfb, nx, err);
     if (rc != LMPC_OK) return fail(nullptr, rc, err);
-    auto cp = [](double *dst, const std::vector<double> &src) {
-        if (dst && !src.empty()) std::memcpy(dst, src.data(), sizeof(double) * src.size());
-    };
     cp(M, P.M); cp(du, P.du0); cp(dl, P.dl0); cp(Dth, P.Dth); cp(Rout, P.Rout); cp(x0, P.x0); cp(Xth, P.Xth);
     return LMPC_OK;
 }
 
 int lmpc_get_prox(const lmpc_handle *h, double *Hinv, double *x0f, double *Xthf, double *Kth) {
     if (!h || !h->P.prox) return LMPC_ERR_BADARG;
-    auto cp = [](double *dst, const std::vector<double> &src) {
-        if (dst && !src.empty()) std::memcpy(dst, src.data(), sizeof(double) * src.size());
-    };
     cp(Hinv, h->P.Hinv); cp(x0f, h->P.x0f); cp(Xthf, h->P.Xthf); cp(Kth, h->P.Kth);
     return LMPC_OK;
 }
@@ -984,9 +988,6 @@ int lmpc_transform_avi(int n, int m, int ms, int nth, int nout, const double *H,
     std::string err;
     int rc = qp_to_avi(P, n, m, ms, nth, nout, H, f, f_theta, A, bu, bl, W, sense, Kfb, nx, err);
     if (rc != LMPC_OK) return fail(nullptr, rc, err);
-    auto cp = [](double *dst, const std::vector<double> &src) {
-        if (dst && !src.empty()) std::memcpy(dst, src.data(), sizeof(double) * src.size());
-    };
     cp(ML, P.M); cp(MR, P.MR); cp(G, P.Gf); cp(du, P.du0); cp(dl, P.dl0); cp(Dth, P.Dth); cp(Rout, P.Rout);
     cp(x0, P.x0); cp(Xth, P.Xth);
     return LMPC_OK;
@@ -996,9 +997,6 @@ int lmpc_get_ldp(const lmpc_handle *h, double *M, double *du, double *dl, double
                  double *x0, double *Xth, int32_t *sense) {
     if (!h) return LMPC_ERR_BADARG;
     const HostPack &P = h->P;
-    auto cp = [](double *dst, const std::vector<double> &src) {
-        if (dst && !src.empty()) std::memcpy(dst, src.data(), sizeof(double) * src.size());
-    };
     cp(M, P.M); cp(du, P.du0); cp(dl, P.dl0); cp(Dth, P.Dth); cp(Rout, P.Rout); cp(x0, P.x0); cp(Xth, P.Xth);
     if (sense && !P.sense.empty()) std::memcpy(sense, P.sense.data(), sizeof(int32_t) * P.sense.size());
     return LMPC_OK;
@@ -1031,7 +1029,7 @@ int lmpc_solve_batch_device(lmpc_handle *h, int64_t N, const double *theta, doub
     if (N == 0) return LMPC_OK;
     if (N > (int64_t)0x7fffffff * 64) return fail(h, LMPC_ERR_BADARG, "lmpc: batch too large for one launch");
     LMPC_ENTER_DEVICE(h);
-    return launch(h, N, theta, x, exitflag, iters, active, warm, (hipStream_t)stream);
+    return launch(h, LoopMode{}, N, theta, x, exitflag, iters, active, warm, (hipStream_t)stream);
 }
 
 // SEVERAL batches of N points each in one call (round 5): on the handles the one-launch kernel covers -- the headline's
@@ -1050,8 +1048,7 @@ int lmpc_solve_batches_device(lmpc_handle *h, int32_t n_batches, int64_t N, cons
     if (N > (int64_t)0x7fffffff * 64) return fail(h, LMPC_ERR_BADARG, "lmpc: batch too large for one launch");
     LMPC_ENTER_DEVICE(h);
     hipStream_t st = (hipStream_t)stream;
-    const bool one_launch = !h->avi && !h->useWave && h->asyncPhase == 0 && h->L.sim.FG == nullptr && h->L.gat.state == nullptr &&
-                            will_screen(h, N) && fast_covers(h) && !h->prof;
+    const bool one_launch = !h->avi && !h->useWave && will_screen(h, N) && fast_covers(h) && !h->prof;
     int done = 0;
     while (done < n_batches) {
         const int nb = n_batches - done < 8 ? n_batches - done : 8;
@@ -1062,7 +1059,7 @@ int lmpc_solve_batches_device(lmpc_handle *h, int32_t n_batches, int64_t N, cons
         }
         if (rc == LMPC_ERR_UNSUPPORTED) {
             for (int b = 0; b < nb; b++) {
-                rc = launch(h, N, theta[done + b], x[done + b], exitflag[done + b], nullptr, nullptr, nullptr, st);
+                rc = launch(h, LoopMode{}, N, theta[done + b], x[done + b], exitflag[done + b], nullptr, nullptr, nullptr, st);
                 if (rc != LMPC_OK) return rc;
             }
         } else if (rc != LMPC_OK) {
@@ -1084,7 +1081,7 @@ int lmpc_solve_batch_f32_device(lmpc_handle *h, int64_t N, const float *theta, f
     LMPC_ENTER_DEVICE(h);
     int rc = ensure_f32(h);
     if (rc != LMPC_OK) return rc;
-    return launch_wave_t<float>(h, wave_args(h), h->dCwf, N, theta, x, exitflag, iters, active, warm, (hipStream_t)stream);
+    return launch_wave_t<float>(h, wave_args(h, LoopMode{}), h->dCwf, N, theta, x, exitflag, iters, active, warm, (hipStream_t)stream);
 }
 
 // ONE theta, as the reference's online call has it (utils.jl:268-283; compute_control in a Simulation loop): no staging
@@ -1109,7 +1106,7 @@ int lmpc_solve_one(lmpc_handle *h, const double *theta, double *x) {
     if (nth) std::memcpy(h->oneHost, theta, sizeof(double) * nth);
     int32_t *hflag = reinterpret_cast<int32_t *>(h->oneHost + oF);
     *hflag = LMPC_EXIT_UNFINISHED;
-    const int rc = launch(h, 1, reinterpret_cast<const double *>(h->oneDev), reinterpret_cast<double *>(h->oneDev + oX),
+    const int rc = launch(h, LoopMode{}, 1, reinterpret_cast<const double *>(h->oneDev), reinterpret_cast<double *>(h->oneDev + oX),
                           reinterpret_cast<int32_t *>(h->oneDev + oF), nullptr, nullptr, nullptr, h->oneStream);
     const hipError_t es = hipStreamSynchronize(h->oneStream);      // (also after a failed launch: nothing may still run)
     if (rc != LMPC_OK) return rc;
@@ -1123,7 +1120,7 @@ int lmpc_solve_one(lmpc_handle *h, const double *theta, double *x) {
 int lmpc_wave_stats(lmpc_handle *h, unsigned long long out[5]) {
     if (!h || !out) return LMPC_ERR_BADARG;
     wave_stat_read(h, out);
-    out[4] = (unsigned long long)wave_first_pass_cap(h, (int64_t)1 << 20);
+    out[4] = (unsigned long long)wave_first_pass_cap(h, wave_args(h, LoopMode{}), (int64_t)1 << 20);
     return LMPC_OK;
 }
 
@@ -1185,8 +1182,9 @@ const char *lmpc_kernel_name(const lmpc_handle *h) {
             return wname.c_str();
         }
         // (large cold plain binary64 batches: four problems per wavefront where that kernel is the default)
-        if (row_pass_cap(const_cast<lmpc_handle *>(h), (int64_t)1 << 20, sizeof(double), false, h->waveGram != 0, h->bnb) > 0) return "row|wave";
-        if (h->bnb && row_bnb_pass_cap(const_cast<lmpc_handle *>(h), (int64_t)1 << 20, sizeof(double)) > 0) return "row|wave";
+        const WaveArgs plain = wave_args(h, LoopMode{});
+        if (row_pass_cap(const_cast<lmpc_handle *>(h), plain, (int64_t)1 << 20, sizeof(double), false, h->waveGram != 0, h->bnb) > 0) return "row|wave";
+        if (h->bnb && row_bnb_pass_cap(const_cast<lmpc_handle *>(h), plain, (int64_t)1 << 20, sizeof(double)) > 0) return "row|wave";
         return "wave";
     }
     // small boxed problems: cold plain batches take the one-launch kernel, everything else on the handle (warm
@@ -1311,11 +1309,7 @@ int lmpc_set_option(lmpc_handle *h, const char *name, int value) {
     if (std::strcmp(name, "region_blocks") == 0) { h->regBlocks = value < 0 ? 0 : (value > 16 ? 16 : value); return LMPC_OK; }
     if (std::strcmp(name, "avi_waves") == 0) { h->aviWaves = value < 0 ? 0 : (value > 32 ? 32 : value); return LMPC_OK; }
     if (std::strcmp(name, "avi_chain_groups") == 0) { h->aviChainGroups = value < 0 ? 0 : value; return LMPC_OK; }
-    if (std::strcmp(name, "qp_tiers") == 0) {
-        h->qpTiers = value < 0 ? 0 : (value > 2 ? 2 : value);
-        h->qpAbCalls = 0; h->qpAbNsPer[0] = h->qpAbNsPer[1] = -1.0; h->qpAbPending[0] = h->qpAbPending[1] = false; h->qpAbCnt[0] = h->qpAbCnt[1] = 0;   // (measure again)
-        return LMPC_OK;
-    }
+    if (std::strcmp(name, "qp_tiers") == 0) { h->qpTiers = value < 0 ? 0 : (value > 2 ? 2 : value); h->qpAb.reset(); return LMPC_OK; }
     if (std::strcmp(name, "list_snapshot") == 0) {
         // (tests: what a front pass left on the work list, lmpc_work_list_read; the buffer for the lists the handle
         // holds now, a larger batch grows it)
@@ -1334,7 +1328,7 @@ int lmpc_set_option(lmpc_handle *h, const char *name, int value) {
         if (!value && (h->laneN == 0 || h->bnb))
             return fail(h, LMPC_ERR_UNSUPPORTED, "lmpc: lane kernel does not cover this problem");
         h->useWave = value != 0;
-        h->qpAbCalls = 0; h->qpAbNsPer[0] = h->qpAbNsPer[1] = -1.0; h->qpAbPending[0] = h->qpAbPending[1] = false; h->qpAbCnt[0] = h->qpAbCnt[1] = 0;   // (another path: measured again)
+        h->qpAb.reset();                                 // (another path: measured again)
         return LMPC_OK;
     }
     return fail(h, LMPC_ERR_BADARG, std::string("lmpc_set_option: unknown option ") + name);
@@ -1360,9 +1354,9 @@ int lmpc_reserve(lmpc_handle *h, int64_t N, void *stream) {
         if (pt.reserve(nr) != hipSuccess || pf.reserve(4) != hipSuccess) { (void)hipGetLastError(); return LMPC_OK; }
         int rc = LMPC_OK;
         if (hipMemsetAsync(pt, 0, sizeof(double) * nr, st) == hipSuccess) {
-            const Restore<bool> noProf(h->prof, false);        // (not a batch: no events, no probe)
-            const Restore<int> noProbe(h->waveProbe, 0);
-            rc = launch_wave(h, wave_args(h), 1, pt, pt + h->P.nth, pf, nullptr, nullptr, nullptr, st);
+            LoopMode quiet;                                    // (not a batch: no events; launched directly: no probe)
+            quiet.prof = false;
+            rc = launch_wave(h, wave_args(h, quiet), 1, pt, pt + h->P.nth, pf, nullptr, nullptr, nullptr, st);
             (void)hipStreamSynchronize(st);
         }
         (void)hipGetLastError();
@@ -1406,7 +1400,7 @@ const char *lmpc_last_error(const lmpc_handle *h) { return h ? h->err.c_str() : 
 lmpc_handle::~lmpc_handle() {
     for (auto &ev : events) { hipEventDestroy(ev.a); if (ev.mid) hipEventDestroy(ev.mid); hipEventDestroy(ev.b); }
     for (auto &e : eventPool) hipEventDestroy(e);
-    for (int v = 0; v < 2; v++) for (int e = 0; e < 2; e++) if (qpAbEv[v][e]) hipEventDestroy(qpAbEv[v][e]);
+    for (int v = 0; v < 2; v++) for (int e = 0; e < 2; e++) if (qpAb.ev[v][e]) hipEventDestroy(qpAb.ev[v][e]);
     if (oneStream) hipStreamDestroy(oneStream);
     if (hFastErr && *hFastErr != 0) std::fprintf(stderr, "lmpc_free: unreported error word %d of the one-launch kernel\n", (int)*hFastErr);
     for (auto &e : pipeEv) hipEventDestroy(e);

@@ -3,6 +3,9 @@
 // (lmpc_set_parameter_layout, lmpc_compute_control*, lmpc_form_parameter_device) and the generated observer
 // (lmpc_set_observer, lmpc_predict_state*, lmpc_correct_state*).  Setup, the plain solves, options and the launch
 // policy stay in lmpc_api.hip; this unit reaches them through the api_* functions of lmpc_internal.hpp.
+// What a loop wants of a launch -- lmpc_simulate_device: the fused plant step, the scenario-asynchronous rounds, the kept
+// factors, no profiling inside the rounds; lmpc_compute_control_device: the gather -- it says in a LoopMode on its own
+// stack, an argument of api_launch.  Nothing of it is written to the handle, so there is nothing to take back.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -28,25 +31,6 @@ void loop_preload() {
 }  // namespace lmpc
 
 namespace {
-// What a closed loop lends to api_launch through the handle -- lmpc_simulate_device: the fused plant step, the
-// scenario-asynchronous rounds, the kept factors, profiling switched off; lmpc_compute_control_device: the gather -- is
-// taken back when the entry point returns, on EVERY path: the handle is then as an ordinary solve expects it.
-struct HandleLoan {
-    lmpc_handle *h;
-    const bool prof;
-    explicit HandleLoan(lmpc_handle *h_) : h(h_), prof(h_->prof) {}
-    HandleLoan(const HandleLoan &) = delete;
-    HandleLoan &operator=(const HandleLoan &) = delete;
-    ~HandleLoan() {
-        h->L.sim = SimFuse{}; h->L.gat = GatherArgs{}; h->waveSim = WaveSim{};
-        h->keepOn = false; h->raWarm = false;
-        h->asyncPhase = 0; h->asyncT = 0; h->asyncCap = 0; h->asyncResetPark = false;
-        h->asyncX = h->asyncR = h->asyncUp = nullptr;
-        h->asyncListIn = h->asyncCntIn = nullptr;
-        h->prof = prof;
-    }
-};
-
 // host-pointer closed loop in either precision: device copies of the caller's arrays around lmpc_simulate_device /
 // lmpc_simulate_f32_device.  uprev == NULL: zeros, and nothing copied back.  The binary64 loop only enqueues, so the
 // device is synchronised before the results are read; the binary32 one leaves that to the blocking copies.
@@ -80,8 +64,8 @@ int simulate_host(lmpc_handle *h, int64_t N, int T, int nx, int nr, int nuprev, 
 extern "C" {
 
 // per-scenario kept closed-loop state of the wavefront path (working set + factorisation, lmpc_wave_kernel.hpp): makes
-// room for N scenarios if the device has it to spare, marks every state "nothing kept", sets h->keepOn
-static int ensure_keep(lmpc_handle *h, int64_t N, hipStream_t st) {
+// room for N scenarios if the device has it to spare and marks every state "nothing kept"; *keep: whether room was made
+static int ensure_keep(lmpc_handle *h, int64_t N, hipStream_t st, bool *keep) {
     const size_t keepR = (size_t)h->W.keepStride, keepI = 5 * 64;
     if (N > h->keepCap) {
         h->dKeepR.reset(); h->dKeepI.reset(); h->keepCap = 0;
@@ -99,7 +83,7 @@ static int ensure_keep(lmpc_handle *h, int64_t N, hipStream_t st) {
     if (N <= h->keepCap) {
         // nothing kept yet: the size word of every scenario's state to -1
         HIP_TRY(h, hipMemset2DAsync(h->dKeepI + 256, sizeof(int32_t) * keepI, 0xFF, sizeof(int32_t), (size_t)N, st));
-        h->keepOn = true;
+        *keep = true;
     }
     return LMPC_OK;
 }
@@ -159,76 +143,85 @@ int lmpc_simulate_device(lmpc_handle *h, int64_t N, int T, int nx, int nr, int n
     // in registers through its unconstrained steps and only the steps that need iterations go through the
     // iterating kernel, one round per such step.  The host reads the work-list counters after every
     // streaming pass (one stream synchronisation per round) and stops when nothing is queued any more.
-    const HandleLoan loan(h);
+    LoopMode mode;
+    // the records back into the caller's x and uprev: the last thing each of the three fused loops enqueues
+    auto unpack = [&](const double *records) -> int {
+        hipLaunchKernelGGL(unpack_theta_kernel, dim3(grid), dim3(256), 0, st, records, x, nuprev > 0 ? uprev : nullptr, nx, nr,
+                           nuprev, (long long)N);
+        HIP_TRY(h, hipGetLastError());
+        return LMPC_OK;
+    };
     if (asyncLoop) {
-        h->asyncX = x; h->asyncR = r; h->asyncUp = nuprev > 0 ? uprev : nullptr;
+        AsyncRound ar;
+        ar.x = x; ar.r = r; ar.up = nuprev > 0 ? uprev : nullptr;
         HIP_TRY(h, hipMemcpyAsync(h->dC + h->L.oFG, F, sizeof(double) * nx * nx, hipMemcpyHostToDevice, st));
         HIP_TRY(h, hipMemcpyAsync(h->dC + h->L.oFG + nx * nx, G, sizeof(double) * nx * nu, hipMemcpyHostToDevice, st));
         HIP_TRY(h, h->simK.reserve((size_t)h->simCap));
         HIP_TRY(h, hipMemsetAsync(h->simK, 0, sizeof(int32_t) * (size_t)N, st));
         if (warm) HIP_TRY(h, hipMemsetAsync(h->simAct, 0, sizeof(uint64_t) * (size_t)N * (size_t)h->P.words(), st));   // first step is cold
-        h->prof = false;
-        h->asyncT = T;
-        h->L.sim = SimFuse{h->simFG, h->simTheta, flag_min, nullptr, nx, nu, nr, nuprev, 0, h->simK, U_traj, X_traj,
+        mode.round = &ar;
+        mode.prof = false;
+        ar.T = T;
+        mode.sim = SimFuse{h->simFG, h->simTheta, flag_min, nullptr, nx, nu, nr, nuprev, 0, h->simK, U_traj, X_traj,
                            (long long)N};
-        h->raWarm = warm != 0;
-        if (h->useWave && runAhead && warm && T > 1 && wave_first_pass_cap(h, N) > 0) {
+        mode.raWarm = warm != 0;
+        // (asked with raWarm set but mode.waveSim still empty and nothing kept: a plain call's answer.  It has to be -- with
+        // the run-ahead loop filled in, "two passes?" is answered "no" for want of the keep a "yes" is about to make room for)
+        if (h->useWave && runAhead && warm && T > 1 && wave_first_pass_cap(h, wave_args(h, mode), N) > 0) {
             // (a first pass at a smaller capacity is in sight: it writes every scenario's state out after each step, so
             // that a step which outgrows it restarts exactly where the step-synchronous loop would)
-            const int rck = ensure_keep(h, N, st);
+            const int rck = ensure_keep(h, N, st, &mode.keep);
             if (rck != LMPC_OK) return rck;
         }
-        if (h->useWave) h->waveSim = WaveSim{h->simFG, h->simK, U_traj, X_traj, flag_min, nx, nu, nr, nuprev, (long long)N, -1, runAhead ? T : 0};
+        if (h->useWave) mode.waveSim = WaveSim{h->simFG, h->simK, U_traj, X_traj, flag_min, nx, nu, nr, nuprev, (long long)N, -1, runAhead ? T : 0};
         constexpr int kBurst = 2;   // steps a scenario of a (short) work list may run ahead before it is parked
         const size_t setLen = (size_t)kShards * kCountStride;
         std::vector<int32_t> hc(3 * setLen);
         uint64_t *masks = warm ? h->simAct : nullptr;
         int rc = LMPC_OK;
-        h->asyncListIn = h->asyncCntIn = nullptr;
-        h->asyncCap = T + 1;
-        h->asyncResetPark = false;
+        ar.cap = T + 1;
         const bool dbg = std::getenv("LMPC_DEBUG_SIM") != nullptr;
         // pass 0 runs every scenario up to its first step that needs iterations; then: solve that step for the
         // listed scenarios, let them run ahead a little (most meet the next such step at once: the transient),
         // park the ones that broke free; when the list has drained, run the parked ones on, compacted.
         bool drained = false;
         for (int pass = 0; pass <= 2 * T + 4 && rc == LMPC_OK; pass++) {
-            h->asyncPhase = 1;
-            rc = api_launch(h, N, h->simTheta, nullptr, nullptr, nullptr, masks, masks, st);
+            ar.phase = 1;
+            rc = api_launch(h, mode, N, h->simTheta, nullptr, nullptr, nullptr, masks, masks, st);
             if (rc != LMPC_OK) break;
             if (hipMemcpyAsync(hc.data(), h->dCount, sizeof(int32_t) * hc.size(), hipMemcpyDeviceToHost, st) != hipSuccess ||
                 hipStreamSynchronize(st) != hipSuccess) { rc = fail(h, LMPC_ERR_HIP, "lmpc_simulate: reading the work-list counters"); break; }
-            const size_t off = (size_t)(h->asyncCntNow - h->dCount);
+            const size_t off = (size_t)(ar.cntNow - h->dCount);
             long long queued = 0, longest = 0, parked = 0, plongest = 0;
             for (int sh = 0; sh < kShards; sh++) {
-                const long long q = hc[off + (size_t)sh * kCountStride], pk = h->asyncResetPark ? 0 : hc[2 * setLen + (size_t)sh * kCountStride];
+                const long long q = hc[off + (size_t)sh * kCountStride], pk = ar.resetPark ? 0 : hc[2 * setLen + (size_t)sh * kCountStride];
                 queued += q; parked += pk;
                 longest = q > longest ? q : longest;
                 plongest = pk > plongest ? pk : plongest;
             }
             if (dbg) std::fprintf(stderr, "lmpc sim pass %d: %lld scenarios queued, %lld parked\n", pass, queued, parked);
-            h->asyncResetPark = false;
+            ar.resetPark = false;
             if (queued > 0) {
-                h->asyncPhase = 2;
-                rc = api_launch(h, N, h->simTheta, nullptr, nullptr, nullptr, masks, masks, st);
-                h->asyncListIn = h->asyncListOut; h->asyncCntIn = h->asyncCntNow; h->asyncMaxIn = longest;
-                h->asyncCap = kBurst;
+                ar.phase = 2;
+                rc = api_launch(h, mode, N, h->simTheta, nullptr, nullptr, nullptr, masks, masks, st);
+                ar.listIn = ar.listOut; ar.cntIn = ar.cntNow; ar.maxIn = longest;
+                ar.cap = kBurst;
                 // a few more rounds without asking: a list never grows from one round to the next, so the grid of
                 // `longest` covers them, and a round on an empty list costs less than the host round trip it saves
                 for (int e = 0; e < h->simBlind && rc == LMPC_OK; e++) {
-                    h->asyncPhase = 1;
-                    rc = api_launch(h, N, h->simTheta, nullptr, nullptr, nullptr, masks, masks, st);
+                    ar.phase = 1;
+                    rc = api_launch(h, mode, N, h->simTheta, nullptr, nullptr, nullptr, masks, masks, st);
                     if (rc != LMPC_OK) break;
-                    h->asyncPhase = 2;
-                    rc = api_launch(h, N, h->simTheta, nullptr, nullptr, nullptr, masks, masks, st);
-                    h->asyncListIn = h->asyncListOut; h->asyncCntIn = h->asyncCntNow;
+                    ar.phase = 2;
+                    rc = api_launch(h, mode, N, h->simTheta, nullptr, nullptr, nullptr, masks, masks, st);
+                    ar.listIn = ar.listOut; ar.cntIn = ar.cntNow;
                 }
             } else if (parked > 0) {
                 // no iterating kernel ran, so nobody cleared the counter set the next pass writes
                 if (hipMemsetAsync(h->dCount, 0, sizeof(int32_t) * 2 * setLen, st) != hipSuccess) { rc = fail(h, LMPC_ERR_HIP, "lmpc_simulate: clearing the work-list counters"); break; }
-                h->asyncListIn = h->dList3; h->asyncCntIn = h->dCount + 2 * setLen; h->asyncMaxIn = plongest;
-                h->asyncCap = T + 1;
-                h->asyncResetPark = true;
+                ar.listIn = h->dList3; ar.cntIn = h->dCount + 2 * setLen; ar.maxIn = plongest;
+                ar.cap = T + 1;
+                ar.resetPark = true;
             } else {
                 drained = true;
                 break;
@@ -241,11 +234,7 @@ int lmpc_simulate_device(lmpc_handle *h, int64_t N, int T, int nx, int nr, int n
                                        "still queued (lmpc_set_option(\"sim_async\", 0) runs the step-synchronous loop)");
         // the last streaming pass queued nothing, so no iterating kernel cleared the other counter set
         if (h->dCount) { hipMemsetAsync(h->dCount, 0, sizeof(int32_t) * 3 * kShards * kCountStride, st); h->countSet = 0; }
-        if (rc != LMPC_OK) return rc;
-        hipLaunchKernelGGL(unpack_theta_kernel, dim3(grid), dim3(256), 0, st, h->simTheta, x, nuprev > 0 ? uprev : nullptr,
-                           nx, nr, nuprev, (long long)N);
-        HIP_TRY(h, hipGetLastError());
-        return LMPC_OK;
+        return rc != LMPC_OK ? rc : unpack(h->simTheta);
     }
     if (!h->useWave && h->simFused && nu <= kMaxSimU) {
         HIP_TRY(h, hipMemcpyAsync(h->dC + h->L.oFG, F, sizeof(double) * nx * nx, hipMemcpyHostToDevice, st));
@@ -254,19 +243,15 @@ int lmpc_simulate_device(lmpc_handle *h, int64_t N, int T, int nx, int nr, int n
         double *cur = h->simTheta, *nxt = h->simTheta2;
         int rc = LMPC_OK;
         for (int k = 0; k < T && rc == LMPC_OK; k++) {
-            h->L.sim = SimFuse{h->simFG, nxt, flag_min, X_traj ? X_traj + (size_t)(k + 1) * N * nx : nullptr,
+            mode.sim = SimFuse{h->simFG, nxt, flag_min, X_traj ? X_traj + (size_t)(k + 1) * N * nx : nullptr,
                                nx, nu, nr, nuprev, k == 0 ? 1 : 0};
             const uint64_t *wm = (warm && k > 0) ? h->simAct : nullptr;
             // no input trajectory asked for: the kernels write neither u nor the per-step flags
-            rc = api_launch(h, N, cur, U_traj ? U_traj + (size_t)k * N * nu : nullptr, nullptr, nullptr,
+            rc = api_launch(h, mode, N, cur, U_traj ? U_traj + (size_t)k * N * nu : nullptr, nullptr, nullptr,
                         warm ? h->simAct : nullptr, wm, st);
             std::swap(cur, nxt);
         }
-        if (rc != LMPC_OK) return rc;
-        hipLaunchKernelGGL(unpack_theta_kernel, dim3(grid), dim3(256), 0, st, cur, x, nuprev > 0 ? uprev : nullptr, nx,
-                           nr, nuprev, (long long)N);
-        HIP_TRY(h, hipGetLastError());
-        return LMPC_OK;
+        return rc != LMPC_OK ? rc : unpack(cur);
     }
     // Wavefront path, warm: every scenario's final working set stays on the device WITH its factorisation, in its
     // order (2 x 64 + cap (cap - 1) / 2 reals and 320 ints per scenario: 17 KB at cap 64), so that a warm step
@@ -274,7 +259,7 @@ int lmpc_simulate_device(lmpc_handle *h, int64_t N, int T, int nx, int nr, int n
     // cleared between two calls (codegen/mpc_update_qp.c:44-54) -- instead of re-appending the rows of the mask one
     // by one.  Option "sim_keep_factor" 0 (or no memory for it): the mask-based warm start of the other paths.
     if (h->useWave && !h->avi && warm && !h->bnb && h->simKeep && T > 1) {
-        const int rck = ensure_keep(h, N, st);
+        const int rck = ensure_keep(h, N, st, &mode.keep);
         if (rck != LMPC_OK) return rck;
     }
     // Wavefront path with its screening pass in front: the plant step is fused into the three kernels of a step like
@@ -286,24 +271,20 @@ int lmpc_simulate_device(lmpc_handle *h, int64_t N, int T, int nx, int nr, int n
         HIP_TRY(h, hipMemcpyAsync(h->dC + h->L.oFG + nx * nx, G, sizeof(double) * nx * nu, hipMemcpyHostToDevice, st));
         int rc = LMPC_OK;
         for (int k = 0; k < T && rc == LMPC_OK; k++) {
-            h->L.sim = SimFuse{h->simFG, h->simTheta, flag_min, X_traj ? X_traj + (size_t)(k + 1) * N * nx : nullptr,
+            mode.sim = SimFuse{h->simFG, h->simTheta, flag_min, X_traj ? X_traj + (size_t)(k + 1) * N * nx : nullptr,
                                nx, nu, nr, nuprev, k == 0 ? 1 : 0};
-            h->waveSim = WaveSim{h->simFG, nullptr, nullptr, X_traj, flag_min, nx, nu, nr, nuprev, (long long)N, k};
+            mode.waveSim = WaveSim{h->simFG, nullptr, nullptr, X_traj, flag_min, nx, nu, nr, nuprev, (long long)N, k};
             const uint64_t *wm = (warm && k > 0) ? h->simAct : nullptr;
-            rc = api_launch(h, N, h->simTheta, U_traj ? U_traj + (size_t)k * N * nu : nullptr, nullptr, nullptr,
+            rc = api_launch(h, mode, N, h->simTheta, U_traj ? U_traj + (size_t)k * N * nu : nullptr, nullptr, nullptr,
                         warm ? h->simAct : nullptr, wm, st);
         }
-        if (rc != LMPC_OK) return rc;
-        hipLaunchKernelGGL(unpack_theta_kernel, dim3(grid), dim3(256), 0, st, h->simTheta, x, nuprev > 0 ? uprev : nullptr,
-                           nx, nr, nuprev, (long long)N);
-        HIP_TRY(h, hipGetLastError());
-        return LMPC_OK;
+        return rc != LMPC_OK ? rc : unpack(h->simTheta);
     }
     for (int k = 0; k < T; k++) {
         // warm start = previous step's final working set (reference codegen DAQP_WARMSTART,
         // codegen/mpc_update_qp.c:44-47); the first step is always cold
         const uint64_t *wm = (warm && k > 0) ? h->simAct : nullptr;
-        int rc = api_launch(h, N, h->simTheta, h->simU, h->simFlag, nullptr, warm ? h->simAct : nullptr, wm, st);
+        int rc = api_launch(h, mode, N, h->simTheta, h->simU, h->simFlag, nullptr, warm ? h->simAct : nullptr, wm, st);
         if (rc != LMPC_OK) return rc;
         const bool last = k == T - 1;
         hipLaunchKernelGGL(plant_theta_kernel<double>, dim3(grid), dim3(256), 0, st, h->simTheta, h->P.nth, nr, h->simU,
@@ -404,7 +385,7 @@ int lmpc_simulate_ref_device(lmpc_handle *h, int64_t N, int T, int nx, const lmp
         hipLaunchKernelGGL(form_parameter_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
                            h->simTheta, x, nx, br, none, uprev, nuprev, none, (long long)N);
         const uint64_t *wm = (warm && k > 0) ? h->simAct : nullptr;
-        int rc = api_launch(h, N, h->simTheta, h->simU, h->simFlag, nullptr, warm ? h->simAct : nullptr, wm, st);
+        int rc = api_launch(h, LoopMode{}, N, h->simTheta, h->simU, h->simFlag, nullptr, warm ? h->simAct : nullptr, wm, st);
         if (rc != LMPC_OK) return rc;
         dispatch_nx(nx, [&](auto NX) {
             hipLaunchKernelGGL(plant_kernel<decltype(NX)::value>, dim3(grid), dim3(256), 0, st, x, uprev, h->simU, h->simFlag, h->simFG, nx,
@@ -461,11 +442,11 @@ int lmpc_compute_control_device(lmpc_handle *h, int64_t N, double *control, cons
     // five arrays itself (GatherArgs) and hands the records of the problems that need iterations to the
     // iterating kernel through ccTheta -- no theta buffer is written or read for the others
     if (api_will_screen(h, N) && h->ccNph == 0 && h->ccFused) {
-        const HandleLoan loan(h);
-        h->L.gat = GatherArgs{state, reference, disturbance, control, affine_parameter, h->ccTheta,
+        LoopMode mode;
+        mode.gat = GatherArgs{state, reference, disturbance, control, affine_parameter, h->ccTheta,
                               h->ccNx, h->ccNr, h->ccNd, h->ccNup, h->ccNp, h->P.nout};
         const bool use_warm_g = warm && h->ccWarmN == N;
-        int rcg = api_launch(h, N, h->ccTheta, control, exitflag ? exitflag : h->ccFlag, nullptr, warm ? h->ccAct : nullptr,
+        int rcg = api_launch(h, mode, N, h->ccTheta, control, exitflag ? exitflag : h->ccFlag, nullptr, warm ? h->ccAct : nullptr,
                          use_warm_g ? h->ccAct : nullptr, st);
         if (rcg != LMPC_OK) return rcg;
         h->ccWarmN = warm ? N : -1;
@@ -481,7 +462,7 @@ int lmpc_compute_control_device(lmpc_handle *h, int64_t N, double *control, cons
     // DAQP_WARMSTART build (codegen/mpc_update_qp.c:44-47): the working sets the previous call ended
     // with are the next call's starting point; otherwise every call starts cold
     const bool use_warm = warm && h->ccWarmN == N && !h->bnb;
-    int rc = api_launch(h, N, h->ccTheta, control, exitflag ? exitflag : h->ccFlag, nullptr,
+    int rc = api_launch(h, LoopMode{}, N, h->ccTheta, control, exitflag ? exitflag : h->ccFlag, nullptr,
                     (warm && !h->bnb) ? h->ccAct : nullptr, use_warm ? h->ccAct : nullptr, st);
     if (rc != LMPC_OK) return rc;
     h->ccWarmN = (warm && !h->bnb) ? N : -1;

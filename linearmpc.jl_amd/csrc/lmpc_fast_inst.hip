@@ -67,7 +67,7 @@ static hipError_t fast_err_word(lmpc_handle *h, hipStream_t st) {
 }
 
 template <int NTHMAX, int NT, int N, bool GATHER>
-static int launch_fast_t(lmpc_handle *h, int64_t nprob, const double *theta, double *x, int32_t *flag, int32_t *iters,
+static int launch_fast_t(lmpc_handle *h, const PackLayout &L, int64_t nprob, const double *theta, double *x, int32_t *flag, int32_t *iters,
                          uint64_t *active, hipStream_t st) {
     // R tiles of 64 problems per workgroup: enough that a workgroup's queue fills a 64-problem claim several
     // times over, few enough that the grid is a couple of workgroups per CU (one resident round)
@@ -140,10 +140,10 @@ static int launch_fast_t(lmpc_handle *h, int64_t nprob, const double *theta, dou
     HIP_TRY(h, fast_err_word(h, st));
     const int spin = h->fastSpinLimit > 0 ? h->fastSpinLimit - 1 : kFastSpinLimit;
     if (stage)
-        hipLaunchKernelGGL(kernStaged, dim3(grid), dim3(256), lds, st, h->L, h->dC, theta, x, flag, (long long)nprob, Rq, nstr,
+        hipLaunchKernelGGL(kernStaged, dim3(grid), dim3(256), lds, st, L, h->dC, theta, x, flag, (long long)nprob, Rq, nstr,
                            h->dFastErr, spin, dk);
     else
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, h->L, h->dC, theta, x, flag, iters, active, (long long)nprob, Rq,
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, L, h->dC, theta, x, flag, iters, active, (long long)nprob, Rq,
                            nstr, h->dFastErr, spin, dk, Rs, Dcap, ctrNow, ctrNext);
     HIP_TRY(h, hipGetLastError());
     fast_record(h, GATHER ? 1 : 0, stage, Rq, nstr, dk, grid, 1, lds, D);
@@ -253,21 +253,23 @@ void fast_preload(lmpc_handle *h) {
     (void)hipGetLastError();
 }
 
-int launch_fast(lmpc_handle *h, int64_t nprob, const double *theta, double *x, int32_t *flag, int32_t *iters,
+int launch_fast(lmpc_handle *h, const LoopMode &mode, int64_t nprob, const double *theta, double *x, int32_t *flag, int32_t *iters,
                 uint64_t *active, hipStream_t st) {
-    const bool gather = h->L.gat.state != nullptr;        // generated-controller call: theta from the five arrays
+    const bool gather = mode.gat.state != nullptr;        // generated-controller call: theta from the five arrays
+    PackLayout tmp;
+    const PackLayout &L = pack_layout(h, mode, tmp);
 #define LMPC_FN(NM, NT)                                                                                               \
     switch (h->laneN) {                                                                                               \
-        case 2: return gather ? launch_fast_t<NM, NT, 2, true>(h, nprob, theta, x, flag, iters, active, st) : launch_fast_t<NM, NT, 2, false>(h, nprob, theta, x, flag, iters, active, st);    \
-        case 3: return gather ? launch_fast_t<NM, NT, 3, true>(h, nprob, theta, x, flag, iters, active, st) : launch_fast_t<NM, NT, 3, false>(h, nprob, theta, x, flag, iters, active, st);    \
-        case 4: return gather ? launch_fast_t<NM, NT, 4, true>(h, nprob, theta, x, flag, iters, active, st) : launch_fast_t<NM, NT, 4, false>(h, nprob, theta, x, flag, iters, active, st);    \
-        case 5: if constexpr (NT <= 8) return gather ? launch_fast_t<NM, NT, 5, true>(h, nprob, theta, x, flag, iters, active, st) : launch_fast_t<NM, NT, 5, false>(h, nprob, theta, x, flag, iters, active, st); break; \
+        case 2: return gather ? launch_fast_t<NM, NT, 2, true>(h, L, nprob, theta, x, flag, iters, active, st) : launch_fast_t<NM, NT, 2, false>(h, L, nprob, theta, x, flag, iters, active, st);    \
+        case 3: return gather ? launch_fast_t<NM, NT, 3, true>(h, L, nprob, theta, x, flag, iters, active, st) : launch_fast_t<NM, NT, 3, false>(h, L, nprob, theta, x, flag, iters, active, st);    \
+        case 4: return gather ? launch_fast_t<NM, NT, 4, true>(h, L, nprob, theta, x, flag, iters, active, st) : launch_fast_t<NM, NT, 4, false>(h, L, nprob, theta, x, flag, iters, active, st);    \
+        case 5: if constexpr (NT <= 8) return gather ? launch_fast_t<NM, NT, 5, true>(h, L, nprob, theta, x, flag, iters, active, st) : launch_fast_t<NM, NT, 5, false>(h, L, nprob, theta, x, flag, iters, active, st); break; \
         default: break;                                                                                               \
     }                                                                                                                 \
     break;
     switch (h->P.nth) {
 #ifdef LMPC_FAST_ONLY_PENDULUM
-        case 7: if (h->laneN == 5) return gather ? launch_fast_t<8, 7, 5, true>(h, nprob, theta, x, flag, iters, active, st) : launch_fast_t<8, 7, 5, false>(h, nprob, theta, x, flag, iters, active, st); break;
+        case 7: if (h->laneN == 5) return gather ? launch_fast_t<8, 7, 5, true>(h, L, nprob, theta, x, flag, iters, active, st) : launch_fast_t<8, 7, 5, false>(h, L, nprob, theta, x, flag, iters, active, st); break;
 #else
         case 1: LMPC_FN(8, 1)   case 2: LMPC_FN(8, 2)   case 3: LMPC_FN(8, 3)   case 4: LMPC_FN(8, 4)
         case 5: LMPC_FN(8, 5)   case 6: LMPC_FN(8, 6)   case 7: LMPC_FN(8, 7)   case 8: LMPC_FN(8, 8)

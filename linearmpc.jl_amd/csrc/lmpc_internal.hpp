@@ -151,7 +151,6 @@ struct lmpc_handle : lmpc_scratch {
     bool bnb = false;           // rows flagged BINARY: branch and bound in the wavefront kernel
     int waveCap = 0;            // tuning: wavefronts per CU for the wave kernel's grid (0 = 16)
     bool waveQueue = true;      // tuning: dynamic problem queue of the wave kernel (0 = static split)
-    lmpc::WaveSim waveSim{};    // scenario-asynchronous closed loop on the wavefront path (kstep == nullptr: off)
     int screenWave = 1;         // tuning: screening pass in front of the wavefront kernel where it applies ("screen_wave")
     bool screenPackOnly = false;   // the lane-style pack holds only what the screening pass reads (wave-only problem)
     DevBuf<int32_t> dQueue;
@@ -187,9 +186,7 @@ struct lmpc_handle : lmpc_scratch {
     // slow path for working sets beyond the 64 lanes (lmpc_big_kernel.hpp): the counters of its overflow lists
     int capFull = 0;            // n + 2 + #soft: the rows a working set of this problem can reach (one beyond the kernels' own n + 1 + #soft)
     DevBuf<int32_t> dOvfCount;
-    bool keepOn = false;        // closed loop on the wavefront path: working set + factor kept between two steps (dKeepR, dKeepI)
-    int simKeep = 1;
-    bool raWarm = false;        // the run-ahead loop in progress is a warm one
+    int simKeep = 1;            // closed loop on the wavefront path: working set + factor kept between two steps ("sim_keep_factor")
     int simRunAhead = 1;        // scenario-asynchronous loop on the wavefront path: consecutive steps of a scenario inside the kernel
     int nBinary = 0;            // rows flagged BINARY = the search's largest depth
     int bigPath = 1;            // tuning: 0 = leave such points at exit flag -7 ("big_path")
@@ -237,17 +234,9 @@ struct lmpc_handle : lmpc_scratch {
     DevBuf<float> dCwf;         // binary32 copy of the wave kernel's pack, built on the first f32 solve
     DevBuf<int32_t> dSw;
     int numCU = 256;
-    int asyncPhase = 0, asyncT = 0;     // scenario-asynchronous closed loop: which half `launch` runs (0 = off)
-    int32_t *asyncCntNow = nullptr, *asyncCntNext = nullptr;
-    int32_t *asyncListOut = nullptr;    // ... the list the last streaming pass wrote (the iterating half reads it)
-    const int32_t *asyncListIn = nullptr, *asyncCntIn = nullptr;   // ... the round before's list: the scenarios to continue
-    const double *asyncX = nullptr, *asyncR = nullptr, *asyncUp = nullptr;   // ... first pass: form theta from these
+    int simAsync = 1;           // tuning: scenario-asynchronous closed loop ("sim_async"; one round: lmpc::AsyncRound)
     int simSmall = 1;                   // ... the all-in-registers instantiation of sim_run_kernel where it applies
     int simBlind = 2;                   // ... rounds enqueued between two reads of the work-list counters
-    int asyncCap = 0;                   // ... steps a scenario may run ahead in this streaming pass
-    bool asyncResetPark = false;        // ... this pass consumes the parked list: clear its counters afterwards
-    long long asyncMaxIn = 0;           // ... its longest shard segment (sizes the grid)
-    int simAsync = 1;           // tuning: scenario-asynchronous closed loop ("sim_async")
     int ccFused = 1;            // tuning: lmpc_compute_control assembles theta inside the screening kernel ("cc_fused")
     int simFused = 1;           // tuning: plant step inside the lane / screening kernels (lmpc_set_option "sim_fused")
     // generated-controller entry point (lmpc_compute_control*): layout of theta
@@ -272,19 +261,21 @@ struct lmpc_handle : lmpc_scratch {
                                 // the tiers pass, and for large batches whichever of the two the handle has MEASURED faster
     // ... that measurement: one large call each way, timed by events that are read (without waiting) by later calls;
     // taken again every 512 calls.  Variant 0 = with the pass, 1 = without.
-    hipEvent_t qpAbEv[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-    bool qpAbPending[2] = {false, false};
-    int64_t qpAbN[2] = {0, 0};
-    double qpAbNsPer[2] = {-1.0, -1.0};      // measured nanoseconds per problem (-1: not measured yet)
-    double qpAbAcc[2] = {-1.0, -1.0};   // ... best sample of the current round of measurements, and how many it holds
-    int qpAbCnt[2] = {0, 0};
-    long long qpAbCalls = 0;
+    struct QpAb {
+        hipEvent_t ev[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};      // (kept by reset(): created once, destroyed with the handle)
+        bool pending[2] = {false, false};
+        int64_t n[2] = {0, 0};
+        double nsPer[2] = {-1.0, -1.0};     // measured nanoseconds per problem (-1: not measured yet)
+        double acc[2] = {-1.0, -1.0};       // ... best sample of the current round of measurements, and how many it holds
+        int cnt[2] = {0, 0};
+        long long calls = 0;
+        void reset() { calls = 0; nsPer[0] = nsPer[1] = -1.0; pending[0] = pending[1] = false; cnt[0] = cnt[1] = 0; }   // measure again
+    } qpAb;
     // four problems per wavefront (lmpc_row_kernel.hpp) in front of / instead of the wavefront kernel
     int rowKernel = -1;         // "row_kernel": -1 = where it applies (large cold batches), 0 = never, 1 = whenever an instantiation covers
     int rowBlocks = 0;          // tuning: workgroups per CU of its grid ("row_blocks", 0 = what LDS and registers allow)
     bool waveWarmed = false;    // lmpc_reserve has sent its one dummy problem through the wavefront kernel
-    bool preloadOnly = false;   // launch_wave in "load the code, launch nothing" mode (preload_code)
-    // profiling
+    // profiling: the user's switch (lmpc_profile and nothing else writes it; a launch ANDs it with LoopMode::prof)
     bool prof = false;
     std::vector<lmpc::EventTriple> events;
     std::vector<hipEvent_t> eventPool;   // recycled by lmpc_profile_read
@@ -306,17 +297,6 @@ int check_fast_err(lmpc_handle *h);
     } while (0)
 
 #define LMPC_TRY(call) do { const int rct__ = (call); if (rct__ != LMPC_OK) return rct__; } while (0)
-
-// a handle field set for a scope and put back on every way out of it
-template <class T>
-struct Restore {
-    T &ref;
-    const T old;
-    Restore(T &r, const T &tmp) : ref(r), old(r) { r = tmp; }
-    Restore(const Restore &) = delete;
-    Restore &operator=(const Restore &) = delete;
-    ~Restore() { ref = old; }
-};
 
 // Profiling bracket of one call: three pooled events on the launch stream -- begin, mid (between a front pass and the
 // iterating kernel), end.  end() hands a call that succeeded to h->events (lmpc_profile_read); on every other way out,
@@ -364,18 +344,58 @@ struct ProfBracket {
     }
 };
 
-// What one launch on the wavefront path (wavefront kernel or row kernel) is told by its caller, down the chain
-// launch_wave -> launch_wave_t -> launch_wave_inst -> launch_wave_cfg and launch_row* -> launch_row_shape.
+// One round of the scenario-asynchronous closed loop.  lmpc_simulate_device keeps it on its stack and points
+// LoopMode::round at it: the inputs of the round's two launches, and what the streaming half leaves for the iterating
+// half and for the next round.
+struct AsyncRound {
+    int phase = 1;                      // which half `launch` runs: 1 streaming (sim_run_kernel), 2 iterating
+    int T = 0;                          // steps of the run
+    int cap = 0;                        // steps a scenario may run ahead in this streaming pass
+    bool resetPark = false;             // this pass consumes the parked list: clear its counters afterwards
+    long long maxIn = 0;                // longest shard segment of listIn (sizes the grid)
+    const int32_t *listIn = nullptr, *cntIn = nullptr;               // the round before's list (nullptr: every scenario)
+    const double *x = nullptr, *r = nullptr, *up = nullptr;          // first pass only: form theta from these
+    int32_t *cntNow = nullptr, *cntNext = nullptr, *listOut = nullptr;   // OUT (launch_sim_run): counter sets, the list it wrote
+};
+
+// What a loop around the batched solve tells a launch: an argument of launch() and everything below it, filled by
+// lmpc_simulate_device (fused plant step, rounds, kept factors, no profiling) and lmpc_compute_control_device (the
+// gather).  A default-constructed one is a plain call: every other entry point passes that.
+struct LoopMode {
+    SimFuse sim{};                      // lane / screening kernels: plant step fused in (FG == nullptr: off)
+    GatherArgs gat{};                   // screening / one-launch kernel: theta from the controller's five arrays (state == nullptr: off)
+    WaveSim waveSim{};                  // wavefront kernel: plant step fused in, run-ahead (FG == nullptr: off)
+    bool keep = false;                  // wavefront kernel: working set + factor kept between two steps (dKeepR, dKeepI)
+    bool raWarm = false;                // the run-ahead loop in progress is a warm one
+    bool prof = true;                   // ANDed with the handle's switch (the rounds, the probe and lmpc_reserve: false)
+    AsyncRound *round = nullptr;        // scenario-asynchronous closed loop (nullptr: off)
+    bool plain() const { return sim.FG == nullptr && gat.state == nullptr && waveSim.FG == nullptr && !keep && round == nullptr; }
+};
+// the handle's layout as a lane / screening / sim_run / one-launch kernel of this call takes it: h->L itself without
+// fusion or gather (whose two structs it holds empty), else `tmp` = a copy of it with the mode's two filled in
+inline const PackLayout &pack_layout(const lmpc_handle *h, const LoopMode &mode, PackLayout &tmp) {
+    if (mode.sim.FG == nullptr && mode.gat.state == nullptr) return h->L;
+    tmp = h->L; tmp.sim = mode.sim; tmp.gat = mode.gat;
+    return tmp;
+}
+
+// What one launch on the wavefront path (wavefront kernel or row kernel) is told by its caller, the wavefront side of its
+// LoopMode included, down launch_wave -> launch_wave_t -> launch_wave_inst -> launch_wave_cfg and launch_row* -> launch_row_shape.
 struct WaveArgs {
     int pass = 0;               // 0: the only pass; 1: first of two (smaller capacity); 2: second (walks the first one's overflow list)
     WaveList list{};            // work list of a front pass (list == nullptr: the whole batch)
     int cap = 0;                // working-set capacity of this launch (the kernel's ldc = cap | 1)
     int level = -1, nwv = 0;    // preferred LDS staging level (-1 = automatic) and wavefronts per workgroup (0 = automatic)
+    WaveSim waveSim{};          // LoopMode::waveSim, keep, raWarm, prof
+    bool keep = false, raWarm = false, prof = true;
+    bool preload = false;       // setup: bring the kernel's code object onto the device, launch nothing (preload_code)
+    bool in_loop() const { return waveSim.FG != nullptr || keep; }
 };
 // ... of a launch at the handle's own capacity and tuning ("wave_cap", "wave_level", "wave_nwv")
-inline WaveArgs wave_args(const lmpc_handle *h, const WaveList &list = WaveList{}) {
+inline WaveArgs wave_args(const lmpc_handle *h, const LoopMode &mode, const WaveList &list = WaveList{}) {
     WaveArgs a;
     a.list = list; a.cap = h->W.cap; a.level = h->waveLevel; a.nwv = h->waveNwv;
+    a.waveSim = mode.waveSim; a.keep = mode.keep; a.raWarm = mode.raWarm; a.prof = mode.prof;
     return a;
 }
 
@@ -491,14 +511,14 @@ int launch_qp_tiers(lmpc_handle *h, int64_t nprob, const double *theta, double *
                     FrontLaunch *fl = nullptr);
 void avi_preload(lmpc_handle *h);
 int avi_reserve(lmpc_handle *h, int64_t nprob, hipStream_t st);
-int launch_fast(lmpc_handle *h, int64_t nprob, const double *theta, double *x, int32_t *flag, int32_t *iters,
+int launch_fast(lmpc_handle *h, const LoopMode &mode, int64_t nprob, const double *theta, double *x, int32_t *flag, int32_t *iters,
                 uint64_t *active, hipStream_t st);
 int launch_fast_multi(lmpc_handle *h, int nb, int64_t nprob, const double *const *theta, double *const *x, int32_t *const *flag,
                       hipStream_t st);
 
-// capacity of the first of two passes the wavefront kernel would run a batch of nprob problems at (0: one pass;
-// lmpc_wave_launch.hpp, compiled into the binary64 translation unit)
-int wave_first_pass_cap(lmpc_handle *h, int64_t nprob);
+// capacity of the first of two passes the wavefront kernel would run a batch of nprob problems at as `a` says (0: one
+// pass; lmpc_wave_launch.hpp, compiled into the binary64 translation unit)
+int wave_first_pass_cap(lmpc_handle *h, const WaveArgs &a, int64_t nprob);
 void wave_stat_read(const lmpc_handle *h, unsigned long long out[4]);
 int wave_reserve(lmpc_handle *h, int64_t nprob, hipStream_t st);
 // the wavefront path's lazily allocated scratch (defined once, next to wave_reserve; each does nothing where its
@@ -510,8 +530,8 @@ int wave_scratch_list1(lmpc_handle *h, int64_t nprob);
 int wave_scratch_slow(lmpc_handle *h, int64_t nprob);
 
 // lmpc_api.hip's launch policy and scratch for the second API unit (lmpc_api_loop.hip); that unit's code preload
-int api_launch(lmpc_handle *h, int64_t nprob, const double *theta, double *x, int32_t *flag, int32_t *iters, uint64_t *active,
-               const uint64_t *warm, hipStream_t st);
+int api_launch(lmpc_handle *h, const LoopMode &mode, int64_t nprob, const double *theta, double *x, int32_t *flag, int32_t *iters,
+               uint64_t *active, const uint64_t *warm, hipStream_t st);
 int api_ensure_sim(lmpc_handle *h, int64_t N);
 int api_ensure_f32(lmpc_handle *h);
 bool api_will_screen(const lmpc_handle *h, int64_t nprob);
@@ -526,7 +546,7 @@ void offset_free_preload();
 // four problems per wavefront (lmpc_row_inst.hip): capacity the batch would run at on that kernel (0: it does not take
 // the batch), and its launch as the only pass (a.pass 0) or the first of two (a.pass 1) of a wavefront-kernel call at
 // a.cap rows
-int row_pass_cap(lmpc_handle *h, int64_t nprob, size_t rs, bool warm, bool gram, bool bnb);
+int row_pass_cap(lmpc_handle *h, const WaveArgs &a, int64_t nprob, size_t rs, bool warm, bool gram, bool bnb);
 template <typename R>
 int launch_row(lmpc_handle *h, const WaveArgs &a, const R *dC, int64_t nprob, const R *theta, R *x, int32_t *flag,
                int32_t *iters, uint64_t *active, hipStream_t st);
@@ -535,7 +555,7 @@ extern template int launch_row<double>(lmpc_handle *, const WaveArgs &, const do
 extern template int launch_row<float>(lmpc_handle *, const WaveArgs &, const float *, int64_t, const float *, float *, int32_t *,
                                       int32_t *, uint64_t *, hipStream_t);
 // ... with branch and bound
-int row_bnb_pass_cap(lmpc_handle *h, int64_t nprob, size_t rs);
+int row_bnb_pass_cap(lmpc_handle *h, const WaveArgs &a, int64_t nprob, size_t rs);
 template <typename R>
 int launch_row_bnb(lmpc_handle *h, const WaveArgs &a, const R *dC, int64_t nprob, const R *theta, R *x, int32_t *flag,
                    int32_t *iters, uint64_t *active, hipStream_t st);

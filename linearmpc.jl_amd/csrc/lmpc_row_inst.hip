@@ -85,7 +85,7 @@ int launch_row_shape(lmpc_handle *h, const WaveArgs &a, const RowLaunch &rl, con
     auto kern = row_kernel<R, S, NS, MS, CAPP, BNB>;
     if (rl.lds > 48 * 1024)
         HIP_TRY(h, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rl.lds));
-    if (h->preloadOnly) {
+    if (a.preload) {
         hipFuncAttributes fa;
         HIP_TRY(h, hipFuncGetAttributes(&fa, (const void *)kern));
         return LMPC_OK;
@@ -168,9 +168,9 @@ int launch_row_shape(lmpc_handle *h, const WaveArgs &a, const RowLaunch &rl, con
 // Working-set capacity at which a batch of this handle would first run on the row kernel: the problem's own capacity
 // (one pass), a smaller one (first of two passes; the statistics of the handle's earlier launches must say that nearly
 // all working sets stay within it), or 0 = the row kernel does not take this batch.
-int row_pass_cap(lmpc_handle *h, int64_t nprob, size_t rs, bool warm, bool gram, bool bnb) {
+int row_pass_cap(lmpc_handle *h, const WaveArgs &a, int64_t nprob, size_t rs, bool warm, bool gram, bool bnb) {
     if (h->rowKernel == 0 || bnb || gram || warm || h->avi) return 0;
-    if (h->waveSim.FG != nullptr || h->keepOn || nprob >= (int64_t)0x3fffffff) return 0;
+    if (a.in_loop() || nprob >= (int64_t)0x3fffffff) return 0;
     // (small batches: the two-slot shape is ahead down to a single problem -- config 3's class 0.14 against 0.17 ms for one
     // solve, 0.53 against 0.63 ms for 512 --, the one-slot and ten-slot shapes only from a few thousand problems on)
     const bool twoSlot = h->P.n > 16 && h->P.n <= 32 && h->P.m <= 96;
@@ -211,9 +211,9 @@ int row_pass_cap(lmpc_handle *h, int64_t nprob, size_t rs, bool warm, bool gram,
 
 // ... for a handle with binary rows: the problem's own capacity if 16 rows hold it, else 48 rows as the first
 // of two passes when that leaves eight rows beyond the binaries (the wavefront kernel's rule, bnb_first_pass_cap)
-int row_bnb_pass_cap(lmpc_handle *h, int64_t nprob, size_t rs) {
+int row_bnb_pass_cap(lmpc_handle *h, const WaveArgs &a, int64_t nprob, size_t rs) {
     if (h->rowKernel == 0 || !h->bnb || h->avi || h->waveGram != 0) return 0;
-    if (h->waveSim.FG != nullptr || h->keepOn || nprob >= (int64_t)0x3fffffff) return 0;
+    if (a.in_loop() || nprob >= (int64_t)0x3fffffff) return 0;
     // (whatever the batch size: a search takes 110 trips here against 185 iterations + 41 node starts on the wavefront
     // kernel -- ONE search 0.98 against 1.50 ms in binary32, 1.18 against 1.84 ms in binary64)
     for (int j = 0; j < h->P.m; j++)

@@ -222,7 +222,7 @@ int scn_loop(lmpc_handle *h, const lmpc_scenario_sim *s, int64_t N, int T, doubl
 // final working set, the first step cold (as lmpc_simulate_ref_device)
 inline int scn_solve(lmpc_handle *h, const lmpc_scenario_sim *s, int64_t N, int k, hipStream_t st) {
     const uint64_t *wm = (s->warm && k > 0) ? h->simAct : nullptr;
-    return api_launch(h, N, h->simTheta, h->simU, h->simFlag, nullptr, s->warm ? h->simAct : nullptr, wm, st);
+    return api_launch(h, LoopMode{}, N, h->simTheta, h->simU, h->simFlag, nullptr, s->warm ? h->simAct : nullptr, wm, st);
 }
 
 // the host-pointer twins: the descriptor's trajectories and outputs and the caller's arrays staged on the device

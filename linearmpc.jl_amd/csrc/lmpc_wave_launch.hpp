@@ -131,7 +131,7 @@ inline int wave_first_pass_cap_impl(lmpc_handle *h, const WaveArgs &a, int64_t n
     // run-ahead (closed loop, consecutive steps of a scenario on the factor in LDS), warm: a step that outgrows a first
     // pass restarts from the factor of the step before it -- which the first pass then has to write out after every
     // step (the kept-state buffers of the step-synchronous loop); without them, one pass
-    if (h->waveSim.FG != nullptr && h->waveSim.T > 0 && h->raWarm && !h->keepOn) return 0;
+    if (a.waveSim.FG != nullptr && a.waveSim.T > 0 && a.raWarm && !a.keep) return 0;
     int c1 = 0;
     if (h->waveTwoPass > 0) c1 = h->waveCap1;
     else if (h->hStat && nprob >= 4096) {
@@ -195,7 +195,7 @@ int launch_wave_cfg(lmpc_handle *h, const WaveArgs &a, const WaveConfig &cfg, co
     auto kern = wave_kernel<R, MR, LDSC, BNB, PACKED, NU, GRAM, SIM>;
     if (cfg.lds > 48 * 1024)
         HIP_TRY(h, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cfg.lds));
-    if (h->preloadOnly) {                              // setup: the translation unit's code object on the device, no launch
+    if (a.preload) {                                   // setup: the translation unit's code object on the device, no launch
         hipFuncAttributes fa;
         HIP_TRY(h, hipFuncGetAttributes(&fa, (const void *)kern));
         return LMPC_OK;
@@ -274,7 +274,7 @@ int launch_wave_cfg(lmpc_handle *h, const WaveArgs &a, const WaveConfig &cfg, co
         HIP_TRY(h, h->dBnbI.reserve(needI));
         bnbR = h->dBnbR.template as<R>();
         bnbI = h->dBnbI.template as<int32_t>();
-    } else if (h->keepOn && sizeof(R) == 8) {
+    } else if (a.keep && sizeof(R) == 8) {
         // closed loop (lmpc_simulate_device, step-synchronous): every scenario's final working set and factor stay on
         // the device between two steps, indexed by scenario
         bnbR = h->dKeepR.template as<R>();
@@ -283,13 +283,13 @@ int launch_wave_cfg(lmpc_handle *h, const WaveArgs &a, const WaveConfig &cfg, co
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * cfg.nwv), cfg.lds, st, Wl, dC, h->dSw, theta, x, flag,
                        iters, active, warm, queue, qchunk, (long long)nprob, wl.list, wl.count, wl.count_next, wl.seg_cap,
                        pass == 1 ? h->dOvfList1.get() : (big ? h->dOvfList.get() : nullptr), pass == 1 ? p1Count : (big ? ovfCount : nullptr),
-                       h->waveSim, bnbR, bnbI, BNB ? h->nBinary : (pass == 1 ? 1 : 0), queueNext, p2Next, p1Next,
+                       a.waveSim, bnbR, bnbI, BNB ? h->nBinary : (pass == 1 ? 1 : 0), queueNext, p2Next, p1Next,
                        BNB ? nullptr : h->dStat.get(), BNB ? nullptr : h->dStatHost);
     h->waveCtrSet ^= 1;
     HIP_TRY(h, hipGetLastError());
     if (big) {
         hipLaunchKernelGGL(big_kernel<R>, dim3(kBigThreads / 64), dim3(64), 0, st, Wl, dC, h->dSw, theta, x, flag, iters,
-                           active, warm, h->dOvfList, ovfCount, h->dBigR.template as<R>(), h->dBigI, bigCap, h->waveSim);
+                           active, warm, h->dOvfList, ovfCount, h->dBigR.template as<R>(), h->dBigI, bigCap, a.waveSim);
         HIP_TRY(h, hipGetLastError());
     }
     // what was enqueued, for lmpc_wave_launch_info (include/lmpc_hip.h lists the words)
@@ -306,7 +306,7 @@ int launch_wave_inst(lmpc_handle *h, const WaveArgs &a, const R *dC, int64_t npr
                      int32_t *iters, uint64_t *active, const uint64_t *warm, hipStream_t st) {
     // (behind a front pass the call's events are that pass's; no front pass here: begin and mid back to back)
     ProfBracket prof(h, st);
-    LMPC_TRY(prof.begin(h->prof && a.list.list == nullptr && !h->preloadOnly));
+    LMPC_TRY(prof.begin(h->prof && a.prof && a.list.list == nullptr && !a.preload));
     LMPC_TRY(prof.mid());
     const int mr = wave_slots(h->P.m, BNB);
     if (BNB) warm = nullptr;                              // a B&B node takes its start from the search, not the caller
@@ -390,10 +390,10 @@ int launch_wave_inst(lmpc_handle *h, const WaveArgs &a, const R *dC, int64_t npr
     };
     auto row_cap = [&](int64_t np, bool warmStart) -> int {   // (0: the row kernel does not take the batch)
         if constexpr (GRAM) return 0;
-        else if constexpr (BNB) return row_bnb_pass_cap(h, np, sizeof(R));
-        else return row_pass_cap(h, np, sizeof(R), warmStart, GRAM, BNB);
+        else if constexpr (BNB) return row_bnb_pass_cap(h, a, np, sizeof(R));
+        else return row_pass_cap(h, a, np, sizeof(R), warmStart, GRAM, BNB);
     };
-    if (h->preloadOnly) {                                     // (the row kernel's code object too, where a large batch would take it)
+    if (a.preload) {                                          // (the row kernel's code object too, where a large batch would take it)
         const int rcap = row_cap((int64_t)1 << 20, false);
         if (rcap > 0) (void)row(at_cap(a, rcap));
         return dispatch(a);

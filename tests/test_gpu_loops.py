@@ -4,8 +4,8 @@ every state-size instantiation, lmpc_simulate_ref_device, lmpc_simulate in every
 wavefront path and at the gates between them, lmpc_simulate_f32, the NULL-able outputs of the C ABI, the generated
 controller's parameter formation, and the state a loop leaves on its handle.  Every comparison is np.array_equal.
 
-Left out: the error-return paths that the handle's loan guard also covers.  They are reached only when a HIP call fails
-inside a loop, and no test provokes that."""
+Left out: the error-return paths of the loops.  They are reached only when a HIP call fails inside a loop, and no test
+provokes that; a loop's state lives on its own stack (LoopMode), so they leave nothing on the handle either."""
 import ctypes
 import glob
 import os
