@@ -1240,6 +1240,83 @@ int lmpc_simulate_scenario_nonlinear(lmpc_handle *h, int64_t N, int T, const lmp
                                      const lmpc_plant_program *prog, const double *q, int q_shared, double *x, double *xhat,
                                      double *uprev, double *U_traj, double *X_traj, int32_t *flag_min);
 
+/*
+ * Differentiable solve: the derivative of the solution map x*(theta) per point, from the optimal active set the solve
+ * returned (`active`, (2m + 63) / 64 words: bit j the upper side of row j, bit m + j the lower side) and its exit flag.
+ * Neither theta nor x is needed.
+ *
+ * On a point with exit flag >= 1 and active rows A (the rows with either side bit set; a row with both bits counts
+ * once; both sides share the row of M and of Dth, so the side does not matter) the map is affine:
+ *     K_A = M_A M_A' + rho_soft S_A                            (S_A: 1 on the diagonal of SOFT rows)
+ *     J   = dx/dtheta = Xth + Rout M_A' K_A^-1 Dth_A           (nout x nth)
+ *     thbar = J' xbar = Xth' xbar + Dth_A' K_A^-1 (M_A Rout') xbar
+ * Where the active set is degenerate the map has a kink; the result is then the derivative of the affine piece the
+ * solver reported (the convention of OptNet and of differentiable MPC), not a subgradient chosen otherwise.
+ *
+ * Per-point status (status[N], may be NULL); every output row 0 .. N - 1 is always written:
+ *      1  done: the result
+ *      0  the point's exit flag is < 1: zeros
+ *     -1  a pivot of K_A is below the handle's zero_tol (dependent active rows): zeros
+ *     -7  |A| is beyond the 64 rows the kernels hold: zeros
+ * (a failed point has status 0 whatever its mask; -7 is decided before the factorisation).
+ *
+ * Arithmetic contract (binary64; every multiply-add an explicit fma, nothing else fused; restated in numpy in
+ * tests/sens_reference.py; the lane kernel, the wavefront kernel and the *_host functions give the same bits):
+ *   - derived pack, kept on the device next to the constant pack from the first call on: P = M Rout' (m x nout),
+ *     P[a][q] = the chain acc = fma(M[a][k], Rout[q][k], acc) from 0 over k = 0 .. n - 1; G the pack's packed triangle.
+ *   - rows of A in ascending row index a_0 < a_1 < ...; K[i][j] = G[a_i][a_j], plus ONE addition of rho_soft on the
+ *     diagonal entries of SOFT rows.
+ *   - K = L D L' without pivoting in that order, column by column: for j, c_p = L[j][p] * D[p] (p < j); for i >= j
+ *     v = K[i][j], then v = fma(-L[i][p], c_p, v) for p = 0 .. j - 1; D[j] = v (i = j; v < zero_tol: status -1),
+ *     rD[j] = 1 / D[j], L[i][j] = v * rD[j] (i > j).
+ *   - w_i = the chain acc = fma(P[a_i][q], xbar[q], acc) from 0 over q = 0 .. nout - 1.
+ *   - forward: z_i = w_i, then z_i = fma(-L[i][p], z_p, z_i) for p = 0 .. i - 1; diagonal: z_i = z_i * rD[i];
+ *     backward: y_i = z_i, then y_i = fma(-L[p][i], y_p, y_i) for p = |A| - 1 DOWN TO i + 1 (the order in which the
+ *     y_p become available to a column-by-column substitution).
+ *   - thbar[t] = one chain from 0: acc = fma(Xth[q][t], xbar[q], acc) over q ascending, then
+ *     acc = fma(Dth[a_i][t], y_i, acc) over i ascending.
+ *   - the Jacobian is the same computation on one factor with xbar = e_r for row r, the products with the exact zeros
+ *     and the one of e_r left out (w_i = P[a_i][r], the output chain starts at Xth[r][t]): row r of J equals the VJP of
+ *     e_r wherever values are compared (the sign of a zero may differ).
+ * The K form loses digits with cond(K_A) (SOFT-heavy sets); that loss is accepted and measured.
+ *
+ * Device calls: DEVICE pointers on the handle's GPU; they only enqueue on `stream` (one 4-byte memset, the lane kernel,
+ * and where a set can exceed its capacity the wavefront kernel over the work list, whose length is read on the device)
+ * and never wait.  The first call builds the derived pack (one blocking upload) and allocates the work list for its N;
+ * later calls of that size allocate nothing (lmpc_set_option "sens_reserve" 1 makes lmpc_reserve do both).  One
+ * stream at a time per handle, as for the solve.  xbar: N x nout; thbar: N x nth; J: N x nout x nth, row-major.
+ * Refused: BINARY rows, is_avi and proximal-point handles (LMPC_ERR_UNSUPPORTED); nth == 0 (LMPC_ERR_BADARG).
+ * Binary64 only.  Options: "sens_cap" 0 / 5 / 8 (capacity of the lane kernel's register factor; 0 = 5 where a set of
+ * the problem reaches at most 5 rows, else 8), "sens_force_list" 1 (every non-empty set goes to the wavefront kernel;
+ * results identical).
+ */
+int lmpc_solve_vjp_device(lmpc_handle *h, int64_t N, const uint64_t *active, const int32_t *exitflag, const double *xbar,
+                          double *thbar, int32_t *status, void *stream);
+int lmpc_solve_jacobian_device(lmpc_handle *h, int64_t N, const uint64_t *active, const int32_t *exitflag, double *J,
+                               int32_t *status, void *stream);
+/* HOST pointers; synchronous (as lmpc_solve_batch is to lmpc_solve_batch_device). */
+int lmpc_solve_vjp(lmpc_handle *h, int64_t N, const uint64_t *active, const int32_t *exitflag, const double *xbar, double *thbar,
+                   int32_t *status);
+int lmpc_solve_jacobian(lmpc_handle *h, int64_t N, const uint64_t *active, const int32_t *exitflag, double *J, int32_t *status);
+/* The kernels' arithmetic on the CPU, no GPU and no handle: the raw LDP pack (row-major, as lmpc_explicit_build_ldp
+ * takes it; du, dl, x0 are not read and may be NULL) and its settings (NULL = defaults; rho_soft and zero_tol are
+ * used, eps_prox > 0 is refused).  Same results bit for bit; lmpc_last_error(NULL) has the text of a refusal. */
+int lmpc_solve_vjp_host(int n, int m, int ms, int nth, int nout, const double *M, const double *du, const double *dl,
+                        const double *Dth, const double *Rout, const double *x0, const double *Xth, const int32_t *sense,
+                        const lmpc_settings *s, int is_avi, int64_t N, const uint64_t *active, const int32_t *exitflag,
+                        const double *xbar, double *thbar, int32_t *status);
+int lmpc_solve_jacobian_host(int n, int m, int ms, int nth, int nout, const double *M, const double *du, const double *dl,
+                             const double *Dth, const double *Rout, const double *x0, const double *Xth, const int32_t *sense,
+                             const lmpc_settings *s, int is_avi, int64_t N, const uint64_t *active, const int32_t *exitflag,
+                             double *J, int32_t *status);
+/* The handle's most recent derivative calls (at most four are kept), oldest first, LMPC_SENS_INFO_WORDS words each:
+ * number of the call in the handle's life (from 1), 1 for the Jacobian / 0 for the VJP, CAP of the sens_lane_kernel
+ * instantiation, the capacity it ran with (0: forced list pass), its grid, workgroup size, LDS bytes, what it staged in
+ * LDS (bit 0: the derived pack, bit 1: its results, stored as whole lines), 1 if sens_wave_kernel was enqueued behind it,
+ * that kernel's grid and LDS bytes, N.  Returns the number of records written (out holds max records). */
+#define LMPC_SENS_INFO_WORDS 12
+int lmpc_sens_launch_info(const lmpc_handle *h, int32_t *out, int max);
+
 #ifdef __cplusplus
 }
 #endif

@@ -46,6 +46,8 @@ SYMBOLS = (
     "lmpc_plant_program_check", "lmpc_plant_program_eval_host", "lmpc_plant_program_eval_device",
     "lmpc_simulate_scenario_nonlinear_device", "lmpc_simulate_scenario_nonlinear",
     "lmpc_noise_draw_host", "lmpc_noise_draw_device",
+    "lmpc_solve_vjp_device", "lmpc_solve_jacobian_device", "lmpc_solve_vjp", "lmpc_solve_jacobian",
+    "lmpc_solve_vjp_host", "lmpc_solve_jacobian_host", "lmpc_sens_launch_info",
 )
 
 
@@ -321,6 +323,21 @@ def lib():
         L.lmpc_noise_draw_host.restype = i32
         L.lmpc_noise_draw_device.argtypes = [vp, npn, ctypes.c_uint64, i32, i64, i64, ctypes.c_int32, i32, vp, vp]
         L.lmpc_noise_draw_device.restype = i32
+    if hasattr(L, "lmpc_solve_vjp_device"):   # (an older build selected with LMPC_HIP_LIB for an A/B lacks them)
+        L.lmpc_solve_vjp_device.argtypes = [vp, i64] + [vp] * 6
+        L.lmpc_solve_vjp_device.restype = i32
+        L.lmpc_solve_jacobian_device.argtypes = [vp, i64] + [vp] * 5
+        L.lmpc_solve_jacobian_device.restype = i32
+        L.lmpc_solve_vjp.argtypes = [vp, i64] + [vp] * 5
+        L.lmpc_solve_vjp.restype = i32
+        L.lmpc_solve_jacobian.argtypes = [vp, i64] + [vp] * 4
+        L.lmpc_solve_jacobian.restype = i32
+        L.lmpc_solve_vjp_host.argtypes = [i32] * 5 + [vp] * 9 + [i32, i64] + [vp] * 5
+        L.lmpc_solve_vjp_host.restype = i32
+        L.lmpc_solve_jacobian_host.argtypes = [i32] * 5 + [vp] * 9 + [i32, i64] + [vp] * 4
+        L.lmpc_solve_jacobian_host.restype = i32
+        L.lmpc_sens_launch_info.argtypes = [vp, vp, i32]
+        L.lmpc_sens_launch_info.restype = i32
     _lib = L
     return L
 

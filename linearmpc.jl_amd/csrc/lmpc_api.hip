@@ -1319,6 +1319,13 @@ int lmpc_set_option(lmpc_handle *h, const char *name, int value) {
         return ensure_snapshot(h, h->listCap);
     }
     if (std::strcmp(name, "avi_tiers") == 0) { h->aviTiers = value != 0; return LMPC_OK; }
+    if (std::strcmp(name, "sens_cap") == 0) {
+        if (value != 0 && value != 5 && value != 8) return fail(h, LMPC_ERR_BADARG, "lmpc_set_option: sens_cap must be 0, 5 or 8");
+        h->sensCap = value;
+        return LMPC_OK;
+    }
+    if (std::strcmp(name, "sens_force_list") == 0) { h->sensForceList = value != 0; return LMPC_OK; }
+    if (std::strcmp(name, "sens_reserve") == 0) { h->sensReserve = value != 0; return LMPC_OK; }
     if (std::strcmp(name, "avi_tiers_first") == 0) {
         h->aviTiersFirst = value < 0 ? -1 : (value > 3 ? 3 : value); h->aviTiersOcc[0] = 0; return LMPC_OK;
     }
@@ -1339,6 +1346,7 @@ int lmpc_reserve(lmpc_handle *h, int64_t N, void *stream) {
     if (N == 0) return LMPC_OK;
     LMPC_ENTER_DEVICE(h);
     hipStream_t st = (hipStream_t)stream;
+    if (h->sensReserve) LMPC_TRY(sens_reserve(h, N));
     if (h->avi) return avi_reserve(h, N, st);
     if (h->useWave) {
         if (wave_screens(h, N)) { const int rc = ensure_lists(h, N, st); if (rc != LMPC_OK) return rc; }

@@ -122,6 +122,11 @@ struct lmpc_scratch {
     // scenario loop (lmpc_scenario.hip): the run's constants (true plant, measurement, cost weights, constraint rows) and
     // its per-run scratch (observer state the caller does not keep, previous control of the cost's du term)
     DevBuf<double> scnC, scnScr;
+    // differentiable solve (lmpc_sens.hip): the derived pack [G | P = M Rout' | Dth | Xth | soft] built by the first call,
+    // the work list of the points left for the wavefront kernel and its counter
+    DevBuf<double> dSens;
+    DevBuf<int32_t> dSensList, dSensCnt;
+    int64_t sensListCap = 0;
 };
 
 struct lmpc_handle : lmpc_scratch {
@@ -229,6 +234,11 @@ struct lmpc_handle : lmpc_scratch {
     int aviChainGroups = 0;     // tuning: cap on the workgroups of the chain's three launches ("avi_chain_groups", 0 = none)
     // what launch_avi last enqueued (lmpc_avi_launch_info): a ring of the eight most recent launches of the chain
     lmpc::LaunchRing<LMPC_AVI_INFO_WORDS, LMPC_AVI_INFO_KEPT> aviRec;
+    // differentiable solve (lmpc_sens.hip): what sens_launch last enqueued (lmpc_sens_launch_info), the four most recent calls
+    lmpc::LaunchRing<LMPC_SENS_INFO_WORDS, 4> sensRec;
+    int sensCap = 0;            // tuning: CAP of the lane kernel, 5 or 8 ("sens_cap", 0 = by the rows a set of the problem reaches)
+    int sensForceList = 0;      // tuning: every point with a non-empty set goes to the wavefront kernel ("sens_force_list")
+    int sensReserve = 0;        // "sens_reserve": lmpc_reserve also allocates what the derivative calls need
     lmpc::WaveLayout W{};
     DevBuf<double> dCw;
     DevBuf<float> dCwf;         // binary32 copy of the wave kernel's pack, built on the first f32 solve
@@ -540,6 +550,10 @@ int api_wave_probe(lmpc_handle *h, const double *theta, int64_t nprob, hipStream
 int api_launch_wave_f32(lmpc_handle *h, const float *dC, int64_t nprob, const float *theta, float *x, int32_t *flag, int32_t *iters,
                         uint64_t *active, const uint64_t *warm, hipStream_t st);
 void loop_preload();
+// differentiable solve (lmpc_sens.hip): derived pack and work list for a batch of N; the same for lmpc_reserve (nothing
+// on a handle the derivative calls refuse)
+int sens_ensure(lmpc_handle *h, int64_t N);
+int sens_reserve(lmpc_handle *h, int64_t N);
 void scenario_preload();
 void offset_free_preload();
 

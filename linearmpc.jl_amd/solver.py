@@ -107,8 +107,69 @@ def _mask_dtypes():
     return (torch.int64, torch.uint64) if hasattr(torch, "uint64") else (torch.int64,)
 
 
+def sens_host(pack, active, exitflag, xbar=None, settings: Settings | None = None, is_avi=False):
+    """`lmpc_solve_vjp_host` (xbar given: returns (thbar (N, nth), status)) / `lmpc_solve_jacobian_host` (xbar None:
+    returns (J (N, nout, nth), status)): the derivative kernels' arithmetic on the CPU from a raw LDP pack, a dict as
+    `BatchedQP.ldp()` / `transform` return it.  Needs no GPU and no handle."""
+    n, m, ms, nth, nout = (int(pack[k]) for k in ("n", "m", "ms", "nth", "nout"))
+    arrs = [_f64(np.asarray(pack[k], float).reshape(s)) for k, s in
+            (("M", (m, n)), ("du", (m,)), ("dl", (m,)), ("Dth", (m, nth)), ("Rout", (nout, n)), ("x0", (nout,)),
+             ("Xth", (nout, nth)))]
+    sense = np.ascontiguousarray(pack["sense"], dtype=np.int32).reshape(m)
+    words = (2 * m + 63) // 64
+    act = np.ascontiguousarray(np.asarray(active, np.uint64).reshape(-1, words))
+    N = act.shape[0]
+    ef = np.ascontiguousarray(np.asarray(exitflag, np.int32).reshape(N))
+    status = np.zeros(N, np.int32)
+    sp = ctypes.cast(ctypes.pointer(settings), _vp) if settings is not None else None
+    head = (n, m, ms, nth, nout, *[_ptr(a) for a in arrs], _ptr(sense), sp, int(bool(is_avi)), N, _ptr(act), _ptr(ef))
+    if xbar is None:
+        out = np.zeros((N, nout, nth))
+        check(lib().lmpc_solve_jacobian_host(*head, _ptr(out), _ptr(status)))
+    else:
+        xb = _f64(np.asarray(xbar, float).reshape(N, nout))
+        out = np.zeros((N, nth))
+        check(lib().lmpc_solve_vjp_host(*head, _ptr(xb), _ptr(out), _ptr(status)))
+    return out, status
+
+
+_AUTOGRAD_FN = None
+
+
+def _autograd_fn():
+    """The torch.autograd.Function of `BatchedQP.solve_autograd` (made on first use: importing the package needs no torch)."""
+    global _AUTOGRAD_FN
+    if _AUTOGRAD_FN is not None:
+        return _AUTOGRAD_FN
+    import torch
+
+    class SolveFunction(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, theta, qp):
+            th = theta.detach().contiguous()
+            active = torch.empty((th.shape[0], qp.words), dtype=torch.int64, device=th.device)
+            x, ef = qp.solve_device(th, active=active)
+            ctx.qp = qp
+            ctx.sens_status = None
+            ctx.save_for_backward(active, ef)
+            ctx.mark_non_differentiable(ef)
+            return x, ef
+
+        @staticmethod
+        def backward(ctx, xbar, _efbar):
+            active, ef = ctx.saved_tensors
+            thbar, status = ctx.qp.solve_vjp_device(active, ef, xbar.contiguous())
+            ctx.sens_status = ctx.qp.last_sens_status = status
+            return thbar, None
+
+    _AUTOGRAD_FN = SolveFunction
+    return SolveFunction
+
+
 class BatchedQP:
     """One condensed-MPC QP structure resident on one GPU, solved for batches of theta."""
+
+    last_sens_status = None     # status tensor of the most recent backward of `solve_autograd`
 
     def __init__(self, handle, device):
         self._h = handle
@@ -1179,6 +1240,94 @@ class BatchedQP:
         f = first[:R].cpu().numpy()
         order = np.lexsort((f, -c))
         return m[order], c[order], f[order]
+
+    # ------------------------------------------------------------------ differentiable solve
+    SENS_LAUNCH_FIELDS = ("seq", "jac", "CAP", "cap", "grid", "block", "lds", "staged", "list_pass", "wave_grid", "wave_lds",
+                          "nprob")
+    SENS_DONE, SENS_FAILED_POINT, SENS_SINGULAR, SENS_TOO_MANY = 1, 0, -1, -7
+
+    def sens_launch_info(self, since=0):
+        """The handle's most recent derivative calls (lmpc_sens_launch_info; at most four are kept), oldest first: one
+        dict per call with jac (1 Jacobian, 0 VJP), the template argument CAP of the sens_lane_kernel instantiation, the
+        capacity it ran with (0: forced list pass), grid, block, lds, staged (bit 0: the derived pack in LDS, bit 1: the
+        results leave through LDS as whole lines), list_pass (1: sens_wave_kernel was enqueued
+        behind it), that kernel's grid and lds, nprob.  "seq" and `since` as in wave_launch_info."""
+        W = len(self.SENS_LAUNCH_FIELDS)
+        out = (ctypes.c_int32 * (4 * W))()
+        k = lib().lmpc_sens_launch_info(self._h, out, 4)
+        if k < 0:
+            check(k, self._h)
+        recs = [dict(zip(self.SENS_LAUNCH_FIELDS, (int(v) for v in out[q * W:(q + 1) * W]))) for q in range(k)]
+        return [r for r in recs if r["seq"] > since]
+
+    def _sens_device_args(self, active, exitflag, status):
+        import torch
+        if active is None or active.dtype not in _mask_dtypes() or active.dim() != 2 or active.shape[1] != self.words:
+            raise ValueError(f"active must be a 64-bit integer CUDA tensor of shape (N, {self.words})")
+        N = int(active.shape[0])
+        dev = active.device
+        if status is None:
+            status = torch.empty(N, dtype=torch.int32, device=dev)
+        return (N, dev, _dev_arg(active, "active", active.dtype, N * self.words, self.device, False),
+                _dev_arg(exitflag, "exitflag", torch.int32, N, self.device, False), status,
+                _dev_arg(status, "status", torch.int32, N, self.device, False))
+
+    def solve_vjp_device(self, active, exitflag, xbar, thbar=None, status=None, stream=None):
+        """`lmpc_solve_vjp_device`: thbar = (dx*/dtheta)' xbar per point from the solve's `active` masks and exit flags
+        (CUDA tensors; xbar (N, nout) float64).  Enqueued on `stream` (default: torch's current stream), not
+        synchronised.  Returns (thbar (N, nth), status (N,) int32: 1 done, 0 failed point, -1 singular, -7 beyond 64 rows)."""
+        import torch
+        N, dev, pa, pf, status, ps = self._sens_device_args(active, exitflag, status)
+        if thbar is None:
+            thbar = torch.empty((N, self.nth), dtype=torch.float64, device=dev)
+        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        check(lib().lmpc_solve_vjp_device(
+            self._h, N, pa, pf, _dev_arg(xbar, "xbar", torch.float64, N * self.nout, self.device, False),
+            _dev_arg(thbar, "thbar", torch.float64, N * self.nth, self.device, False), ps, _vp(st)), self._h)
+        return thbar, status
+
+    def solve_jacobian_device(self, active, exitflag, J=None, status=None, stream=None):
+        """`lmpc_solve_jacobian_device`: J = dx*/dtheta per point, (N, nout, nth); arguments and status as
+        `solve_vjp_device`."""
+        import torch
+        N, dev, pa, pf, status, ps = self._sens_device_args(active, exitflag, status)
+        if J is None:
+            J = torch.empty((N, self.nout, self.nth), dtype=torch.float64, device=dev)
+        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        check(lib().lmpc_solve_jacobian_device(
+            self._h, N, pa, pf, _dev_arg(J, "J", torch.float64, N * self.nout * self.nth, self.device, False), ps, _vp(st)),
+            self._h)
+        return J, status
+
+    def solve_vjp(self, active, exitflag, xbar):
+        """Host arrays in and out (`lmpc_solve_vjp`; synchronous): (thbar, status)."""
+        act = np.ascontiguousarray(np.asarray(active, np.uint64).reshape(-1, self.words))
+        N = act.shape[0]
+        ef = np.ascontiguousarray(np.asarray(exitflag, np.int32).reshape(N))
+        xb = _f64(np.asarray(xbar, float).reshape(N, self.nout))
+        out, status = np.zeros((N, self.nth)), np.zeros(N, np.int32)
+        check(lib().lmpc_solve_vjp(self._h, N, _ptr(act), _ptr(ef), _ptr(xb), _ptr(out), _ptr(status)), self._h)
+        return out, status
+
+    def solve_jacobian(self, active, exitflag):
+        """Host arrays in and out (`lmpc_solve_jacobian`; synchronous): (J (N, nout, nth), status)."""
+        act = np.ascontiguousarray(np.asarray(active, np.uint64).reshape(-1, self.words))
+        N = act.shape[0]
+        ef = np.ascontiguousarray(np.asarray(exitflag, np.int32).reshape(N))
+        out, status = np.zeros((N, self.nout, self.nth)), np.zeros(N, np.int32)
+        check(lib().lmpc_solve_jacobian(self._h, N, _ptr(act), _ptr(ef), _ptr(out), _ptr(status)), self._h)
+        return out, status
+
+    def solve_autograd(self, theta):
+        """The batched solve inside a torch graph: returns (x, exitflag) with x = x*(theta) carrying the gradient
+        (forward `solve_device` with the active sets kept, backward ONE `solve_vjp_device` on the current torch stream)
+        and exitflag marked non-differentiable.  The status of the most recent backward is `x.grad_fn.sens_status`
+        (an int32 CUDA tensor, None before the backward).  With a theta that does not require grad this is
+        `solve_device` and nothing else: no masks are written or kept."""
+        import torch
+        if not (theta.requires_grad and torch.is_grad_enabled()):
+            return self.solve_device(theta.detach())
+        return _autograd_fn().apply(theta, self)
 
     def check(self):
         """`lmpc_check`: wait for the handle's GPU, then raise if a kernel reported an internal failure
