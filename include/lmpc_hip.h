@@ -1317,6 +1317,92 @@ int lmpc_solve_jacobian_host(int n, int m, int ms, int nth, int nout, const doub
 #define LMPC_SENS_INFO_WORDS 12
 int lmpc_sens_launch_info(const lmpc_handle *h, int32_t *out, int max);
 
+/*
+ * Scenario loop adjoint: the gradient of a run of lmpc_simulate_scenario_device with respect to its initial values and
+ * its r / d / p trajectories.  Once a step's active set is known the step is affine in its inputs, so the adjoint of a
+ * run is a backward sweep over the steps: one VJP of the differentiable solve per step (above) and one transposed glue
+ * step.  A run is recorded by the TAPED forward call and differentiated by lmpc_scenario_vjp*, which reads only the tape
+ * and the constants -- not theta, x or u.
+ *
+ * lmpc_simulate_scenario_taped_device: lmpc_simulate_scenario_device (the same PRE / POST kernels, the same loop, every
+ * output the same bits) whose step k writes its solve's final working set and exit flags into slice k of the tape
+ * (DEVICE arrays of the caller, step-major: active T x N x lmpc_active_words(h), flag T x N); with s->warm step k starts
+ * from slice k - 1.  lmpc_simulate_scenario_taped: HOST arrays throughout, synchronous.
+ *
+ * The fields of lmpc_scenario_grad -- DEVICE arrays for lmpc_scenario_vjp_device, HOST arrays for the other two:
+ *   Xbar       in   (T+1) x N x nx   cotangent of X_traj, NULL = zeros        Ubar  in  T x N x nu  cotangent of U_traj
+ *   x0bar      out  N x nx           xhat0bar  out  N x nx: non-NULL exactly when the forward run was given an xhat
+ *   uprev0bar  out  N x nuprev
+ *   rbar, dbar, pbar  out, each optional: max(r.T, 1) x N x r.w (d, p alike; a block with T < 1 counts as one column, as
+ *              in the forward), STEP-major -- column c of the trajectory is slice c -- and always per scenario, also for
+ *              a shared source block (stride 0: the caller sums over scenarios)
+ *   status_min out  N int32, optional: the smallest per-step VJP status; 1 = every step was differentiated (T = 0: 1)
+ * The call zeroes rbar / dbar / pbar first and writes every other output.  The blocks' src and k0, the noise block, the
+ * output trajectories and the cost of the descriptor are not read.
+ *
+ * State carried from step k + 1 to step k, per scenario: alpha = d/dx_{k+1} (nx), beta = d/d(predicted xhat_{k+1}) (nx,
+ * observer only), gamma = d/duprev_{k+1} (nuprev).  At k = T: alpha = Xbar[T], beta = gamma = 0.  With the TRUE plant's
+ * rows [f, F, G, Gd] and [h, C, Dd] and the handle's observer rows [f^, F^, G^, Gd^], [h^, C^, Dd^], Kt, step k is
+ * (binary64; every sum ONE chain of explicit fmas in index order, every "+" below one addition, nothing else fused):
+ *   1. ubar_l = Ubar[k][l]; fma(G[a][l], alpha_a, .) over a; observer: fma(G^[a][l], beta_a, .) over a; l < nuprev:
+ *      + gamma_l.
+ *   2. thbar = lmpc_solve_vjp's arithmetic on tape slice k with xbar = ubar.  A step whose status is not 1 (exit flag
+ *      < 1, dependent rows, more than 64 rows) gives thbar = 0: its control is treated as a constant, and status_min
+ *      says so.
+ *   3. xi_c = thbar[c] (c < nx); observer: fma(F^[a][c], beta_a, .) over a, then eta_j = fma(Kt[j][c], xi_c, .) over c
+ *      from 0.
+ *   4. alpha'_c = Xbar[k][c]; fma(F[a][c], alpha_a, .) over a; without observer + xi_c; with observer
+ *      fma(C[j][c], eta_j, .) over j, and beta'_c = xi_c; fma(-C^[j][c], eta_j, .) over j.
+ *   5. delta_q = from 0: fma(Gd[a][q], alpha_a, .) over a; observer: fma(Gd^[a][q], beta_a, .) over a,
+ *      fma(Dd[j][q], eta_j, .) over j, fma(-Dd^[j][q], eta_j, .) over j.  dbar[column the POST kernel read d_k from] +=
+ *      delta_q (alpha, beta: the carried ones, not the primed).
+ *   6. the entries of thbar behind the state, in theta's order r-block, d-block, uprev, p-block: each r / d / p entry is
+ *      added once into the gradient column the forward read it from (the preview's k + 1 offset of r and the hold of the
+ *      last column are the forward's own rule, one function serves both); gamma' = the uprev entries.
+ * After step 0: x0bar = alpha, + beta where an observer ran from xhat == NULL (it started at x); xhat0bar = beta
+ * otherwise; uprev0bar = gamma.  Restated in numpy in tests/scenario_adjoint_reference.py; scenario_adjoint_kernel and
+ * lmpc_scenario_vjp_host run one body and give the same bits.
+ *
+ * lmpc_scenario_vjp_device enqueues on `stream` and never waits: T + 1 launches of scenario_adjoint_kernel (launch k
+ * finishes step k + 1 and forms ubar of step k) with the launches of lmpc_solve_vjp_device between them.  Its scratch
+ * (alpha, beta, gamma, ubar, thbar, the step's status) is one group of the handle, allocated by the first call of a
+ * size and released by lmpc_release_scratch.  lmpc_scenario_vjp: HOST arrays, synchronous.  lmpc_scenario_vjp_host: the
+ * same arithmetic on the CPU, no GPU and no handle, from the raw LDP pack and settings as lmpc_solve_vjp_host takes them
+ * plus the observer's arrays (NULL without use_observer).
+ * Refused: what lmpc_solve_vjp refuses -- BINARY rows, is_avi and proximal-point handles (LMPC_ERR_UNSUPPORTED), nth == 0
+ * (LMPC_ERR_BADARG) -- and a descriptor lmpc_scenario_check refuses.  Binary64 only; the offset-free, uncertain, nonlinear
+ * and explicit loops have no adjoint.  Not covered: gradients with respect to the noise block and the plant's matrices,
+ * cotangents of Y_traj / Xhat_traj.
+ */
+typedef struct lmpc_scenario_tape {
+    uint64_t *active;                    /* T x N x lmpc_active_words(h) */
+    int32_t *flag;                       /* T x N                        */
+} lmpc_scenario_tape;
+typedef struct lmpc_scenario_grad {
+    const double *Xbar, *Ubar;
+    double *x0bar, *xhat0bar, *uprev0bar, *rbar, *dbar, *pbar;
+    int32_t *status_min;
+} lmpc_scenario_grad;
+int lmpc_simulate_scenario_taped_device(lmpc_handle *h, int64_t N, int T, const lmpc_scenario_sim *s, double *x, double *xhat,
+                                        double *uprev, double *U_traj, double *X_traj, int32_t *flag_min,
+                                        const lmpc_scenario_tape *tape, void *stream);
+int lmpc_simulate_scenario_taped(lmpc_handle *h, int64_t N, int T, const lmpc_scenario_sim *s, double *x, double *xhat,
+                                 double *uprev, double *U_traj, double *X_traj, int32_t *flag_min, const lmpc_scenario_tape *tape);
+int lmpc_scenario_vjp_device(lmpc_handle *h, int64_t N, int T, const lmpc_scenario_sim *s, const lmpc_scenario_tape *tape,
+                             const lmpc_scenario_grad *g, void *stream);
+int lmpc_scenario_vjp(lmpc_handle *h, int64_t N, int T, const lmpc_scenario_sim *s, const lmpc_scenario_tape *tape,
+                      const lmpc_scenario_grad *g);
+int lmpc_scenario_vjp_host(int n, int m, int ms, int nth, int nout, const double *M, const double *du, const double *dl,
+                           const double *Dth, const double *Rout, const double *x0, const double *Xth, const int32_t *sense,
+                           const lmpc_settings *settings, int is_avi, const lmpc_observer *observer, int64_t N, int T,
+                           const lmpc_scenario_sim *s, const lmpc_scenario_tape *tape, const lmpc_scenario_grad *g);
+/* The handle's most recent backward sweeps (at most four are kept), oldest first, LMPC_SCENARIO_ADJOINT_INFO_WORDS words
+ * each: number of the call in the handle's life (from 1), NX of the scenario_adjoint_kernel instantiation (0: run-time
+ * nx), its grid, LDS bytes, T, N, 1 if the VJP's pass over its work list was enqueued, entries of a theta-bar record
+ * staged at a time.  Returns the number of records written (out holds max records). */
+#define LMPC_SCENARIO_ADJOINT_INFO_WORDS 8
+int lmpc_scenario_adjoint_launch_info(const lmpc_handle *h, int32_t *out, int max);
+
 #ifdef __cplusplus
 }
 #endif

@@ -48,6 +48,8 @@ SYMBOLS = (
     "lmpc_noise_draw_host", "lmpc_noise_draw_device",
     "lmpc_solve_vjp_device", "lmpc_solve_jacobian_device", "lmpc_solve_vjp", "lmpc_solve_jacobian",
     "lmpc_solve_vjp_host", "lmpc_solve_jacobian_host", "lmpc_sens_launch_info",
+    "lmpc_simulate_scenario_taped_device", "lmpc_simulate_scenario_taped", "lmpc_scenario_vjp_device", "lmpc_scenario_vjp",
+    "lmpc_scenario_vjp_host", "lmpc_scenario_adjoint_launch_info",
 )
 
 
@@ -102,6 +104,17 @@ class ScenarioSim(ctypes.Structure):
                 ("Y_traj", ctypes.c_void_p), ("Ym_traj", ctypes.c_void_p), ("Xhat_traj", ctypes.c_void_p),
                 ("D_traj", ctypes.c_void_p), ("cost", ctypes.POINTER(SimCost)),
                 ("cost_out", ctypes.c_void_p), ("violation_out", ctypes.c_void_p)]
+
+
+class ScenarioTape(ctypes.Structure):
+    """`lmpc_scenario_tape`: every step's final working set and exit flags of a taped scenario run, step-major."""
+    _fields_ = [("active", ctypes.c_void_p), ("flag", ctypes.c_void_p)]
+
+
+class ScenarioGrad(ctypes.Structure):
+    """`lmpc_scenario_grad`: cotangents in, gradients out of `lmpc_scenario_vjp*`."""
+    _fields_ = [(k, ctypes.c_void_p) for k in ("Xbar", "Ubar", "x0bar", "xhat0bar", "uprev0bar", "rbar", "dbar", "pbar",
+                                               "status_min")]
 
 
 class OffsetFree(ctypes.Structure):
@@ -338,6 +351,20 @@ def lib():
         L.lmpc_solve_jacobian_host.restype = i32
         L.lmpc_sens_launch_info.argtypes = [vp, vp, i32]
         L.lmpc_sens_launch_info.restype = i32
+    if hasattr(L, "lmpc_scenario_vjp_device"):   # (an older build selected with LMPC_HIP_LIB for an A/B lacks them)
+        tp, gp = ctypes.POINTER(ScenarioTape), ctypes.POINTER(ScenarioGrad)
+        L.lmpc_simulate_scenario_taped_device.argtypes = [vp, i64, i32, sp] + [vp] * 6 + [tp, vp]
+        L.lmpc_simulate_scenario_taped_device.restype = i32
+        L.lmpc_simulate_scenario_taped.argtypes = [vp, i64, i32, sp] + [vp] * 6 + [tp]
+        L.lmpc_simulate_scenario_taped.restype = i32
+        L.lmpc_scenario_vjp_device.argtypes = [vp, i64, i32, sp, tp, gp, vp]
+        L.lmpc_scenario_vjp_device.restype = i32
+        L.lmpc_scenario_vjp.argtypes = [vp, i64, i32, sp, tp, gp]
+        L.lmpc_scenario_vjp.restype = i32
+        L.lmpc_scenario_vjp_host.argtypes = [i32] * 5 + [vp] * 9 + [i32, ctypes.POINTER(Observer), i64, i32, sp, tp, gp]
+        L.lmpc_scenario_vjp_host.restype = i32
+        L.lmpc_scenario_adjoint_launch_info.argtypes = [vp, vp, i32]
+        L.lmpc_scenario_adjoint_launch_info.restype = i32
     _lib = L
     return L
 

@@ -127,6 +127,13 @@ struct lmpc_scratch {
     DevBuf<double> dSens;
     DevBuf<int32_t> dSensList, dSensCnt;
     int64_t sensListCap = 0;
+    // scenario loop adjoint (lmpc_scenario_adjoint.hip): per scenario [alpha | beta | gamma | ubar | theta-bar] of the
+    // backward sweep and the step's VJP status; adjCap: scenarios the status holds, adjDoubles: doubles the state holds
+    // (the doubles per scenario vary with the descriptor; both only grow)
+    DevBuf<double> adjState;
+    DevBuf<int32_t> adjStatus;
+    int64_t adjCap = 0;
+    size_t adjDoubles = 0;
 };
 
 struct lmpc_handle : lmpc_scratch {
@@ -236,6 +243,8 @@ struct lmpc_handle : lmpc_scratch {
     lmpc::LaunchRing<LMPC_AVI_INFO_WORDS, LMPC_AVI_INFO_KEPT> aviRec;
     // differentiable solve (lmpc_sens.hip): what sens_launch last enqueued (lmpc_sens_launch_info), the four most recent calls
     lmpc::LaunchRing<LMPC_SENS_INFO_WORDS, 4> sensRec;
+    // ... and the backward sweeps of the scenario loop (lmpc_scenario_adjoint_launch_info), the four most recent calls
+    lmpc::LaunchRing<LMPC_SCENARIO_ADJOINT_INFO_WORDS, 4> adjRec;
     int sensCap = 0;            // tuning: CAP of the lane kernel, 5 or 8 ("sens_cap", 0 = by the rows a set of the problem reaches)
     int sensForceList = 0;      // tuning: every point with a non-empty set goes to the wavefront kernel ("sens_force_list")
     int sensReserve = 0;        // "sens_reserve": lmpc_reserve also allocates what the derivative calls need
@@ -554,6 +563,12 @@ void loop_preload();
 // on a handle the derivative calls refuse)
 int sens_ensure(lmpc_handle *h, int64_t N);
 int sens_reserve(lmpc_handle *h, int64_t N);
+// ... what lmpc_solve_vjp* refuses of a handle (LMPC_OK, or the code with its text set), and the launches of
+// lmpc_solve_vjp_device for a caller that has passed it (the scenario adjoint, once per step); *list_pass: whether the
+// wavefront kernel's pass over the work list was enqueued
+int sens_refusal(lmpc_handle *h, const char *who);
+int sens_vjp_enqueue(lmpc_handle *h, int64_t N, const uint64_t *active, const int32_t *flag, const double *xbar, double *thbar,
+                     int32_t *status, hipStream_t st, int *list_pass);
 void scenario_preload();
 void offset_free_preload();
 

@@ -27,8 +27,10 @@ std::string call_problem(lmpc_handle *h, int64_t N, int T, const lmpc_scenario_s
 }
 
 // the run itself, on device arrays, once the call has passed its refusals
+// tape != nullptr: step k's solve writes its final working set and exit flags into slice k of the tape, a warm step
+// reads slice k - 1, and the POST kernel takes the step's flags from the tape
 int run(lmpc_handle *h, int64_t N, int T, const lmpc_scenario_sim *s, double *x, double *xhat, double *uprev, double *U_traj,
-        double *X_traj, int32_t *flag_min, hipStream_t st) {
+        double *X_traj, int32_t *flag_min, const lmpc_scenario_tape *tape, hipStream_t st) {
     { const int rce = api_ensure_sim(h, N); if (rce != LMPC_OK) return rce; }
     const int nx = s->nx;
     std::vector<double> hostC;
@@ -39,13 +41,20 @@ int run(lmpc_handle *h, int64_t N, int T, const lmpc_scenario_sim *s, double *x,
       if (rcb != LMPC_OK) return rcb; }
     const bool wantCost = scn_want_cost(s);
     const unsigned grid = (unsigned)((N + 255) / 256);
+    const size_t slice = (size_t)N * (size_t)h->P.words();
     return scn_loop(h, s, N, T, U_traj, X_traj, A, B,
-        [&](int) {
+        [&](int k) {
+            if (tape) B.flag = tape->flag + (size_t)k * N;
             dispatch_nx(nx, [&](auto NX) {
                 hipLaunchKernelGGL(scenario_pre_kernel<decltype(NX)::value>, dim3(grid), dim3(256), sizeof(double) * 256 * (size_t)nx, st, A, K);
             });
         },
-        [&](int k) { return scn_solve(h, s, N, k, st); },
+        [&](int k) {
+            if (!tape) return scn_solve(h, s, N, k, st);
+            uint64_t *act = tape->active + (size_t)k * slice;
+            return api_launch(h, LoopMode{}, N, h->simTheta, h->simU, tape->flag + (size_t)k * N, nullptr, act,
+                              (s->warm && k > 0) ? act - slice : nullptr, st);
+        },
         [&](int) {
             dispatch_nx(nx, [&](auto NX) {
                 if (wantCost) hipLaunchKernelGGL((scenario_post_kernel<decltype(NX)::value, true>), dim3(grid), dim3(256), 0, st, B, K);
@@ -81,7 +90,7 @@ int lmpc_simulate_scenario_device(lmpc_handle *h, int64_t N, int T, const lmpc_s
     if (N == 0 || T == 0) return LMPC_OK;
     LMPC_NEED_DEVICE(h);
     LMPC_ENTER_DEVICE(h);
-    return run(h, N, T, s, x, xhat, uprev, U_traj, X_traj, flag_min, (hipStream_t)stream);
+    return run(h, N, T, s, x, xhat, uprev, U_traj, X_traj, flag_min, nullptr, (hipStream_t)stream);
 }
 
 int lmpc_simulate_scenario(lmpc_handle *h, int64_t N, int T, const lmpc_scenario_sim *s, double *x, double *xhat,
@@ -96,7 +105,40 @@ int lmpc_simulate_scenario(lmpc_handle *h, int64_t N, int T, const lmpc_scenario
     Staging sg;
     const StagedScenario g = stage_scenario(sg, N, T, s, x, xhat, uprev, U_traj, X_traj, flag_min);
     if (sg.err != hipSuccess) return sg.fail(h);
-    const int rc = run(h, N, T, &g.d, g.x, g.xhat, g.uprev, g.U, g.X, g.flag_min, nullptr);
+    const int rc = run(h, N, T, &g.d, g.x, g.xhat, g.uprev, g.U, g.X, g.flag_min, nullptr, nullptr);
+    if (rc == LMPC_OK && (!sg.ok(hipDeviceSynchronize(), "hipDeviceSynchronize") || !sg.download_all())) return sg.fail(h);
+    return rc;
+}
+
+int lmpc_simulate_scenario_taped_device(lmpc_handle *h, int64_t N, int T, const lmpc_scenario_sim *s, double *x, double *xhat,
+                                        double *uprev, double *U_traj, double *X_traj, int32_t *flag_min,
+                                        const lmpc_scenario_tape *tape, void *stream) {
+    if (!h) return LMPC_ERR_BADARG;
+    std::string msg = call_problem(h, N, T, s, x, xhat, uprev, true);
+    if (msg.empty() && N > 0 && T > 0 && (!tape || !tape->active || !tape->flag)) msg = "tape: NULL";
+    if (!msg.empty()) return fail(h, LMPC_ERR_BADARG, "lmpc_simulate_scenario_taped_device: " + msg);
+    if (N == 0 || T == 0) return LMPC_OK;
+    LMPC_NEED_DEVICE(h);
+    LMPC_ENTER_DEVICE(h);
+    return run(h, N, T, s, x, xhat, uprev, U_traj, X_traj, flag_min, tape, (hipStream_t)stream);
+}
+
+int lmpc_simulate_scenario_taped(lmpc_handle *h, int64_t N, int T, const lmpc_scenario_sim *s, double *x, double *xhat,
+                                 double *uprev, double *U_traj, double *X_traj, int32_t *flag_min, const lmpc_scenario_tape *tape) {
+    if (!h) return LMPC_ERR_BADARG;
+    std::string msg = call_problem(h, N, T, s, x, xhat, uprev, false);
+    if (msg.empty() && N > 0 && T > 0 && (!tape || !tape->active || !tape->flag)) msg = "tape: NULL";
+    if (!msg.empty()) return fail(h, LMPC_ERR_BADARG, "lmpc_simulate_scenario_taped: " + msg);
+    if (N == 0 || T == 0) return LMPC_OK;
+    LMPC_NEED_DEVICE(h);
+    LMPC_ENTER_DEVICE(h);
+    Staging sg;
+    const StagedScenario g = stage_scenario(sg, N, T, s, x, xhat, uprev, U_traj, X_traj, flag_min);
+    lmpc_scenario_tape dt;
+    dt.active = (uint64_t *)sg.out(tape->active, sizeof(uint64_t) * (size_t)T * (size_t)N * (size_t)h->P.words());
+    dt.flag = (int32_t *)sg.out(tape->flag, sizeof(int32_t) * (size_t)T * (size_t)N);
+    if (sg.err != hipSuccess) return sg.fail(h);
+    const int rc = run(h, N, T, &g.d, g.x, g.xhat, g.uprev, g.U, g.X, g.flag_min, &dt, nullptr);
     if (rc == LMPC_OK && (!sg.ok(hipDeviceSynchronize(), "hipDeviceSynchronize") || !sg.download_all())) return sg.fail(h);
     return rc;
 }

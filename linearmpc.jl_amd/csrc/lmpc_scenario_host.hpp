@@ -186,13 +186,19 @@ inline int scn_begin(lmpc_handle *h, DevBuf<double> &buf, int64_t N, const lmpc_
     return LMPC_OK;
 }
 
+// the first trajectory column of step k's r / d / p blocks of theta, for the forward's PRE record and the adjoint's
+template <class Rec>
+void scn_step_columns(Rec &A, int k) {
+    A.r.k0 = A.r.H > 0 ? k + 1 : k;                   // simulation.jl:102 get_preview(rs, k, Np) / rs[:, k]
+    A.d.k0 = k; A.p.k0 = k;                           // :103-104 get_preview(ds, k - 1, Np) / ds[:, k]
+}
+
 // step k's fields of the two records (ScnPre / ScnPost or the offset-free loop's)
 template <class Pre, class Post>
 void scn_advance(Pre &A, Post &B, const lmpc_scenario_sim *s, int64_t N, int T, int k, double *U_traj, double *X_traj) {
     const size_t row = (size_t)k * N;
     A.k = k;
-    A.r.k0 = A.r.H > 0 ? k + 1 : k;                   // simulation.jl:102 get_preview(rs, k, Np) / rs[:, k]
-    A.d.k0 = k; A.p.k0 = k;                           // :103-104 get_preview(ds, k - 1, Np) / ds[:, k]
+    scn_step_columns(A, k);
     A.ym_out = s->Ym_traj ? s->Ym_traj + row * s->ny : nullptr;
     A.y_out = s->Y_traj ? s->Y_traj + row * s->ny : nullptr;
     A.xhat_out = s->Xhat_traj ? s->Xhat_traj + row * s->nx : nullptr;

@@ -192,6 +192,18 @@ int sens_ensure(lmpc_handle *h, int64_t N) {
     return LMPC_OK;
 }
 
+int sens_refusal(lmpc_handle *h, const char *who) { return sens_refuse(h, who); }
+
+int sens_vjp_enqueue(lmpc_handle *h, int64_t N, const uint64_t *active, const int32_t *flag, const double *xbar, double *thbar,
+                     int32_t *status, hipStream_t st, int *list_pass) {
+    // (a sweep's VJPs are not the caller's derivative calls: lmpc_sens_launch_info keeps showing those)
+    const auto kept = h->sensRec;
+    const int rc = sens_launch<false>(h, N, active, flag, xbar, thbar, status, st);
+    if (rc == LMPC_OK && list_pass) *list_pass = h->sensRec.newest()[8];
+    h->sensRec = kept;
+    return rc;
+}
+
 int sens_reserve(lmpc_handle *h, int64_t N) {
     if (h->avi || h->P.avi || h->P.prox || h->P.nth == 0) return LMPC_OK;
     for (int32_t s : h->P.sense) if (s & SENSE_BINARY) return LMPC_OK;

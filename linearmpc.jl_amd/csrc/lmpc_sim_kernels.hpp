@@ -46,16 +46,23 @@ inline ThetaBlock to_block(const lmpc_block *b) {
     return t;
 }
 
-// entry q of column `col` of a block for scenario i; the column clamped to the trajectory ("hold last"), NULL = 0
+// the column of the trajectory that column `col` of a block is read from: clamped to the trajectory ("hold last").
+// The one statement of the rule: block_at reads through it, the scenario adjoint adds through it.
+__host__ __device__ __forceinline__ int block_col(const ThetaBlock &b, int col) {
+    col = col < b.T ? col : b.T - 1;
+    return col > 0 ? col : 0;
+}
+// entry q of column `col` of a block for scenario i, NULL = 0
 __device__ __forceinline__ double block_at(const ThetaBlock &b, long long i, int col, int q) {
     if (b.src == nullptr) return 0.0;
-    col = col < b.T ? col : b.T - 1;
-    col = col > 0 ? col : 0;
-    return b.src[i * b.stride + (long long)col * b.w + q];
+    return b.src[i * b.stride + (long long)block_col(b, col) * b.w + q];
 }
-// entry q (< width()) of the block as it enters theta: the columns from k0 on, one after the other
+// entry q (< width()) of the block as it enters theta: the columns from k0 on, one after the other -- row
+// block_entry_row of trajectory column block_entry_col
+__host__ __device__ __forceinline__ int block_entry_col(const ThetaBlock &b, int q) { return block_col(b, b.k0 + q / b.w); }
+__host__ __device__ __forceinline__ int block_entry_row(const ThetaBlock &b, int q) { return q % b.w; }
 __device__ __forceinline__ double block_entry(const ThetaBlock &b, long long i, int q) {
-    return block_at(b, i, b.k0 + q / b.w, q % b.w);
+    return b.src == nullptr ? 0.0 : b.src[i * b.stride + (long long)block_entry_col(b, q) * b.w + block_entry_row(b, q)];
 }
 
 // (The kernels that are not templates are `inline`: this header is part of two translation units.  The compiler takes
@@ -119,7 +126,7 @@ inline __global__ __launch_bounds__(256) void update_parameter_kernel(
 // unrolled, so every index into a scenario's record is static and the record is read and written with wide accesses
 // (element by element from run-time loops a 32-byte record moved at a quarter of the rate); NXT == 0: run-time nx (<= 32).
 template <int NXT, class F>
-__device__ __forceinline__ void for_nx(int nx, F &&f) {
+__host__ __device__ __forceinline__ void for_nx(int nx, F &&f) {
     if constexpr (NXT > 0) {
 #pragma unroll
         for (int c = 0; c < NXT; c++) f(c);

@@ -295,10 +295,16 @@ class Simulation:
     plant = a `NonlinearPlant` (`lmpc_simulate_scenario_nonlinear_device`): the true plant is its traced program, stepped
     on the device; params (nq,) or (N_scen, nq) are its q; process_noise, measurement_noise, Gw, seed and observer= as
     above; the measurement is its linear C, Dd, h_offset.  A list of plants, an `ExplicitMPC` or an `OffsetFreeObserver`
-    raises ValueError."""
+    raises ValueError.
+    tape=True keeps every step's working set and exit flags (`lmpc_simulate_scenario_taped_device`; the run is the same
+    bit for bit) so that `vjp` can differentiate the run.  The plain loop alone has an adjoint: an `ExplicitMPC`, an
+    `OffsetFreeObserver`, noise drawn or supplied through the uncertain loop, a list of plants and a `NonlinearPlant` are
+    refused here, before any call into the library (those loops are entry points of their own with no adjoint beside
+    them): an LmpcError with the code of LMPC_ERR_UNSUPPORTED.  What the library itself refuses (BINARY rows, a
+    variational or proximal-point controller) is refused by `vjp`, with the library's text."""
 
     def __init__(self, mpc, scenario, plant, observer=None, warm=False, cost=None, mode=0, Gw=None, seed=0, plant_index=None,
-                 params=None):
+                 params=None, tape=False):
         import torch
         from .mpc import ExplicitMPC
         from .nonlinear import NonlinearPlant
@@ -333,6 +339,10 @@ class Simulation:
             raise ValueError("Gw needs the scenario's process_noise")
         if empc is not None and isinstance(observer, OffsetFreeObserver):
             raise ValueError("the offset-free observer is not available in the explicit controller's loop")
+        if tape and (empc is not None or uncertain or nonlinear or isinstance(observer, OffsetFreeObserver)):
+            from ._cabi import LmpcError
+            raise LmpcError(-103, "lmpc_scenario_vjp: the explicit, offset-free, uncertain and nonlinear scenario loops "
+                                  "have no adjoint (the plain scenario loop alone is differentiated)")
         if empc is not None:                      # simulation.jl:37 with compute_control(empc, x), utils.jl:53-60
             if empc.controller is None:
                 raise RuntimeError("Need to build a binary search tree to evaluate control law")
@@ -359,6 +369,7 @@ class Simulation:
         obs = _observer_arrays(observer)
         if obs is not None:
             model.set_observer(*obs, plant.nx + ndo, plant.nu, plant.nd, plant.ny)
+        self._observer = None if obs is None else (obs, (plant.nx + ndo, plant.nu, plant.nd, plant.ny))
         specs = scenario_blocks(mpc, scenario, ndo)
         up = lambda sp: None if sp["data"] is None else torch.from_numpy(np.swapaxes(sp["data"], -1, -2).copy()).to(dev)
         x = torch.from_numpy(scenario.x0.copy()).to(dev)
@@ -394,7 +405,8 @@ class Simulation:
                 r_preview=specs["r"]["H"], d_preview=specs["d"]["H"], p_preview=specs["p"]["H"],
                 r_width=specs["r"]["w"], d_width=specs["d"]["w"], p_width=specs["p"]["w"], uprev=uprev,
                 use_observer=obs is not None, warm=warm, cost=cost, want=want,
-                want_cost=cost is not None, want_violation=cost is not None and cost[0].nc > 0)
+                want_cost=cost is not None, want_violation=cost is not None and cost[0].nc > 0, **({"tape": True} if tape else {}))
+        self._tape = out.get("tape")
         torch.cuda.synchronize(dev)
         model.check()
         per = lambda t: np.ascontiguousarray(t.cpu().numpy().transpose(1, 2, 0))      # (T, S, w) -> (S, w, T)
@@ -420,6 +432,52 @@ class Simulation:
             for k in ("xs", "us", "ys", "yms", "xhats", "ds", "rs") + (("dhats",) if off is not None else ()) + \
                     (("ws",) if hasattr(self, "ws") else ()):
                 setattr(self, k, getattr(self, k)[0])
+
+    def vjp(self, xs_bar=None, us_bar=None):
+        """The gradient of <xs_bar, xs> + <us_bar, us> of a run made with tape=True (`lmpc_scenario_vjp_device`).  xs_bar /
+        us_bar: shaped like `xs` / `us` ((N_scen, w, N), or (w, N) for a single scenario; xs_bar may carry an N + 1-th column
+        for the state after the last step), None = zeros.  Returns a dict of numpy arrays in the shapes of the inputs the run
+        was given: x0 like the scenario's x0; r, d, p like the scenario's trajectories (a shared trajectory gets the sum over
+        the scenarios, columns beyond the run zeros; a block theta does not hold is left out); uprev (nuprev,): the
+        controller's one previous control, summed over the scenarios; status_min (N_scen,): 1 where every step was
+        differentiated (BatchedQP.scenario_vjp).  The controller's handle is shared by every Simulation of the MPC: the
+        run's own observer is put back on it first, so a Simulation made in between with another observer does not
+        change the result."""
+        import torch
+        if self._tape is None:
+            raise ValueError("Simulation.vjp needs a run made with tape=True")
+        if self._observer is not None:
+            self.model.set_observer(*self._observer[0], *self._observer[1])
+        tape, sc = self._tape, self.scenario
+        S, T, nx, nu = tape["N"], tape["T"], tape["nx"], tape["nu"]
+        dev = tape["flag"].device
+
+        def step_major(a, w, cols):
+            if a is None:
+                return None
+            a = np.asarray(a, float)
+            a = a[None] if a.ndim == 2 else a
+            if a.shape[:2] != (S, w) or a.shape[2] not in cols:
+                raise ValueError(f"a cotangent must have shape ({S}, {w}, {cols[0]}), got {a.shape}")
+            full = np.zeros((cols[-1], S, w))
+            full[:a.shape[2]] = a.transpose(2, 0, 1)
+            return torch.from_numpy(full).to(dev)
+
+        g = self.model.scenario_vjp(tape, Xbar=step_major(xs_bar, nx, (T, T + 1)), Ubar=step_major(us_bar, nu, (T,)))
+        torch.cuda.synchronize(dev)
+        x0 = g["x0bar"].cpu().numpy()
+        out = dict(x0=x0[0] if sc.single else x0, status_min=g["status_min"].cpu().numpy())
+        if tape["nup"]:
+            out["uprev"] = g["uprev0bar"].cpu().numpy().sum(axis=0)
+        for k in ("r", "d", "p"):
+            a = getattr(sc, k)
+            if a is None or k + "bar" not in g:
+                continue
+            bar = g[k + "bar"].cpu().numpy()                   # (S, w, Tc): the columns of the run
+            full = np.zeros((S,) + a.shape[-2:])
+            full[..., :bar.shape[-1]] = bar
+            out[k] = full if a.ndim == 3 else full.sum(axis=0)
+        return out
 
 
 _scoring = {}

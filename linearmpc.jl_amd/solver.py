@@ -133,7 +133,100 @@ def sens_host(pack, active, exitflag, xbar=None, settings: Settings | None = Non
     return out, status
 
 
+def scenario_vjp_host(pack, sim, active, flag, Xbar=None, Ubar=None, observer=None, xhat_given=False,
+                      settings: Settings | None = None, is_avi=False, want=("r", "d", "p")):
+    """`lmpc_scenario_vjp_host`: the backward sweep of a taped scenario run on the CPU, no GPU and no handle.  pack: a raw
+    LDP pack as `BatchedQP.ldp()` returns it.  sim: dict with nx, nu, nd, ny, plant (rows [f, F, G, Gd]), measurement
+    (rows [h, C, Dd] or None), nuprev, use_observer and the blocks r, d, p as (w, T, H) (columns available, preview
+    length) or None.  active (T, N, words) uint64 and flag (T, N) int32: the tape.  Xbar (T+1, N, nx), Ubar (T, N, nu) or
+    None.  observer: (plant_dynamics, measurement_function, k_transpose) with use_observer.  Returns a dict: x0bar,
+    xhat0bar (None unless xhat_given), uprev0bar, rbar / dbar / pbar step-major (Tc, N, w) or None, status_min."""
+    n, m, ms, nth, nout = (int(pack[k]) for k in ("n", "m", "ms", "nth", "nout"))
+    arrs = [_f64(np.asarray(pack[k], float).reshape(sh)) for k, sh in
+            (("M", (m, n)), ("du", (m,)), ("dl", (m,)), ("Dth", (m, nth)), ("Rout", (nout, n)), ("x0", (nout,)),
+             ("Xth", (nout, nth)))]
+    sense = np.ascontiguousarray(pack["sense"], dtype=np.int32).reshape(m)
+    words = (2 * m + 63) // 64
+    flag = np.ascontiguousarray(np.asarray(flag, np.int32))
+    T, N = (int(v) for v in flag.shape)
+    act = np.ascontiguousarray(np.asarray(active, np.uint64).reshape(T, N, words))
+    nx, nu, nd, ny, nup = (int(sim[k]) for k in ("nx", "nu", "nd", "ny", "nuprev"))
+    use_obs = bool(sim.get("use_observer"))
+    keep = [_f64(np.asarray(sim["plant"], float).reshape(-1)),
+            None if sim.get("measurement") is None else _f64(np.asarray(sim["measurement"], float).reshape(-1))]
+    d = _cabi.ScenarioSim()
+    d.nx, d.nu, d.nd, d.ny = nx, nu, nd, ny
+    d.plant = keep[0].ctypes.data
+    d.measurement = None if keep[1] is None else keep[1].ctypes.data
+    d.nuprev, d.use_observer, d.warm = nup, int(use_obs), 0
+    out = dict(x0bar=np.zeros((N, nx)), xhat0bar=np.zeros((N, nx)) if (use_obs and xhat_given) else None,
+               uprev0bar=np.zeros((N, nup)), status_min=np.zeros(N, np.int32), rbar=None, dbar=None, pbar=None)
+    for name in ("r", "d", "p"):
+        b = sim.get(name)
+        if b is None:
+            setattr(d, name, Block(None, 0, 0, 1, 0, 0))
+            continue
+        w, Tc, H = (int(v) for v in b)
+        setattr(d, name, Block(None, 0, w, Tc, 0, H))
+        if name in want and w > 0:
+            out[name + "bar"] = np.full((max(Tc, 1), N, w), np.nan)      # (the call zeroes it)
+    d.noise = Block(None, 0, 0, 1, 0, 0)
+    od = None
+    if use_obs and observer is not None:
+        oa = [_f64(np.asarray(a, float).reshape(-1)) for a in observer]
+        keep += oa
+        od = ctypes.byref(Observer(nx, nu, nd, ny, *[a.ctypes.data for a in oa]))
+    xb = None if Xbar is None else _f64(np.asarray(Xbar, float).reshape(T + 1, N, nx))
+    ub = None if Ubar is None else _f64(np.asarray(Ubar, float).reshape(T, N, nu))
+    ptr = lambda a: None if a is None else a.ctypes.data
+    tape = _cabi.ScenarioTape(ptr(act), ptr(flag))
+    g = _cabi.ScenarioGrad(ptr(xb), ptr(ub), ptr(out["x0bar"]), ptr(out["xhat0bar"]), ptr(out["uprev0bar"]), ptr(out["rbar"]),
+                           ptr(out["dbar"]), ptr(out["pbar"]), ptr(out["status_min"]))
+    sp = ctypes.cast(ctypes.pointer(settings), _vp) if settings is not None else None
+    check(lib().lmpc_scenario_vjp_host(n, m, ms, nth, nout, *[_ptr(a) for a in arrs], _ptr(sense), sp, int(bool(is_avi)), od,
+                                       N, T, ctypes.byref(d), ctypes.byref(tape), ctypes.byref(g)))
+    return out
+
+
 _AUTOGRAD_FN = None
+_SCENARIO_FN = None
+
+
+def _scenario_fn():
+    """The torch.autograd.Function of `BatchedQP.simulate_scenario_autograd` (made on first use)."""
+    global _SCENARIO_FN
+    if _SCENARIO_FN is not None:
+        return _SCENARIO_FN
+    import torch
+
+    class ScenarioFunction(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, qp, T, plant, kw, x, uprev, r, d, p):
+            det = lambda t: None if t is None else t.detach()
+            out = qp.simulate_scenario(x.detach().clone(), T, plant, r=det(r), d=det(d), p=det(p),
+                                       uprev=None if uprev is None else uprev.detach().clone(), want=("U", "X"), tape=True, **kw)
+            ctx.qp, ctx.tape = qp, out["tape"]
+            ctx.shapes = [None if t is None else tuple(t.shape) for t in (r, d, p)]
+            ctx.status_min = None
+            ctx.mark_non_differentiable(out["flag_min"])
+            return out["X"], out["U"], out["flag_min"]
+
+        @staticmethod
+        def backward(ctx, Xbar, Ubar, _fbar):
+            g = ctx.qp.scenario_vjp(ctx.tape, Xbar=None if Xbar is None else Xbar.contiguous(),
+                                    Ubar=None if Ubar is None else Ubar.contiguous())
+            ctx.status_min = g["status_min"]
+            grads = []
+            for name, shape in zip(("rbar", "dbar", "pbar"), ctx.shapes):
+                t = g.get(name)
+                if t is None or shape is None:
+                    grads.append(None)
+                else:                                  # a shared block: the per-scenario gradient summed over scenarios
+                    grads.append(t if len(shape) == 3 else t.sum(0).reshape(shape))
+            return (None, None, None, None, g["x0bar"], g["uprev0bar"] if ctx.tape["nup"] else None, *grads)
+
+    _SCENARIO_FN = ScenarioFunction
+    return ScenarioFunction
 
 
 def _autograd_fn():
@@ -726,7 +819,7 @@ class BatchedQP:
     def simulate_scenario(self, x, T, plant, measurement=None, nd=0, ny=0, r=None, d=None, p=None, noise=None,
                           r_preview=0, d_preview=0, p_preview=0, r_width=0, d_width=None, p_width=0, xhat=None,
                           uprev=None, use_observer=False, warm=False, cost=None, want=("U", "X"), want_cost=False,
-                          want_violation=False, stream=None, launch=None):
+                          want_violation=False, stream=None, launch=None, tape=False):
         """The scenario loop (`lmpc_simulate_scenario_device`): torch CUDA tensors in and out, enqueued on `stream`
         (default: torch's current stream), not synchronised.  `launch(desc, N, T, x, xhat, uprev, U, X, flag_min,
         stream)`, all but desc, N, T as ctypes pointers: another entry point taking the same descriptor and arrays
@@ -737,7 +830,8 @@ class BatchedQP:
         [h_offset, C, Dd] (host arrays).  r / d / p / noise: (w,), (w, Tc) shared or (N, w, Tc) per scenario, or None
         = zeros of width r_width / d_width (default nd) / p_width; *_preview = Np or 0.  cost: `sim_cost(...)`.
         want: which of "U", "X", "Y", "Ym", "Xhat", "D" to store.  Returns a dict of tensors (step-major, as the C
-        side lays them out) plus x, xhat, uprev, flag_min and, if asked for, cost / violation."""
+        side lays them out) plus x, xhat, uprev, flag_min and, if asked for, cost / violation.  tape=True: the taped
+        run (`lmpc_simulate_scenario_taped_device`, the same outputs) and out["tape"], what `scenario_vjp` takes."""
         import torch
         f64, dv = torch.float64, self.device
         if not (x.is_cuda and x.dtype == f64 and x.is_contiguous() and x.dim() == 2 and x.device.index == dv):
@@ -780,12 +874,83 @@ class BatchedQP:
         st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
         args = (_vp(x.data_ptr()), _dev_arg(xhat, "xhat", f64, N * nx, dv), _dev_arg(uprev, "uprev", f64, N * nup, dv),
                 _vp(ptr(out.get("U"))), _vp(ptr(out.get("X"))), _vp(out["flag_min"].data_ptr()), _vp(st))
-        if launch is not None:
+        if tape:
+            if launch is not None:
+                raise ValueError("tape=True is the plain scenario loop's: it cannot be combined with launch=")
+            act = torch.empty((T, N, self.words), dtype=torch.int64, device=dev)
+            flg = torch.empty((T, N), dtype=torch.int32, device=dev)
+            ct = _cabi.ScenarioTape(act.data_ptr(), flg.data_ptr())
+            check(lib().lmpc_simulate_scenario_taped_device(self._h, N, T, ctypes.byref(desc), *args[:-1], ctypes.byref(ct),
+                                                            args[-1]), self._h)
+            out["tape"] = dict(active=act, flag=flg, desc=desc, N=N, T=T, nx=nx, nu=nu, nup=nup,
+                               xhat_given=xhat is not None, keep=keep)
+        elif launch is not None:
             launch(desc, N, T, *args)
         else:
             check(lib().lmpc_simulate_scenario_device(self._h, N, T, ctypes.byref(desc), *args), self._h)
         out["_keep"] = keep                      # the launches are asynchronous: keep the sources alive
         return out
+
+    SCENARIO_ADJOINT_FIELDS = ("seq", "NX", "grid", "lds", "T", "nprob", "list_pass", "tile")
+
+    def scenario_adjoint_launch_info(self, since=0):
+        """The handle's most recent backward sweeps (lmpc_scenario_adjoint_launch_info; at most four are kept), oldest
+        first: NX of the scenario_adjoint_kernel instantiation (0: run-time nx), grid, lds, T, nprob, list_pass (1: the
+        VJP's wavefront pass was enqueued), tile (entries of a theta-bar record staged at a time)."""
+        W = len(self.SCENARIO_ADJOINT_FIELDS)
+        out = (ctypes.c_int32 * (4 * W))()
+        k = lib().lmpc_scenario_adjoint_launch_info(self._h, out, 4)
+        if k < 0:
+            check(k, self._h)
+        recs = [dict(zip(self.SCENARIO_ADJOINT_FIELDS, (int(v) for v in out[q * W:(q + 1) * W]))) for q in range(k)]
+        return [r for r in recs if r["seq"] > since]
+
+    def scenario_vjp(self, tape, Xbar=None, Ubar=None, want=("r", "d", "p"), stream=None):
+        """`lmpc_scenario_vjp_device` on the tape of `simulate_scenario(..., tape=True)`: the gradient of
+        <Xbar, X> + <Ubar, U> (step-major CUDA tensors (T+1, N, nx) / (T, N, nu), None = zeros) with respect to the run's
+        initial values and trajectories.  Enqueued on `stream` (default: torch's current stream), not synchronised.
+        Returns a dict of tensors: x0bar (N, nx), xhat0bar (N, nx; only when the run was given an xhat), uprev0bar
+        (N, nuprev), status_min (N,) int32 and, for each block of `want` the run's theta has, rbar / dbar / pbar as
+        (N, w, Tc) views -- always per scenario: the gradient of a shared trajectory is their sum over scenarios.  With
+        use_observer the sweep reads the handle's observer as it stands: it must still be the one the taped run used."""
+        import torch
+        f64, dv = torch.float64, self.device
+        desc, N, T, nx, nu, nup = (tape[k] for k in ("desc", "N", "T", "nx", "nu", "nup"))
+        dev = tape["flag"].device
+        g = dict(x0bar=torch.empty((N, nx), dtype=f64, device=dev), uprev0bar=torch.empty((N, nup), dtype=f64, device=dev),
+                 status_min=torch.empty(N, dtype=torch.int32, device=dev))
+        if tape["xhat_given"]:
+            g["xhat0bar"] = torch.empty((N, nx), dtype=f64, device=dev)
+        raw = {}
+        for name in ("r", "d", "p"):
+            b = getattr(desc, name)
+            if name in want and b.w > 0:
+                raw[name] = torch.empty((max(int(b.T), 1), N, int(b.w)), dtype=f64, device=dev)
+                g[name + "bar"] = raw[name].permute(1, 2, 0)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        cg = _cabi.ScenarioGrad(_dev_arg(Xbar, "Xbar", f64, (T + 1) * N * nx, dv), _dev_arg(Ubar, "Ubar", f64, T * N * nu, dv),
+                                g["x0bar"].data_ptr(), ptr(g.get("xhat0bar")), g["uprev0bar"].data_ptr(), ptr(raw.get("r")),
+                                ptr(raw.get("d")), ptr(raw.get("p")), g["status_min"].data_ptr())
+        ct = _cabi.ScenarioTape(tape["active"].data_ptr(), tape["flag"].data_ptr())
+        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        check(lib().lmpc_scenario_vjp_device(self._h, N, T, ctypes.byref(desc), ctypes.byref(ct), ctypes.byref(cg), _vp(st)),
+              self._h)
+        return g
+
+    def simulate_scenario_autograd(self, x, T, plant, r=None, d=None, p=None, uprev=None, **kw):
+        """The scenario loop inside a torch graph: returns (X, U, flag_min) -- X (T+1, N, nx) and U (T, N, nu) carry the
+        gradient to whichever of x, uprev, r, d, p require it (forward: the taped run on copies of x and uprev; backward:
+        ONE `scenario_vjp` on the current torch stream; a shared block's gradient is the per-scenario one summed over
+        scenarios), flag_min is marked non-differentiable.  The `status_min` of the most recent backward is
+        `X.grad_fn.status_min`.  kw: the other arguments of `simulate_scenario` (want / tape / launch excluded).  With no
+        input requiring grad this is the plain call on copies of x and uprev, and no tape is allocated."""
+        import torch
+        ins = (x, uprev, r, d, p)
+        if not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ins)):
+            out = self.simulate_scenario(x.detach().clone(), T, plant, r=r, d=d, p=p,
+                                         uprev=None if uprev is None else uprev.detach().clone(), want=("U", "X"), **kw)
+            return out["X"], out["U"], out["flag_min"]
+        return _scenario_fn().apply(self, T, plant, kw, x, uprev, r, d, p)
 
     def uncertainty(self, N, nx, process=None, measurement_noise=None, Gw=None, seed=0, scenario_offset=0, step_offset=0,
                     plants=None, plant_index=None, W=None):
