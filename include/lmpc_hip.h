@@ -1318,6 +1318,83 @@ int lmpc_solve_jacobian_host(int n, int m, int ms, int nth, int nout, const doub
 int lmpc_sens_launch_info(const lmpc_handle *h, int32_t *out, int max);
 
 /*
+ * Gradient with respect to the pack: what a cotangent xbar of the batch's solutions gives for the pack itself, SUMMED
+ * over the N points -- one small gradient per handle.  With lmpc_transform_vjp behind it this is the derivative with
+ * respect to the controller's data (H, f, f_theta, A, bu, bl, W, K).
+ *
+ * A point with exit flag >= 1 has active rows a_0 < a_1 < ... (as above) and sides u_i = 1 if the upper bit of row a_i
+ * is set, else 0 (a row with both bits counts as upper).  Its solution is one affine piece of the pack:
+ *     d_i = (u_i ? du : dl)[a_i] + Dth[a_i] . theta      lambda = K_A^-1 d      v = M_A' lambda
+ *     x = x0 + Xth theta + Rout v
+ * With y = K_A^-1 (M_A Rout') xbar (the y of the VJP above), w = M_A' y, vbar = Rout' xbar and g = vbar - w the point
+ * contributes
+ *     Mbar[a_i][c]   lambda_i g_c - y_i v_c            Routbar[q][c]  xbar_q v_c
+ *     dubar[a_i]     y_i where u_i = 1                 x0bar[q]       xbar_q
+ *     dlbar[a_i]     y_i where u_i = 0                 Xthbar[q][t]   xbar_q theta_t
+ *     Dthbar[a_i][t] y_i theta_t
+ * Status per point and thbar (N x nth; both may be NULL) are those of lmpc_solve_vjp_device on the same inputs, bit
+ * for bit.  A point whose status is not 1 contributes +0.0 to every sum.
+ *
+ * Arithmetic contract (binary64; every multiply-add an explicit fma, nothing else fused; restated in numpy in
+ * tests/pack_grad_reference.py; the lane path, the wavefront path, the host-pointer call and the *_host function give
+ * the same values):
+ *   - the derived pack, the factor, w_i (here the right-hand side of y), both substitutions and thbar are those of the
+ *     contract above.
+ *   - d_i is one chain: it starts at the side's bound, then acc = fma(Dth[a_i][t], theta[t], acc) for t ascending.
+ *     lambda comes from d by the same forward, diagonal and backward order as y.
+ *   - v_c, w_c, vbar_c are chains from 0: fma(M[a_i][c], lambda_i, acc) over i ascending, the same with y_i, and
+ *     fma(Rout[q][c], xbar[q], acc) over q ascending; g_c = vbar_c - w_c.
+ *   - the Mbar contribution is fma(lambda_i, g_c, -(y_i * v_c)); every other contribution is one product or a copy.
+ *   - every output entry is the root of the balanced binary tree over the point indices 0 .. 2^ceil(log2 N) - 1: a leaf
+ *     is the point's contribution, +0.0 for an absent index, a row outside the point's set or a status other than 1; a
+ *     node is left + right.  Results are compared as values (the sign of a zero is free).  No atomic touches a double.
+ *
+ * Device call: DEVICE pointers; it only enqueues on `stream` and never waits.  The batch is processed in slabs of 2^s
+ * points: per slab the lane kernel (and the wavefront kernel over the work list) leaves [lambda | y] per point, the
+ * reduce kernel one partial per 64 points, and launches of the tree kernel the slab's sum; a last tree sums the slab
+ * sums into the caller's arrays.  Scratch: one slab of records and partials plus one sum per slab, allocated by the
+ * first call of a size (or by lmpc_reserve after lmpc_set_option "pack_grad_reserve" 1), released by
+ * lmpc_release_scratch.  lmpc_set_option "pack_grad_slab" s (8 .. 20; 0 = the largest s whose records and partials stay
+ * within 64 MiB).  Outputs row-major as lmpc_get_ldp lays the pack out (Mbar m x n, dubar m, dlbar m, Dthbar m x nth,
+ * Routbar nout x n, x0bar nout, Xthbar nout x nth); any of them may be NULL, and with all of them NULL only stage 1 runs
+ * (thbar and status at the VJP's cost).  theta: N x nth, xbar: N x nout.  As for the VJP, the first call on a handle also
+ * uploads the constants it needs with one blocking copy (lmpc_reserve with "pack_grad_reserve" 1 does it ahead of time).
+ * Refusals and options "sens_cap" / "sens_force_list" as for lmpc_solve_vjp_device.  Binary64 only.
+ */
+int lmpc_solve_pack_vjp_device(lmpc_handle *h, int64_t N, const double *theta, const uint64_t *active, const int32_t *exitflag,
+                               const double *xbar, double *Mbar, double *dubar, double *dlbar, double *Dthbar, double *Routbar,
+                               double *x0bar, double *Xthbar, double *thbar, int32_t *status, void *stream);
+/* HOST pointers; synchronous. */
+int lmpc_solve_pack_vjp(lmpc_handle *h, int64_t N, const double *theta, const uint64_t *active, const int32_t *exitflag,
+                        const double *xbar, double *Mbar, double *dubar, double *dlbar, double *Dthbar, double *Routbar,
+                        double *x0bar, double *Xthbar, double *thbar, int32_t *status);
+/* The same arithmetic on the CPU, no GPU and no handle, from the raw LDP pack and settings as lmpc_solve_vjp_host takes
+ * them (here du, dl are read wherever m > 0; x0 is not read and may be NULL). */
+int lmpc_solve_pack_vjp_host(int n, int m, int ms, int nth, int nout, const double *M, const double *du, const double *dl,
+                             const double *Dth, const double *Rout, const double *x0, const double *Xth, const int32_t *sense,
+                             const lmpc_settings *s, int is_avi, int64_t N, const double *theta, const uint64_t *active,
+                             const int32_t *exitflag, const double *xbar, double *Mbar, double *dubar, double *dlbar,
+                             double *Dthbar, double *Routbar, double *x0bar, double *Xthbar, double *thbar, int32_t *status);
+/* The handle's most recent pack-gradient calls (at most four are kept), oldest first, LMPC_PACK_GRAD_INFO_WORDS words
+ * each: number of the call (from 1), CAP of the pack_grad_lane_kernel instantiation, the capacity it ran with, its grid
+ * on the first slab, its LDS bytes, what was staged in LDS (bit 0: the derived pack by the lane kernel, bit 1: M and
+ * Rout by the reduce kernel), 1 if pack_grad_wave_kernel was enqueued, its grid, the reduce kernel's grid on the first
+ * slab, its LDS bytes, log2 of the slab, the number of slabs, the tree kernel's launches in the call, the scratch in
+ * KiB, the doubles of one partial, N, the column chunks of M the reduce kernel's grid was split into on the first slab
+ * (its grid.y less one).  Without any output array the reduce and tree fields are 0. */
+#define LMPC_PACK_GRAD_INFO_WORDS 17
+int lmpc_pack_grad_launch_info(const lmpc_handle *h, int32_t *out, int max);
+/* Host only: the adjoint of lmpc_transform.  Inputs as lmpc_transform (column-major H, f_theta, A, W, Kfb), then the
+ * gradients with respect to its seven outputs (row-major as it writes them; a NULL one counts as zero), then the
+ * gradients with respect to its inputs in the inputs' own layout (Hbar symmetric, as the transform reads (H + H') / 2;
+ * any may be NULL).  Plain binary64, no bit contract.  Fails as lmpc_transform fails. */
+int lmpc_transform_vjp(int n, int m, int ms, int nth, int nout, const double *H, const double *f, const double *f_theta,
+                       const double *A, const double *bu, const double *bl, const double *W, const int32_t *sense,
+                       const double *Kfb, int nx, const double *Mbar, const double *dubar, const double *dlbar,
+                       const double *Dthbar, const double *Routbar, const double *x0bar, const double *Xthbar, double *Hbar,
+                       double *fbar, double *fthbar, double *Abar, double *bubar, double *blbar, double *Wbar, double *Kfbbar);
+
+/*
  * Scenario loop adjoint: the gradient of a run of lmpc_simulate_scenario_device with respect to its initial values and
  * its r / d / p trajectories.  Once a step's active set is known the step is affine in its inputs, so the adjoint of a
  * run is a backward sweep over the steps: one VJP of the differentiable solve per step (above) and one transposed glue

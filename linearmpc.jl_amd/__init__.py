@@ -10,7 +10,8 @@ one-process-per-GPU sharding helpers (shard).  Importing the package does not ne
 setting up or solving does, and there is no CPU fallback.
 """
 from ._cabi import LIB_PATH, SYMBOLS, LmpcError, Settings, default_settings, default_settings_f32, lib  # noqa: F401
-from .solver import BatchedQP, MultiQP, scenario_vjp_host, sens_host, transform, transform_avi  # noqa: F401
+from .solver import (BatchedQP, MultiQP, pack_vjp_host, scenario_vjp_host, sens_host, solve_mpqp_autograd, transform,  # noqa: F401
+                     transform_avi, transform_vjp)
 from .mpc import MPC, MPQP, ExplicitMPC, GeneratedController  # noqa: F401
 from .shard import gather_shards, shard_bounds, shard_counts, solve_sharded  # noqa: F401
 from .simulation import (Gaussian, OffsetFreeObserver, Plant, Scenario, Simulation, Uniform, constraint_violation, evaluate_cost,  # noqa: F401
@@ -18,7 +19,7 @@ from .simulation import (Gaussian, OffsetFreeObserver, Plant, Scenario, Simulati
 from .nonlinear import NonlinearPlant, TraceError, abs_, cos, fma, maximum, minimum, sin  # noqa: F401
 from . import explicit  # noqa: F401
 
-__all__ = ["BatchedQP", "MultiQP", "transform", "transform_avi", "sens_host", "scenario_vjp_host", "MPC", "MPQP", "ExplicitMPC", "GeneratedController", "Settings", "default_settings", "default_settings_f32", "LmpcError",
+__all__ = ["BatchedQP", "MultiQP", "transform", "transform_avi", "sens_host", "scenario_vjp_host", "pack_vjp_host", "transform_vjp", "solve_mpqp_autograd", "MPC", "MPQP", "ExplicitMPC", "GeneratedController", "Settings", "default_settings", "default_settings_f32", "LmpcError",
            "gather_shards", "shard_bounds", "shard_counts", "solve_sharded", "explicit", "lib", "LIB_PATH", "Plant", "Scenario", "Simulation", "evaluate_cost", "constraint_violation",
            "OffsetFreeObserver", "offset_free_observer", "Uniform", "Gaussian", "noise_draw", "SYMBOLS",
            "NonlinearPlant", "TraceError", "sin", "cos", "fma", "minimum", "maximum", "abs_"]

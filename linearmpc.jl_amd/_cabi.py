@@ -50,6 +50,8 @@ SYMBOLS = (
     "lmpc_solve_vjp_host", "lmpc_solve_jacobian_host", "lmpc_sens_launch_info",
     "lmpc_simulate_scenario_taped_device", "lmpc_simulate_scenario_taped", "lmpc_scenario_vjp_device", "lmpc_scenario_vjp",
     "lmpc_scenario_vjp_host", "lmpc_scenario_adjoint_launch_info",
+    "lmpc_solve_pack_vjp_device", "lmpc_solve_pack_vjp", "lmpc_solve_pack_vjp_host", "lmpc_pack_grad_launch_info",
+    "lmpc_transform_vjp",
 )
 
 
@@ -351,6 +353,17 @@ def lib():
         L.lmpc_solve_jacobian_host.restype = i32
         L.lmpc_sens_launch_info.argtypes = [vp, vp, i32]
         L.lmpc_sens_launch_info.restype = i32
+    if hasattr(L, "lmpc_solve_pack_vjp_device"):   # (an older build selected with LMPC_HIP_LIB for an A/B lacks them)
+        L.lmpc_solve_pack_vjp_device.argtypes = [vp, i64] + [vp] * 14
+        L.lmpc_solve_pack_vjp_device.restype = i32
+        L.lmpc_solve_pack_vjp.argtypes = [vp, i64] + [vp] * 13
+        L.lmpc_solve_pack_vjp.restype = i32
+        L.lmpc_solve_pack_vjp_host.argtypes = [i32] * 5 + [vp] * 9 + [i32, i64] + [vp] * 13
+        L.lmpc_solve_pack_vjp_host.restype = i32
+        L.lmpc_pack_grad_launch_info.argtypes = [vp, vp, i32]
+        L.lmpc_pack_grad_launch_info.restype = i32
+        L.lmpc_transform_vjp.argtypes = [i32] * 5 + [vp] * 9 + [i32] + [vp] * 15
+        L.lmpc_transform_vjp.restype = i32
     if hasattr(L, "lmpc_scenario_vjp_device"):   # (an older build selected with LMPC_HIP_LIB for an A/B lacks them)
         tp, gp = ctypes.POINTER(ScenarioTape), ctypes.POINTER(ScenarioGrad)
         L.lmpc_simulate_scenario_taped_device.argtypes = [vp, i64, i32, sp] + [vp] * 6 + [tp, vp]

@@ -974,6 +974,19 @@ int lmpc_transform(int n, int m, int ms, int nth, int nout, const double *H, con
     return LMPC_OK;
 }
 
+int lmpc_transform_vjp(int n, int m, int ms, int nth, int nout, const double *H, const double *f, const double *f_theta,
+                       const double *A, const double *bu, const double *bl, const double *W, const int32_t *sense,
+                       const double *Kfb, int nx, const double *Mbar, const double *dubar, const double *dlbar,
+                       const double *Dthbar, const double *Routbar, const double *x0bar, const double *Xthbar, double *Hbar,
+                       double *fbar, double *fthbar, double *Abar, double *bubar, double *blbar, double *Wbar, double *Kfbbar) {
+    std::string err;
+    const int rc = qp_to_ldp_vjp(n, m, ms, nth, nout, H, f, f_theta, A, bu, bl, W, sense, Kfb, nx,
+                                 LdpBars{Mbar, dubar, dlbar, Dthbar, Routbar, x0bar, Xthbar},
+                                 QpBars{Hbar, fbar, fthbar, Abar, bubar, blbar, Wbar, Kfbbar}, err);
+    if (rc != LMPC_OK) return fail(nullptr, rc, err);
+    return LMPC_OK;
+}
+
 int lmpc_get_prox(const lmpc_handle *h, double *Hinv, double *x0f, double *Xthf, double *Kth) {
     if (!h || !h->P.prox) return LMPC_ERR_BADARG;
     cp(Hinv, h->P.Hinv); cp(x0f, h->P.x0f); cp(Xthf, h->P.Xthf); cp(Kth, h->P.Kth);
@@ -1326,6 +1339,12 @@ int lmpc_set_option(lmpc_handle *h, const char *name, int value) {
     }
     if (std::strcmp(name, "sens_force_list") == 0) { h->sensForceList = value != 0; return LMPC_OK; }
     if (std::strcmp(name, "sens_reserve") == 0) { h->sensReserve = value != 0; return LMPC_OK; }
+    if (std::strcmp(name, "pack_grad_slab") == 0) {
+        if (value != 0 && (value < 8 || value > 20)) return fail(h, LMPC_ERR_BADARG, "lmpc_set_option: pack_grad_slab must be 0 or 8 .. 20");
+        h->packGradSlab = value;
+        return LMPC_OK;
+    }
+    if (std::strcmp(name, "pack_grad_reserve") == 0) { h->packGradReserve = value != 0; return LMPC_OK; }
     if (std::strcmp(name, "avi_tiers_first") == 0) {
         h->aviTiersFirst = value < 0 ? -1 : (value > 3 ? 3 : value); h->aviTiersOcc[0] = 0; return LMPC_OK;
     }
@@ -1347,6 +1366,7 @@ int lmpc_reserve(lmpc_handle *h, int64_t N, void *stream) {
     LMPC_ENTER_DEVICE(h);
     hipStream_t st = (hipStream_t)stream;
     if (h->sensReserve) LMPC_TRY(sens_reserve(h, N));
+    if (h->packGradReserve) LMPC_TRY(pack_grad_reserve(h, N));
     if (h->avi) return avi_reserve(h, N, st);
     if (h->useWave) {
         if (wave_screens(h, N)) { const int rc = ensure_lists(h, N, st); if (rc != LMPC_OK) return rc; }

@@ -134,6 +134,13 @@ struct lmpc_scratch {
     DevBuf<int32_t> adjStatus;
     int64_t adjCap = 0;
     size_t adjDoubles = 0;
+    // gradient with respect to the pack (lmpc_pack_grad.hip): the constants [M | Rout | du | dl] built by the first call;
+    // one slab of records [lambda | y] and statuses, its partials (one per 64 points), one sum per slab.  pgCap: the N
+    // they were sized for, pgSlabLog: log2 of the slab they were sized for (the work list is dSensList)
+    DevBuf<double> pgK, pgRec, pgPart, pgSum;
+    DevBuf<int32_t> pgSt;
+    int64_t pgCap = 0;
+    int pgSlabLog = 0;
 };
 
 struct lmpc_handle : lmpc_scratch {
@@ -248,6 +255,10 @@ struct lmpc_handle : lmpc_scratch {
     int sensCap = 0;            // tuning: CAP of the lane kernel, 5 or 8 ("sens_cap", 0 = by the rows a set of the problem reaches)
     int sensForceList = 0;      // tuning: every point with a non-empty set goes to the wavefront kernel ("sens_force_list")
     int sensReserve = 0;        // "sens_reserve": lmpc_reserve also allocates what the derivative calls need
+    // ... and the pack gradients (lmpc_pack_grad_launch_info), the four most recent calls
+    lmpc::LaunchRing<LMPC_PACK_GRAD_INFO_WORDS, 4> packGradRec;
+    int packGradSlab = 0;       // tuning: log2 of the points of a slab ("pack_grad_slab", 0 = by the scratch budget)
+    int packGradReserve = 0;    // "pack_grad_reserve": lmpc_reserve also allocates what lmpc_solve_pack_vjp_device needs
     lmpc::WaveLayout W{};
     DevBuf<double> dCw;
     DevBuf<float> dCwf;         // binary32 copy of the wave kernel's pack, built on the first f32 solve
@@ -569,6 +580,11 @@ int sens_reserve(lmpc_handle *h, int64_t N);
 int sens_refusal(lmpc_handle *h, const char *who);
 int sens_vjp_enqueue(lmpc_handle *h, int64_t N, const uint64_t *active, const int32_t *flag, const double *xbar, double *thbar,
                      int32_t *status, hipStream_t st, int *list_pass);
+// ... the derived pack [G | P | Dth | Xth | soft] of a raw pack on the host (G == nullptr: accumulated from M)
+void sens_derived_pack(int n, int m, int nth, int nout, const double *M, const double *G, const double *Dth, const double *Rout,
+                       const double *Xth, const int32_t *sense, std::vector<double> &C);
+// gradient with respect to the pack (lmpc_pack_grad.hip): its scratch for a batch of N, for lmpc_reserve
+int pack_grad_reserve(lmpc_handle *h, int64_t N);
 void scenario_preload();
 void offset_free_preload();
 

@@ -48,6 +48,14 @@ int qp_to_ldp(HostPack &P, int n, int m, int ms, int nth, int nout,
               const double *H, const double *f, const double *f_theta, const double *A,
               const double *bu, const double *bl, const double *W, const int32_t *sense,
               const double *Kfb, int nx, std::string &err);
+// ... and its exact adjoint: the gradients with respect to the transform's seven outputs (row-major, NULL = zero) give
+// those with respect to its inputs (the inputs' own layout; any may be NULL)
+struct LdpBars { const double *M, *du, *dl, *Dth, *Rout, *x0, *Xth; };
+struct QpBars { double *H, *f, *fth, *A, *bu, *bl, *W, *Kfb; };
+int qp_to_ldp_vjp(int n, int m, int ms, int nth, int nout,
+                  const double *H, const double *f, const double *f_theta, const double *A,
+                  const double *bu, const double *bl, const double *W, const int32_t *sense,
+                  const double *Kfb, int nx, const LdpBars &in, const QpBars &out, std::string &err);
 
 // The same boundary for a NON-symmetric H with H + H' positive definite (several objectives: reference
 // mpc2mpqp.jl:900-950; setup.jl:13 is_avi): fills the AVI pack (see HostPack).  LMPC_ERR_NONCONVEX if the symmetric

@@ -194,6 +194,13 @@ int sens_ensure(lmpc_handle *h, int64_t N) {
 
 int sens_refusal(lmpc_handle *h, const char *who) { return sens_refuse(h, who); }
 
+void sens_derived_pack(int n, int m, int nth, int nout, const double *M, const double *G, const double *Dth, const double *Rout,
+                       const double *Xth, const int32_t *sense, std::vector<double> &C) {
+    SensDims d;
+    d.m = m; d.nth = nth; d.nout = nout; d.words = (2 * m + 63) / 64;
+    sens_build_pack(n, d, M, G, Dth, Rout, Xth, sense, C);
+}
+
 int sens_vjp_enqueue(lmpc_handle *h, int64_t N, const uint64_t *active, const int32_t *flag, const double *xbar, double *thbar,
                      int32_t *status, hipStream_t st, int *list_pass) {
     // (a sweep's VJPs are not the caller's derivative calls: lmpc_sens_launch_info keeps showing those)

@@ -254,6 +254,40 @@ int qp_to_prox(HostPack &P, int n, int m, int ms, int nth, int nout,
     return LMPC_OK;
 }
 
+// Upper Cholesky factor of (H + H') / 2 = R'R (H column-major) and Rinv = R^-1, both row-major: shared by the transform
+// and its adjoint
+static int chol_upper_inverse(const double *H, int n, std::vector<double> &R, std::vector<double> &Rinv, std::string &err) {
+    // upper Cholesky factor of the symmetrised Hessian, H = R'R (codegen.jl:242)
+    R.assign((size_t)n * n, 0.0);
+    auto Hs = [&](int i, int j) { return 0.5 * (H[i + (size_t)n * j] + H[j + (size_t)n * i]); };
+    for (int i = 0; i < n; i++) {
+        double d = Hs(i, i);
+        for (int k = 0; k < i; k++) d -= R[(size_t)k * n + i] * R[(size_t)k * n + i];
+        if (!(d > 0.0) || !std::isfinite(d)) {
+            err = "lmpc_setup: Hessian is not positive definite";
+            return LMPC_ERR_NONCONVEX;
+        }
+        const double rii = std::sqrt(d);
+        R[(size_t)i * n + i] = rii;
+        for (int j = i + 1; j < n; j++) {
+            double s = Hs(i, j);
+            for (int k = 0; k < i; k++) s -= R[(size_t)k * n + i] * R[(size_t)k * n + j];
+            R[(size_t)i * n + j] = s / rii;
+        }
+    }
+    // Rinv = R^-1 (upper triangular), column by column
+    Rinv.assign((size_t)n * n, 0.0);
+    for (int c = 0; c < n; c++) {
+        Rinv[(size_t)c * n + c] = 1.0 / R[(size_t)c * n + c];
+        for (int i = c - 1; i >= 0; i--) {
+            double s = 0.0;
+            for (int k = i + 1; k <= c; k++) s -= R[(size_t)i * n + k] * Rinv[(size_t)k * n + c];
+            Rinv[(size_t)i * n + c] = s / R[(size_t)i * n + i];
+        }
+    }
+    return LMPC_OK;
+}
+
 int qp_to_ldp(HostPack &P, int n, int m, int ms, int nth, int nout,
               const double *H, const double *f, const double *f_theta, const double *A,
               const double *bu, const double *bl, const double *W, const int32_t *sense,
@@ -274,33 +308,11 @@ int qp_to_ldp(HostPack &P, int n, int m, int ms, int nth, int nout,
               "lmpc_setup_ex takes the flag DAQP.setup takes); the LDP transform does not apply";
         return LMPC_ERR_UNSUPPORTED;
     }
-    // upper Cholesky factor of the symmetrised Hessian, H = R'R (codegen.jl:242)
-    std::vector<double> R((size_t)n * n, 0.0);
-    auto Hs = [&](int i, int j) { return 0.5 * (H[i + (size_t)n * j] + H[j + (size_t)n * i]); };
-    for (int i = 0; i < n; i++) {
-        double d = Hs(i, i);
-        for (int k = 0; k < i; k++) d -= R[(size_t)k * n + i] * R[(size_t)k * n + i];
-        if (!(d > 0.0) || !std::isfinite(d)) {
-            err = "lmpc_setup: Hessian is not positive definite";
-            return LMPC_ERR_NONCONVEX;
-        }
-        const double rii = std::sqrt(d);
-        R[(size_t)i * n + i] = rii;
-        for (int j = i + 1; j < n; j++) {
-            double s = Hs(i, j);
-            for (int k = 0; k < i; k++) s -= R[(size_t)k * n + i] * R[(size_t)k * n + j];
-            R[(size_t)i * n + j] = s / rii;
-        }
-    }
-    // Rinv = R^-1 (upper triangular), column by column
-    std::vector<double> Rinv((size_t)n * n, 0.0);
-    for (int c = 0; c < n; c++) {
-        Rinv[(size_t)c * n + c] = 1.0 / R[(size_t)c * n + c];
-        for (int i = c - 1; i >= 0; i--) {
-            double s = 0.0;
-            for (int k = i + 1; k <= c; k++) s -= R[(size_t)i * n + k] * Rinv[(size_t)k * n + c];
-            Rinv[(size_t)i * n + c] = s / R[(size_t)i * n + i];
-        }
+    // upper Cholesky factor of the symmetrised Hessian, H = R'R (codegen.jl:242), and Rinv = R^-1
+    std::vector<double> R, Rinv;
+    {
+        const int rc = chol_upper_inverse(H, n, R, Rinv, err);
+        if (rc != LMPC_OK) return rc;
     }
     // Mext = [I_ms; A] * Rinv  (codegen.jl:243); simple rows are rows of Rinv
     P.M.assign((size_t)m * n, 0.0);
@@ -369,6 +381,160 @@ int qp_to_ldp(HostPack &P, int n, int m, int ms, int nth, int nout,
         }
     }
     return finish_pack(P, err);
+}
+
+// With C = Rinv, Z = C C' = H^-1, E = [I_ms; A], S = the first nout rows of I and s_j the norm of row j of E C, the
+// transform above is  M = (E C) / s,  Dth = (W + E Z f_theta) / s,  du, dl = (bu, bl + E Z f) / s,  Rout = S C,
+// x0 = -S Z f,  Xth = -S Z f_theta - [K 0].  Its adjoint, term by term (sym(X) = (X + X') / 2):
+//     dot_j = Mbar_j . M_j + Dthbar_j . Dth_j + dubar_j du_j + dlbar_j dl_j
+//     M0bar_j = (Mbar_j - M_j dot_j) / s_j     Wbar = Dthbar / s     bubar = dubar / s     blbar = dlbar / s
+//     Phi = E' Wbar - S' Xthbar     phi = E' (bubar + blbar) - S' x0bar
+//     fthbar = Z Phi     fbar = Z phi     Zbar = Phi f_theta' + phi f'
+//     Cbar = triu(E' M0bar + S' Routbar)     T = C' Cbar     U = striu(T) + diag(T) / 2
+//     Hbar = -Z sym(Zbar) Z - C sym(U) C'
+//     Abar = M0bar[ms:] C' + Wbar[ms:] (Z f_theta)' + (bubar + blbar)[ms:] (Z f)'     Kbar = -Xthbar[:, :nx]
+// (rows with s_j = 0 are not scaled by the transform and pass through unscaled here)
+int qp_to_ldp_vjp(int n, int m, int ms, int nth, int nout,
+                  const double *H, const double *f, const double *f_theta, const double *A,
+                  const double *bu, const double *bl, const double *W, const int32_t *sense,
+                  const double *Kfb, int nx, const LdpBars &in, const QpBars &out, std::string &err) {
+    HostPack P;
+    int rc = qp_to_ldp(P, n, m, ms, nth, nout, H, f, f_theta, A, bu, bl, W, sense, Kfb, nx, err);
+    if (rc != LMPC_OK) return rc;
+    std::vector<double> R, C;
+    rc = chol_upper_inverse(H, n, R, C, err);
+    if (rc != LMPC_OK) return rc;
+    const int mg = m - ms;
+    const size_t N = (size_t)n;
+    auto at = [](const double *p, size_t i) { return p ? p[i] : 0.0; };
+    std::vector<double> E((size_t)m * n, 0.0), Z(N * N, 0.0);
+    for (int i = 0; i < ms; i++) E[(size_t)i * n + i] = 1.0;
+    for (int g = 0; g < mg; g++)
+        for (int c = 0; c < n; c++) E[(size_t)(ms + g) * n + c] = A[g + (size_t)mg * c];
+    for (int i = 0; i < n; i++)
+        for (int j = 0; j < n; j++) {
+            double s = 0.0;
+            for (int k = (i > j ? i : j); k < n; k++) s += C[i * N + k] * C[j * N + k];
+            Z[i * N + j] = s;
+        }
+    std::vector<double> M0b((size_t)m * n, 0.0), Wb((size_t)m * nth, 0.0), bub(m, 0.0), blb(m, 0.0), shb(m, 0.0);
+    for (int j = 0; j < m; j++) {
+        double nrm2 = 0.0;
+        for (int k = 0; k < n; k++) {
+            double s = 0.0;
+            for (int c = 0; c <= k; c++) s += E[(size_t)j * n + c] * C[c * N + k];
+            nrm2 += s * s;
+        }
+        const double sj = std::sqrt(nrm2);
+        const bool scaled = sj > 0.0;
+        double dot = 0.0;
+        if (scaled) {
+            for (int k = 0; k < n; k++) dot += at(in.M, (size_t)j * n + k) * P.M[(size_t)j * n + k];
+            for (int t = 0; t < nth; t++) dot += at(in.Dth, (size_t)j * nth + t) * P.Dth[(size_t)j * nth + t];
+            dot += at(in.du, j) * P.du0[j] + at(in.dl, j) * P.dl0[j];
+        }
+        const double r = scaled ? 1.0 / sj : 1.0;
+        for (int k = 0; k < n; k++) M0b[(size_t)j * n + k] = (at(in.M, (size_t)j * n + k) - P.M[(size_t)j * n + k] * dot) * r;
+        for (int t = 0; t < nth; t++) Wb[(size_t)j * nth + t] = at(in.Dth, (size_t)j * nth + t) * r;
+        bub[j] = at(in.du, j) * r;
+        blb[j] = at(in.dl, j) * r;
+        shb[j] = bub[j] + blb[j];
+    }
+    std::vector<double> Phi(N * nth, 0.0), phi(n, 0.0);
+    for (int c = 0; c < n; c++) {
+        for (int t = 0; t < nth; t++) {
+            double s = c < nout ? -at(in.Xth, (size_t)c * nth + t) : 0.0;
+            for (int j = 0; j < m; j++) s += E[(size_t)j * n + c] * Wb[(size_t)j * nth + t];
+            Phi[c * (size_t)nth + t] = s;
+        }
+        double s = c < nout ? -at(in.x0, c) : 0.0;
+        for (int j = 0; j < m; j++) s += E[(size_t)j * n + c] * shb[j];
+        phi[c] = s;
+    }
+    // Z f_theta and Z f (rows of Abar), fthbar = Z Phi, fbar = Z phi
+    std::vector<double> Zft(N * nth, 0.0), Zf(n, 0.0);
+    for (int i = 0; i < n; i++) {
+        double sf = 0.0, sb = 0.0;
+        for (int c = 0; c < n; c++) { sf += Z[i * N + c] * at(f, c); sb += Z[i * N + c] * phi[c]; }
+        Zf[i] = sf;
+        if (out.f) out.f[i] = sb;
+        for (int t = 0; t < nth; t++) {
+            double s = 0.0, q = 0.0;
+            for (int c = 0; c < n; c++) {
+                s += Z[i * N + c] * at(f_theta, c + N * t);
+                q += Z[i * N + c] * Phi[c * (size_t)nth + t];
+            }
+            Zft[i * (size_t)nth + t] = s;
+            if (out.fth) out.fth[i + N * t] = q;
+        }
+    }
+    if (out.H) {
+        // X = sym(Zbar), Y = sym(U); Hbar = -Z X Z - C Y C'
+        std::vector<double> X(N * N, 0.0), Y(N * N, 0.0), T1(N * N, 0.0), T2(N * N, 0.0);
+        for (int i = 0; i < n; i++)
+            for (int j = 0; j < n; j++) {
+                double s = phi[i] * at(f, j);
+                for (int t = 0; t < nth; t++) s += Phi[i * (size_t)nth + t] * at(f_theta, j + N * t);
+                T1[i * N + j] = s;
+            }
+        for (int i = 0; i < n; i++)
+            for (int j = 0; j < n; j++) X[i * N + j] = 0.5 * (T1[i * N + j] + T1[j * N + i]);
+        // Cbar (upper) into T1, T = C' Cbar into T2
+        for (int i = 0; i < n; i++)
+            for (int k = 0; k < n; k++) {
+                double s = 0.0;
+                if (i <= k) {
+                    s = i < nout ? at(in.Rout, (size_t)i * n + k) : 0.0;
+                    for (int j = 0; j < m; j++) s += E[(size_t)j * n + i] * M0b[(size_t)j * n + k];
+                }
+                T1[i * N + k] = s;
+            }
+        for (int a = 0; a < n; a++)
+            for (int b = 0; b < n; b++) {
+                double s = 0.0;
+                for (int i = 0; i <= a && i <= b; i++) s += C[i * N + a] * T1[i * N + b];
+                T2[a * N + b] = s;
+            }
+        for (int a = 0; a < n; a++)
+            for (int b = 0; b < n; b++) {
+                const double uab = a < b ? T2[a * N + b] : a == b ? 0.5 * T2[a * N + a] : 0.0;
+                const double uba = b < a ? T2[b * N + a] : a == b ? 0.5 * T2[a * N + a] : 0.0;
+                Y[a * N + b] = 0.5 * (uab + uba);
+            }
+        auto mul = [&](const std::vector<double> &L, const std::vector<double> &Rm, bool rt, std::vector<double> &O) {
+            for (int i = 0; i < n; i++)
+                for (int j = 0; j < n; j++) {
+                    double s = 0.0;
+                    for (int k = 0; k < n; k++) s += L[i * N + k] * (rt ? Rm[j * N + k] : Rm[k * N + j]);
+                    O[i * N + j] = s;
+                }
+        };
+        mul(Z, X, false, T1);
+        mul(T1, Z, false, T2);         // Z X Z
+        mul(C, Y, false, T1);
+        mul(T1, C, true, X);           // C Y C'
+        for (int i = 0; i < n; i++)
+            for (int j = 0; j < n; j++)          // (symmetric to the last bit: the two halves of each product sum are averaged)
+                out.H[i + N * j] = -0.5 * ((T2[i * N + j] + X[i * N + j]) + (T2[j * N + i] + X[j * N + i]));
+    }
+    if (out.A)
+        for (int g = 0; g < mg; g++)
+            for (int c = 0; c < n; c++) {
+                const size_t j = (size_t)ms + g;
+                double s = shb[j] * Zf[c];
+                for (int k = c; k < n; k++) s += M0b[j * n + k] * C[c * N + k];
+                for (int t = 0; t < nth; t++) s += Wb[j * nth + t] * Zft[c * (size_t)nth + t];
+                out.A[g + (size_t)mg * c] = s;
+            }
+    for (int j = 0; j < m; j++) {
+        if (out.bu) out.bu[j] = bub[j];
+        if (out.bl) out.bl[j] = blb[j];
+        if (out.W) for (int t = 0; t < nth; t++) out.W[j + (size_t)m * t] = Wb[(size_t)j * nth + t];
+    }
+    if (out.Kfb)
+        for (int k = 0; k < nout; k++)
+            for (int t = 0; t < nx; t++) out.Kfb[k + (size_t)nout * t] = -at(in.Xth, (size_t)k * nth + t);
+    return LMPC_OK;
 }
 
 }  // namespace lmpc

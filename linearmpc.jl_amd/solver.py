@@ -133,6 +133,67 @@ def sens_host(pack, active, exitflag, xbar=None, settings: Settings | None = Non
     return out, status
 
 
+PACK_BARS = ("M", "du", "dl", "Dth", "Rout", "x0", "Xth")
+
+
+def _pack_bar_shapes(n, m, nth, nout):
+    return dict(M=(m, n), du=(m,), dl=(m,), Dth=(m, nth), Rout=(nout, n), x0=(nout,), Xth=(nout, nth))
+
+
+def pack_vjp_host(pack, theta, active, exitflag, xbar, settings: Settings | None = None, is_avi=False, want=PACK_BARS):
+    """`lmpc_solve_pack_vjp_host`: the gradient of sum_p <xbar_p, x*_p> with respect to the LDP pack, summed over the
+    batch, on the CPU from a raw pack (a dict as `BatchedQP.ldp()` / `transform` return it).  Returns a dict with the
+    arrays named in `want` (of M, du, dl, Dth, Rout, x0, Xth; the others are passed as NULL), thbar (N, nth) and status."""
+    n, m, ms, nth, nout = (int(pack[k]) for k in ("n", "m", "ms", "nth", "nout"))
+    shapes = _pack_bar_shapes(n, m, nth, nout)
+    arrs = [_f64(np.asarray(pack[k], float).reshape(shapes[k])) for k in PACK_BARS]
+    sense = np.ascontiguousarray(pack["sense"], dtype=np.int32).reshape(m)
+    words = (2 * m + 63) // 64
+    act = np.ascontiguousarray(np.asarray(active, np.uint64).reshape(-1, words))
+    N = act.shape[0]
+    ef = np.ascontiguousarray(np.asarray(exitflag, np.int32).reshape(N))
+    th = _f64(np.asarray(theta, float).reshape(N, nth))
+    xb = _f64(np.asarray(xbar, float).reshape(N, nout))
+    out = {k: np.full(shapes[k], np.nan) for k in PACK_BARS if k in want}
+    out["thbar"], out["status"] = np.zeros((N, nth)), np.zeros(N, np.int32)
+    sp = ctypes.cast(ctypes.pointer(settings), _vp) if settings is not None else None
+    check(lib().lmpc_solve_pack_vjp_host(n, m, ms, nth, nout, *[_ptr(a) for a in arrs], _ptr(sense), sp, int(bool(is_avi)), N,
+                                         _ptr(th), _ptr(act), _ptr(ef), _ptr(xb), *[_ptr(out.get(k)) for k in PACK_BARS],
+                                         _ptr(out["thbar"]), _ptr(out["status"])))
+    return out
+
+
+def transform_vjp(H, f, f_theta, A, bu, bl, W, bars, senses=None, nout=None, K=None, nx=0):
+    """`lmpc_transform_vjp`: the adjoint of `transform`.  bars: dict of gradients with respect to the transform's outputs
+    (row-major M, du, dl, Dth, Rout, x0, Xth; a missing one counts as zero).  Returns a dict with the gradients H
+    (symmetric), f, f_theta, A, bu, bl, W and K (nout x nx; None without a K)."""
+    H = _f64(H, "F")
+    n = H.shape[0]
+    f_theta = _f64(np.asarray(f_theta, float).reshape(n, -1), "F")
+    nth = f_theta.shape[1]
+    bu = _f64(np.asarray(bu, float).reshape(-1))
+    bl = _f64(np.asarray(bl, float).reshape(-1))
+    m = bu.size
+    A = _f64(np.asarray(A, float).reshape(-1, n), "F")
+    mg = A.shape[0]
+    ms = m - mg
+    W = _f64(np.asarray(W, float).reshape(m, nth), "F")
+    f = _f64(np.zeros(n) if f is None else np.asarray(f, float).reshape(n))
+    nout = n if nout is None else int(nout)
+    sense = np.ascontiguousarray(np.zeros(m, np.int32) if senses is None else senses, dtype=np.int32)
+    Kf = None if K is None else _f64(np.asarray(K, float).reshape(nout, -1), "F")
+    nx = int(nx if K is not None else 0)
+    shapes = _pack_bar_shapes(n, m, nth, nout)
+    ins = [None if bars.get(k) is None else _f64(np.asarray(bars[k], float).reshape(shapes[k])) for k in PACK_BARS]
+    out = dict(H=np.zeros((n, n), order="F"), f=np.zeros(n), f_theta=np.zeros((n, nth), order="F"),
+               A=np.zeros((mg, n), order="F"), bu=np.zeros(m), bl=np.zeros(m), W=np.zeros((m, nth), order="F"),
+               K=None if K is None else np.zeros((nout, nx), order="F"))
+    check(lib().lmpc_transform_vjp(n, m, ms, nth, nout, _ptr(H), _ptr(f), _ptr(f_theta), _ptr(A), _ptr(bu), _ptr(bl), _ptr(W),
+                                   _ptr(sense), _ptr(Kf) if Kf is not None else None, nx, *[_ptr(a) for a in ins],
+                                   *[_ptr(out[k]) for k in ("H", "f", "f_theta", "A", "bu", "bl", "W", "K")]))
+    return out
+
+
 def scenario_vjp_host(pack, sim, active, flag, Xbar=None, Ubar=None, observer=None, xhat_given=False,
                       settings: Settings | None = None, is_avi=False, want=("r", "d", "p")):
     """`lmpc_scenario_vjp_host`: the backward sweep of a taped scenario run on the CPU, no GPU and no handle.  pack: a raw
@@ -257,6 +318,66 @@ def _autograd_fn():
 
     _AUTOGRAD_FN = SolveFunction
     return SolveFunction
+
+
+_MPQP_FN = None
+
+
+def _mpqp_fn():
+    """The torch.autograd.Function of `solve_mpqp_autograd` (made on first use)."""
+    global _MPQP_FN
+    if _MPQP_FN is not None:
+        return _MPQP_FN
+    import torch
+
+    class SolveMpqpFunction(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, kw, H, f, f_theta, A, bu, bl, W, K, theta):
+            host = lambda t: None if t is None else t.detach().cpu().numpy().astype(np.float64)
+            data = [host(t) for t in (H, f, f_theta, A, bu, bl, W)]
+            qp = BatchedQP.from_mpqp(*data, senses=kw["senses"], nout=kw["nout"], K=host(K), nx=kw["nx"],
+                                     settings=kw["settings"], device=kw["device"])
+            th = theta.detach().contiguous()
+            active = torch.empty((th.shape[0], qp.words), dtype=torch.int64, device=th.device)
+            x, ef = qp.solve_device(th, active=active)
+            ctx.qp, ctx.kw, ctx.data, ctx.K = qp, kw, data, host(K)
+            ctx.like = [None if t is None else (tuple(t.shape), t.dtype, t.device) for t in (H, f, f_theta, A, bu, bl, W, K)]
+            ctx.sens_status = None
+            ctx.save_for_backward(th, active, ef)
+            ctx.mark_non_differentiable(ef)
+            return x, ef
+
+        @staticmethod
+        def backward(ctx, xbar, _efbar):
+            th, active, ef = ctx.saved_tensors
+            need = ctx.needs_input_grad[1:9]
+            # (with nothing but theta requiring grad no sum is asked for: the call is then stage 1 alone, the VJP's work)
+            g = ctx.qp.solve_pack_vjp_device(th, active, ef, xbar.contiguous(), want_thbar=True,
+                                             want=PACK_BARS if any(need) else ())
+            ctx.sens_status = g["status"]
+            grads = [None] * 8
+            if any(need):
+                bars = {k: g[k].cpu().numpy() for k in PACK_BARS}          # the one download of the G doubles
+                kw = ctx.kw
+                d = transform_vjp(*ctx.data, bars, senses=kw["senses"], nout=kw["nout"], K=ctx.K, nx=kw["nx"])
+                for q, name in enumerate(("H", "f", "f_theta", "A", "bu", "bl", "W", "K")):
+                    if need[q] and ctx.like[q] is not None and d[name] is not None:
+                        shape, dtype, device = ctx.like[q]
+                        grads[q] = torch.as_tensor(np.ascontiguousarray(d[name]), dtype=dtype, device=device).reshape(shape)
+            return (None, *grads, g["thbar"] if ctx.needs_input_grad[9] else None)
+
+    _MPQP_FN = SolveMpqpFunction
+    return SolveMpqpFunction
+
+
+def solve_mpqp_autograd(H, f, f_theta, A, bu, bl, W, theta, senses=None, nout=None, K=None, nx=0, settings=None, device=0):
+    """The batched solve of an mpQP given as torch tensors, inside a torch graph: returns (x, exitflag), x carrying the
+    gradient with respect to whichever of H, f, f_theta, A, bu, bl, W, K and theta require grad.  Forward: `from_mpqp`
+    on the tensors' values, then `solve_device` with the masks kept.  Backward: ONE `solve_pack_vjp_device` (with thbar),
+    one download of the summed pack gradient, `transform_vjp` on the host.  theta: (N, nth) float64 CUDA tensor on
+    `device`; the data tensors may live anywhere.  The status of the backward is `x.grad_fn.sens_status`."""
+    kw = dict(senses=senses, nout=nout, nx=int(nx), settings=settings, device=int(device))
+    return _mpqp_fn().apply(kw, H, f, f_theta, A, bu, bl, W, K, theta)
 
 
 class BatchedQP:
@@ -1482,6 +1603,68 @@ class BatchedQP:
         out, status = np.zeros((N, self.nout, self.nth)), np.zeros(N, np.int32)
         check(lib().lmpc_solve_jacobian(self._h, N, _ptr(act), _ptr(ef), _ptr(out), _ptr(status)), self._h)
         return out, status
+
+    # ------------------------------------------------------------------ gradient with respect to the pack
+    PACK_GRAD_LAUNCH_FIELDS = ("seq", "CAP", "cap", "grid", "lds", "staged", "list_pass", "wave_grid", "reduce_grid",
+                               "reduce_lds", "slab", "slabs", "tree_launches", "scratch_kib", "doubles", "nprob", "reduce_chunks")
+
+    def pack_grad_launch_info(self, since=0):
+        """The handle's most recent pack-gradient calls (lmpc_pack_grad_launch_info; at most four are kept), oldest
+        first: CAP / cap of the pack_grad_lane_kernel, its grid on the first slab and LDS bytes, staged (bit 0: the derived
+        pack in the lane kernel's LDS, bit 1: M and Rout in the reduce kernel's), list_pass and wave_grid of
+        pack_grad_wave_kernel, the reduce kernel's grid and LDS bytes, slab (log2 of its points), slabs, the tree
+        kernel's launches, the scratch in KiB, the doubles of one partial, nprob, reduce_chunks (the column chunks of M
+        the reduce kernel's grid was split into on the first slab)."""
+        W = len(self.PACK_GRAD_LAUNCH_FIELDS)
+        out = (ctypes.c_int32 * (4 * W))()
+        k = lib().lmpc_pack_grad_launch_info(self._h, out, 4)
+        if k < 0:
+            check(k, self._h)
+        recs = [dict(zip(self.PACK_GRAD_LAUNCH_FIELDS, (int(v) for v in out[q * W:(q + 1) * W]))) for q in range(k)]
+        return [r for r in recs if r["seq"] > since]
+
+    def solve_pack_vjp_device(self, theta, active, exitflag, xbar, want_thbar=False, status=None, stream=None, out=None,
+                              want=PACK_BARS, thbar=None):
+        """`lmpc_solve_pack_vjp_device`: the gradient of sum_p <xbar_p, x*_p> with respect to the pack, summed over the
+        batch (CUDA tensors; theta (N, nth), xbar (N, nout) float64).  Enqueued on `stream` (default: torch's current
+        stream), not synchronised.  Returns a dict of device tensors M, du, dl, Dth, Rout, x0, Xth (those named in `want`;
+        `out` may hold preallocated ones), status, and thbar (N, nth) with `want_thbar` (or a preallocated `thbar`)."""
+        import torch
+        N, dev, pa, pf, status, ps = self._sens_device_args(active, exitflag, status)
+        shapes = _pack_bar_shapes(self.n, self.m, self.nth, self.nout)
+        res = {}
+        for k in PACK_BARS:
+            if k in want:
+                t = None if out is None else out.get(k)
+                res[k] = torch.empty(shapes[k], dtype=torch.float64, device=dev) if t is None else t
+        ptrs = [_dev_arg(res.get(k), k + "bar", torch.float64, int(np.prod(shapes[k])), self.device) if res.get(k) is not None
+                and res[k].numel() else None for k in PACK_BARS]
+        if thbar is None and want_thbar:
+            thbar = torch.empty((N, self.nth), dtype=torch.float64, device=dev)
+        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        check(lib().lmpc_solve_pack_vjp_device(
+            self._h, N, _dev_arg(theta, "theta", torch.float64, N * self.nth, self.device, False), pa, pf,
+            _dev_arg(xbar, "xbar", torch.float64, N * self.nout, self.device, False), *ptrs,
+            _dev_arg(thbar, "thbar", torch.float64, N * self.nth, self.device), ps, _vp(st)), self._h)
+        res["status"] = status
+        if thbar is not None:
+            res["thbar"] = thbar
+        return res
+
+    def solve_pack_vjp(self, theta, active, exitflag, xbar, want=PACK_BARS):
+        """Host arrays in and out (`lmpc_solve_pack_vjp`; synchronous): dict with the arrays named in `want`, thbar and
+        status."""
+        act = np.ascontiguousarray(np.asarray(active, np.uint64).reshape(-1, self.words))
+        N = act.shape[0]
+        ef = np.ascontiguousarray(np.asarray(exitflag, np.int32).reshape(N))
+        th = _f64(np.asarray(theta, float).reshape(N, self.nth))
+        xb = _f64(np.asarray(xbar, float).reshape(N, self.nout))
+        shapes = _pack_bar_shapes(self.n, self.m, self.nth, self.nout)
+        out = {k: np.full(shapes[k], np.nan) for k in PACK_BARS if k in want}
+        out["thbar"], out["status"] = np.zeros((N, self.nth)), np.zeros(N, np.int32)
+        check(lib().lmpc_solve_pack_vjp(self._h, N, _ptr(th), _ptr(act), _ptr(ef), _ptr(xb), *[_ptr(out.get(k)) for k in PACK_BARS],
+                                        _ptr(out["thbar"]), _ptr(out["status"])), self._h)
+        return out
 
     def solve_autograd(self, theta):
         """The batched solve inside a torch graph: returns (x, exitflag) with x = x*(theta) carrying the gradient
