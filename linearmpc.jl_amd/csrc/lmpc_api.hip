@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "lmpc_internal.hpp"
+#include "lmpc_fast_kernel.hpp"
 #include "lmpc_lane_kernel.hpp"
 #include "lmpc_screen_kernel.hpp"
 #include "lmpc_simrun_kernel.hpp"
@@ -68,7 +69,9 @@ void fill_layout(lmpc_handle *h) {
     o = (o + 7) & ~7;
     L.oXthP = o; o += P.nout * L.nthp;
     o = (o + 7) & ~7;
-    L.oFG = o; o += 32 * 32 + 32 * kMaxSimU;           // closed loop: F (nx <= 32) and G (nu <= kMaxSimU)
+    L.oFG = o; o += kPackFG;                           // closed loop: F (nx <= 32) and G (nu <= kMaxSimU)
+    // the one-launch kernel's constants once more, as the image its workgroups load (lmpc_fast_kernel.hpp)
+    if (fast_image_wanted(N, P.n, P.m, P.ms, P.nth)) o = fast_image_offset(L.oFG) + fast_image_doubles(N, L.nthp);
     h->nC = (size_t)o;
     L.imm_mask = 0; L.eq_mask = 0;
     for (int j = 0; j < P.m && j < 64; j++) {
@@ -235,6 +238,7 @@ int finalize_handle(lmpc_handle *h) {
         for (int k = 0; k < P.nout; k++)
             for (int t = 0; t < P.nth; t++) buf[L.oXthP + k * L.nthp + t] = P.Xth[(size_t)k * P.nth + t];
     }
+    if (fast_image_wanted(N, P.n, P.m, P.ms, P.nth)) fast_image_fill(buf.data(), L, N);
     HIP_TRY(h, h->dC.reserve(h->nC ? h->nC : 1));
     HIP_TRY(h, hipMemcpy(h->dC, buf.data(), sizeof(double) * h->nC, hipMemcpyHostToDevice));
     return LMPC_OK;

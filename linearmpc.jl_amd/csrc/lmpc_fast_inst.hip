@@ -51,7 +51,7 @@ static void fast_record(lmpc_handle *h, int form, bool stage, int Rq, int nstr, 
 static hipError_t fast_err_word(lmpc_handle *h, hipStream_t st) {
     if (h->dFastErr) return hipSuccess;
 #ifdef LMPC_FAST_TRACE
-    const size_t eb = 64 + sizeof(long long) * 8 * 4 * 65536;
+    const size_t eb = 64 + sizeof(long long) * kFastTraceSlots * 4 * 65536;
     hipError_t e = h->dFastTrace.reserve(eb / sizeof(int32_t));
     if (e == hipSuccess) e = hipMemsetAsync(h->dFastTrace, 0, eb, st);
     if (e == hipSuccess) h->dFastErr = h->dFastTrace;
@@ -149,7 +149,7 @@ static int launch_fast_t(lmpc_handle *h, const PackLayout &L, int64_t nprob, con
     fast_record(h, GATHER ? 1 : 0, stage, Rq, nstr, dk, grid, 1, lds, D);
 #ifdef LMPC_FAST_TRACE
     if (const char *f = std::getenv("LMPC_FAST_TRACE_FILE")) {
-        std::vector<long long> tr((size_t)grid * 4 * 8);
+        std::vector<long long> tr((size_t)grid * 4 * kFastTraceSlots);
         if (hipStreamSynchronize(st) == hipSuccess &&
             hipMemcpy(tr.data(), reinterpret_cast<char *>(h->dFastErr) + 64, sizeof(long long) * tr.size(), hipMemcpyDeviceToHost) == hipSuccess) {
             if (FILE *fp = std::fopen(f, "wb")) { std::fwrite(tr.data(), sizeof(long long), tr.size(), fp); std::fclose(fp); }

@@ -45,6 +45,7 @@ namespace lmpc {
 #endif
 constexpr int kFastGridWaves = 3;         // workgroups per CU the default grid is sized for (launch_fast_t)
 constexpr int kFastSpinLimit = 1 << 22;
+constexpr int kFastTraceSlots = 9;         // (-DLMPC_FAST_TRACE) words of a wavefront's trace record: stamps 0 .. 6, where it ran, entry
 constexpr int kFastCtrs = 16;              // ticket counters of the dynamic tail (a power of two)
 constexpr int kFastMaxTiles = 96;          // tiles of 64 problems per workgroup at most (LDS queue: 256 bytes per tile)
 #ifndef LMPC_FAST_AHEAD
@@ -79,6 +80,33 @@ __device__ __forceinline__ int lds_load(const int *p) {
 // doubles of the screening constants kept in LDS: rows of Dth padded to NTHMAX columns, (du, dl) pairs, the first
 // output's row of Xth, x0 of the first output (+ padding to an even count)
 __host__ __device__ constexpr int fast_scr_doubles(int N, int NTHMAX) { return (N * NTHMAX + 2 * N + NTHMAX + 1 + 1) & ~1; }
+// doubles of M, G, du0, dl0 at the front of LDS (m == n == N; padded to an even count)
+__host__ __device__ constexpr int fast_const_doubles(int N) { return (N * N + N * (N + 1) / 2 + 2 * N + 1) & ~1; }
+// THE CONSTANTS AS ONE IMAGE.  What a workgroup keeps at the front of LDS -- the two blocks above -- lies in the handle's
+// constant pack a second time, contiguous and in LDS order, right behind the closed loop's F / G block (fill_layout
+// appends it for the handles fast_covers() can accept): a staged workgroup's set-up is then ONE 16-byte load per thread
+// and one 16-byte LDS store instead of five dependent round trips through the pack's sections (see fast_body).  The
+// image's words are copies of the pack's own (fast_image_fill), so every LDS word holds the bits it held when the
+// sections were read one by one.
+__host__ __device__ constexpr int fast_image_doubles(int N, int NTHMAX) { return fast_const_doubles(N) + fast_scr_doubles(N, NTHMAX); }
+__host__ __device__ constexpr int fast_image_pieces(int N, int NTHMAX) { return fast_image_doubles(N, NTHMAX) / 2; }
+__host__ __device__ constexpr int fast_image_offset(int oFG) { return oFG + kPackFG; }   // (oFG and kPackFG: multiples of 8 doubles)
+static_assert(kPackFG % 8 == 0, "the image starts on a 64-byte boundary");
+// which packs carry the image: the sizes the kernel is instantiated for (fast_covers() narrows this by flags and settings)
+inline bool fast_image_wanted(int N, int n, int m, int ms, int nth) {
+    return N >= 2 && N <= 5 && n == N && m == N && ms == N && nth >= 1 && nth <= 16;
+}
+// the image from the sections of the pack `buf` it lies in (host; L.nthp is the kernel's NTHMAX); paddings are zero
+inline void fast_image_fill(double *buf, const PackLayout &L, int N) {
+    const int nconst = N * N + N * (N + 1) / 2 + 2 * N, NTHMAX = L.nthp;
+    double *img = buf + fast_image_offset(L.oFG), *scr = img + fast_const_doubles(N);
+    for (int i = 0; i < fast_image_doubles(N, NTHMAX); i++) img[i] = 0.0;
+    for (int i = 0; i < nconst; i++) img[i] = buf[L.oM + i];                       // M, G, du0, dl0: consecutive in the pack
+    for (int i = 0; i < N * NTHMAX; i++) scr[i] = buf[L.oDthP + i];
+    for (int i = 0; i < 2 * N; i++) scr[N * NTHMAX + i] = buf[L.oBnd + i];
+    for (int i = 0; i < NTHMAX; i++) scr[N * NTHMAX + 2 * N + i] = buf[L.oXthP + i];
+    scr[N * NTHMAX + 2 * N + NTHMAX] = buf[L.ox0];
+}
 // Hand-over of a queued problem: the streaming wavefront that found it has its shifts b_j = Dth_j . theta and the
 // output shift x0 + Xth theta in registers; the first kFastPay queue positions of a workgroup carry them in LDS next
 // to the index, so the solving wavefront starts on an LDS read instead of re-reading the record from L2 and
@@ -185,21 +213,44 @@ __device__ __forceinline__ void fast_body(
     char *dma0 = reinterpret_cast<char *>(sX + (stage ? R * 64 : 0));                  // the LDS-DMA rings, if any
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int nth = P.nth;
-    for (int i = tid; i < nconst; i += 256) sconst[i] = C[P.oM + i];
-    for (int i = tid; i < N * NTHMAX; i += 256) sScr[i] = C[P.oDthP + i];
-    if (tid < 2 * N) sScr[N * NTHMAX + tid] = C[P.oBnd + tid];
-    if (tid < NTHMAX) sScr[N * NTHMAX + 2 * N + tid] = C[P.oXthP + tid];
-    if (tid == 0) sScr[N * NTHMAX + 2 * N + NTHMAX] = C[P.ox0];
+#ifdef LMPC_FAST_TRACE
+    const long long trc_entry = (long long)wall_clock64();     // (before the first constant is asked for)
+#endif
+    // Set-up.  The staged kernels take the constants in ONE round trip: they lie in the pack once more as a contiguous
+    // image in LDS order (fast_image_fill); every thread below `pieces` asks for its 16 bytes, the queue is initialised
+    // while they travel, then they are stored -- the longer of the two, not their sum (1.8 -> 0.8 us of a workgroup's
+    // 17 us at the in-flight shape, 13.0 -> 12.6 us per step; profiles/fast_setup.md).  The other kernels copy section
+    // by section as before: with the image a call issued alone took 25.8 instead of 22.7 us on fast_kernel (measured, not
+    // explained -- the sections the solving pass reads with scalar loads are then no longer touched first), and the
+    // generated controller's kernel compiled to more scalar spills and scratch reloads in its tile loop.  Same words in the
+    // same LDS places either way.
+    constexpr bool image = STAGE;
+    constexpr int pieces = fast_image_pieces(N, NTHMAX);
+    static_assert(fast_image_doubles(N, NTHMAX) % 2 == 0, "the image is a whole number of 16-byte pieces");
+    static_assert(fast_const_doubles(N) == ((nconst + 1) & ~1), "image and LDS layout agree");
+    static_assert(pieces <= 256, "one piece per thread");
+    typedef double img2d __attribute__((ext_vector_type(2)));
+    img2d piece = {0.0, 0.0};
+    if constexpr (image) {
+        if (tid < pieces) piece = reinterpret_cast<const img2d *>(C + fast_image_offset(P.oFG))[tid];
+    } else {
+        for (int i = tid; i < nconst; i += 256) sconst[i] = C[P.oM + i];
+        for (int i = tid; i < N * NTHMAX; i += 256) sScr[i] = C[P.oDthP + i];
+        if (tid < 2 * N) sScr[N * NTHMAX + tid] = C[P.oBnd + tid];
+        if (tid < NTHMAX) sScr[N * NTHMAX + 2 * N + tid] = C[P.oXthP + tid];
+        if (tid == 0) sScr[N * NTHMAX + 2 * N + NTHMAX] = C[P.ox0];
+    }
     for (int i = tid; i < R * 64; i += 256) ring[i] = -1;
     if (tid < 4) ctrl[tid] = 0;
+    if (image && tid < pieces) reinterpret_cast<img2d *>(lds)[tid] = piece;
     __syncthreads();
     const double *sM = sconst, *sG = sM + N * N, *sdu = sG + N * (N + 1) / 2, *sdl = sdu + N;
     const double ntol = -P.primal_tol;
     const long long ntiles = (nprob + 63) / 64;
-#ifdef LMPC_FAST_TRACE      // diagnostic build: 100 MHz timestamps per wavefront into errflag[16 + 8 * wave ..]
-    long long *trc = reinterpret_cast<long long *>(errflag + 16) + ((long long)blockIdx.x * 4 + wv) * 8;
+#ifdef LMPC_FAST_TRACE      // diagnostic build: 100 MHz timestamps per wavefront, kFastTraceSlots words each, behind errflag[16]
+    long long *trc = reinterpret_cast<long long *>(errflag + 16) + ((long long)blockIdx.x * 4 + wv) * kFastTraceSlots;
     int npass = 0;
+    if (lane == 0) trc[8] = trc_entry;                         // kernel entry: stamp 0 - this = the set-up
 #define LMPC_TRC(i) do { if (lane == 0) trc[i] = (long long)wall_clock64(); } while (0)
 #else
 #define LMPC_TRC(i) do { } while (0)
@@ -236,9 +287,9 @@ __device__ __forceinline__ void fast_body(
                 dst[t] = v;
             }
         } else {
-            const double *src = theta + pc * nth;
+            const double *src = theta + pc * NT;               // NT == nth: the host dispatches on the handle's nth
 #pragma unroll
-            for (int t = 0; t < NT; t++) dst[t] = src[t];      // NT == nth (nth <= 16)
+            for (int t = 0; t < NT; t++) dst[t] = src[t];
         }
     };
     auto write_x = [&](long long pid, const double (&th)[NT], const double (&u)[N], bool with_u) {

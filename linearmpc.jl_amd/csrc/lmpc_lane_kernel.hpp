@@ -37,6 +37,7 @@ namespace lmpc {
 // the oracle's order (F's terms, then G's), the next record [x+; r; u[0:nup]], bookkeeping of the run.
 // th: this problem's current record; u: its nu outputs.  kMaxSimU bounds the outputs kept in registers.
 constexpr int kMaxSimU = 4;
+constexpr int kPackFG = 32 * 32 + 32 * kMaxSimU;          // doubles of the pack's block at PackLayout::oFG: F (nx <= 32), G (nu <= kMaxSimU)
 __device__ __forceinline__ void sim_advance(const SimFuse &S, const double *__restrict__ FGc,
                                             const double *__restrict__ th, const double *u,
                                             const long long pid, const int flag) {

@@ -18,7 +18,7 @@ torch.cuda.synchronize()
 os.environ["LMPC_FAST_TRACE_FILE"] = "/tmp/fast_trace.bin"
 x, ef = qp.solve_device(ths[0])
 torch.cuda.synchronize()
-t = np.fromfile("/tmp/fast_trace.bin", dtype=np.int64).reshape(-1, 4, 8).astype(np.float64)
+t = np.fromfile("/tmp/fast_trace.bin", dtype=np.int64).reshape(-1, 4, 9).astype(np.float64)      # (kFastTraceSlots words per wavefront)
 # rows by ROLE (role = (wave + workgroup) & 3; roles 0..2 stream, role 3 solves from the start)
 t = np.stack([np.roll(t[b], b & 3, axis=0) for b in range(t.shape[0])])
 t0 = t[:, :, 0][t[:, :, 0] > 0].min()
