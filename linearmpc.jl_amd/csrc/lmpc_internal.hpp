@@ -572,17 +572,29 @@ int api_launch_wave_f32(lmpc_handle *h, const float *dC, int64_t nprob, const fl
 void loop_preload();
 // differentiable solve (lmpc_sens.hip): derived pack and work list for a batch of N; the same for lmpc_reserve (nothing
 // on a handle the derivative calls refuse)
+struct SensDims;
+struct SensView;
 int sens_ensure(lmpc_handle *h, int64_t N);
 int sens_reserve(lmpc_handle *h, int64_t N);
-// ... what lmpc_solve_vjp* refuses of a handle (LMPC_OK, or the code with its text set), and the launches of
-// lmpc_solve_vjp_device for a caller that has passed it (the scenario adjoint, once per step); *list_pass: whether the
-// wavefront kernel's pass over the work list was enqueued
-int sens_refusal(lmpc_handle *h, const char *who);
+// ... why a handle has no derivative (nullptr: it has one) with the refusal's code, and the refusal itself
+const char *sens_no_derivative(const lmpc_handle *h, int *code);
+int sens_refuse(lmpc_handle *h, const char *who);
+// ... CAP of the lane kernels and the grid of the wavefront kernels for N points (one copy for every derivative)
+int sens_cap_of(const lmpc_handle *h);
+unsigned sens_wave_grid(const lmpc_handle *h, int64_t N);
+// ... the launches of lmpc_solve_vjp_device for a caller that has passed its refusals (the scenario adjoint, once per
+// step); *list_pass: whether the wavefront kernel's pass over the work list was enqueued
 int sens_vjp_enqueue(lmpc_handle *h, int64_t N, const uint64_t *active, const int32_t *flag, const double *xbar, double *thbar,
                      int32_t *status, hipStream_t st, int *list_pass);
-// ... the derived pack [G | P | Dth | Xth | soft] of a raw pack on the host (G == nullptr: accumulated from M)
-void sens_derived_pack(int n, int m, int nth, int nout, const double *M, const double *G, const double *Dth, const double *Rout,
-                       const double *Xth, const int32_t *sense, std::vector<double> &C);
+// ... for the _host twins: what they refuse of a raw pack (`bounds`: du and dl are there; *st: the settings in force),
+// its derived pack [G | P | Dth | Xth | soft] (G == nullptr: accumulated from M), the points' loop
+int sens_check_pack(const char *who, int n, int m, int ms, int nth, int nout, const double *M, const double *Dth, const double *Rout,
+                    const double *Xth, const int32_t *sense, bool bounds, const lmpc_settings *s, int is_avi, int64_t N,
+                    lmpc_settings *st);
+void sens_build_pack(int n, const SensDims &d, const double *M, const double *G, const double *Dth, const double *Rout,
+                     const double *Xth, const int32_t *sense, std::vector<double> &C);
+void sens_host_points(const SensView &S, const SensDims &d, bool jac, int64_t N, const uint64_t *active, const int32_t *flag,
+                      const double *xbar, double *out, int32_t *status);
 // gradient with respect to the pack (lmpc_pack_grad.hip): its scratch for a batch of N, for lmpc_reserve
 int pack_grad_reserve(lmpc_handle *h, int64_t N);
 void scenario_preload();

@@ -26,13 +26,6 @@ int pg_slab_log(const lmpc_handle *h) {
     return s;
 }
 
-// the same lane capacity as the VJP picks (lmpc_sens.hip)
-int pg_cap_of(const lmpc_handle *h) {
-    if (h->sensCap == 5 || h->sensCap == 8) return h->sensCap;
-    const int reach = h->P.n + h->P.nsoft < h->P.m ? h->P.n + h->P.nsoft : h->P.m;
-    return reach <= 5 ? 5 : 8;
-}
-
 int pg_ensure(lmpc_handle *h, int64_t N, size_t *bytes) {
     const PackGradDims g = pg_dims(h);
     const size_t G = pack_grad_doubles(g);
@@ -100,7 +93,7 @@ int pg_launch(lmpc_handle *h, int64_t N, const double *theta, const uint64_t *ac
     A.st = h->pgSt; A.rec = h->pgRec; A.recK = pg_rec_rows(g.m);
     A.list = h->dSensList; A.count = h->dSensCnt;
     A.part = h->pgPart;
-    const int CAP = pg_cap_of(h);
+    const int CAP = sens_cap_of(h);                      // the lane capacity the VJP picks
     A.cap = h->sensForceList ? 0 : CAP;
     const size_t cbytes = sizeof(double) * sens_pack_doubles(A.d);
     A.staged = cbytes <= kSensStageMax;
@@ -112,7 +105,6 @@ int pg_launch(lmpc_handle *h, int64_t N, const double *theta, const uint64_t *ac
     const int slog = h->pgSlabLog;
     const int64_t slab = (int64_t)1 << slog;
     const int64_t nslab = (N + slab - 1) / slab;
-    const long long resident = 4LL * h->numCU;
     bool sums = false;                                   // no output array asked for: stage 1 alone (thbar and status)
     for (int q = 0; q < PG_ARRAYS; q++) sums = sums || out.p[q] != nullptr;
     unsigned grid1 = 0, gridw = 0, gridr = 0;
@@ -131,7 +123,7 @@ int pg_launch(lmpc_handle *h, int64_t N, const double *theta, const uint64_t *ac
         if (CAP == 5) pg_launch_lane<5>(A, grid, lds1, st);
         else pg_launch_lane<8>(A, grid, lds1, st);
         HIP_TRY(h, hipGetLastError());
-        const unsigned gw = (unsigned)(ns < resident ? ns : resident);
+        const unsigned gw = sens_wave_grid(h, ns);
         if (pass2) {
             hipLaunchKernelGGL(pack_grad_wave_kernel, dim3(gw), dim3(64), 0, st, A);
             HIP_TRY(h, hipGetLastError());
@@ -159,7 +151,7 @@ int pg_launch(lmpc_handle *h, int64_t N, const double *theta, const uint64_t *ac
 
 int pg_checks(lmpc_handle *h, int64_t N, const char *who) {
     if (!h || N < 0 || N > 0x7fffffffLL) return LMPC_ERR_BADARG;
-    return sens_refusal(h, who);
+    return sens_refuse(h, who);
 }
 
 // the point's contributions into the dense vector c (output arrays one after the other, each row-major), zeros elsewhere
@@ -190,9 +182,7 @@ void pg_contrib(const PackGradDims &g, const double *M, const double *Rout, cons
 }  // namespace
 
 int pack_grad_reserve(lmpc_handle *h, int64_t N) {
-    if (h->avi || h->P.avi || h->P.prox || h->P.nth == 0) return LMPC_OK;
-    for (int32_t s : h->P.sense) if (s & SENSE_BINARY) return LMPC_OK;
-    return pg_ensure(h, N, nullptr);
+    return sens_no_derivative(h, nullptr) ? LMPC_OK : pg_ensure(h, N, nullptr);
 }
 
 }  // namespace lmpc
@@ -252,17 +242,8 @@ int lmpc_solve_pack_vjp_host(int n, int m, int ms, int nth, int nout, const doub
                              const int32_t *exitflag, const double *xbar, double *Mbar, double *dubar, double *dlbar,
                              double *Dthbar, double *Routbar, double *x0bar, double *Xthbar, double *thbar, int32_t *status) {
     (void)x0;
-    auto bad = [](int code, const char *msg) { g_setup_err = msg; return code; };
-    if (n <= 0 || m < 0 || ms < 0 || ms > m || nth < 0 || nout <= 0 || nout > n || N < 0 || !Rout || (m > 0 && (!M || !sense)))
-        return bad(LMPC_ERR_BADARG, "lmpc_solve_pack_vjp_host: inconsistent dimensions or a NULL pack array");
     lmpc_settings st;
-    if (s) st = *s; else lmpc_default_settings(&st);
-    if (is_avi || st.eps_prox > 0.0)
-        return bad(LMPC_ERR_UNSUPPORTED, "lmpc_solve_pack_vjp_host: variational and proximal-point problems have no derivative here");
-    for (int j = 0; j < m; j++)
-        if (sense[j] & SENSE_BINARY) return bad(LMPC_ERR_UNSUPPORTED, "lmpc_solve_pack_vjp_host: BINARY rows have no derivative");
-    if (nth == 0) return bad(LMPC_ERR_BADARG, "lmpc_solve_pack_vjp_host: the problem has no parameter (nth = 0)");
-    if (!Xth || (m > 0 && (!Dth || !du || !dl))) return bad(LMPC_ERR_BADARG, "lmpc_solve_pack_vjp_host: a NULL pack array");
+    LMPC_TRY(sens_check_pack("lmpc_solve_pack_vjp_host", n, m, ms, nth, nout, M, Dth, Rout, Xth, sense, du && dl, s, is_avi, N, &st));
     PackGradDims g;
     g.n = n; g.m = m; g.nth = nth; g.nout = nout;
     double *outs[PG_ARRAYS] = {Mbar, dubar, dlbar, Dthbar, Routbar, x0bar, Xthbar};
@@ -273,12 +254,15 @@ int lmpc_solve_pack_vjp_host(int n, int m, int ms, int nth, int nout, const doub
     for (int q = 0; q < PG_ARRAYS; q++)
         if (outs[q]) std::memset(outs[q], 0, sizeof(double) * len[q]);
     if (N == 0) return LMPC_OK;
-    if (!theta || !active || !exitflag || !xbar) return bad(LMPC_ERR_BADARG, "lmpc_solve_pack_vjp_host: a required array is NULL");
+    if (!theta || !active || !exitflag || !xbar) {
+        g_setup_err = "lmpc_solve_pack_vjp_host: a required array is NULL";
+        return LMPC_ERR_BADARG;
+    }
     const int words = (2 * m + 63) / 64;
     SensDims d;
     d.m = m; d.nth = nth; d.nout = nout; d.words = words;
     std::vector<double> C;
-    sens_derived_pack(n, m, nth, nout, M, nullptr, Dth, Rout, Xth, sense, C);
+    sens_build_pack(n, d, M, nullptr, Dth, Rout, Xth, sense, C);
     const SensView S = sens_view(C.data(), d, st.rho_soft, st.zero_tol);
     // the balanced tree as a binary counter: level[l] holds the sum of a finished block of 2^l points
     std::vector<std::vector<double>> level;
@@ -288,11 +272,10 @@ int lmpc_solve_pack_vjp_host(int n, int m, int ms, int nth, int nout, const doub
     for (int64_t p = 0; p < N; p++) {
         const uint64_t *mask = active + (size_t)p * words;
         const int k = sens_active_rows<kSensMaxSet>(mask, words, m, a);
-        int stp;
-        if (exitflag[p] < 1) stp = SENS_FAILED_POINT;
-        else if (k > kSensMaxSet) stp = SENS_TOO_MANY;
-        else stp = pack_grad_point<kSensMaxSet>(S, du, dl, mask, a, k, theta + (size_t)p * nth, xbar + (size_t)p * nout, lam.data(),
-                                                y.data(), tb.data());
+        int stp = sens_classify(exitflag[p], k, kSensMaxSet);
+        if (stp == SENS_DONE)
+            stp = pack_grad_point<kSensMaxSet>(S, du, dl, mask, a, k, theta + (size_t)p * nth, xbar + (size_t)p * nout, lam.data(),
+                                               y.data(), tb.data());
         if (status) status[p] = stp;
         if (thbar)
             for (int t = 0; t < nth; t++) thbar[(size_t)p * nth + t] = stp == SENS_DONE ? tb[t] : 0.0;

@@ -3,8 +3,8 @@
 // and leaves the record [lambda | y]; stage 2 (pack_grad_reduce_kernel) forms every point's contributions, one point
 // per lane, and sums the 64 points of a wavefront in the contract's pairing; pack_grad_tree_kernel sums the partials
 // pairwise.  The arithmetic contract is stated in include/lmpc_hip.h ("Gradient with respect to the pack") and
-// restated in numpy in tests/pack_grad_reference.py.  The factor and the substitutions are those of
-// lmpc_sens_kernel.hpp, operation for operation.  Internal to liblmpc_hip.so.
+// restated in numpy in tests/pack_grad_reference.py.  The factor, the substitutions and the lane kernel's ends are
+// lmpc_sens_kernel.hpp's, called from here.  Internal to liblmpc_hip.so.
 #pragma once
 
 #include "lmpc_sens_kernel.hpp"
@@ -55,83 +55,29 @@ LMPC_SENS_HD inline int pack_grad_locate(const PackGradDims &d, size_t e, size_t
 // 1 if row j is active at its upper side (a row with both bits counts as upper)
 LMPC_SENS_HD inline int pack_grad_upper(const uint64_t *mask, int j) { return (int)((mask[j >> 6] >> (j & 63)) & 1); }
 
-// One point with |A| = k <= CAP: the factor of sens_point, then lambda = K_A^-1 d and y = K_A^-1 (P_A xbar) by the same
-// forward, diagonal and backward order, and thbar (where asked for) as sens_point forms it.  lam and y are written for
-// i < k only with SENS_DONE.
+// One point with |A| = k <= CAP: on the factor of sens_point, y = K_A^-1 (P_A xbar) and lambda = K_A^-1 d side by side,
+// and thbar (where asked for) as sens_point forms it.  lam and y are written for i < k only with SENS_DONE.
 template <int CAP>
 LMPC_SENS_HD inline int pack_grad_point(const SensView &S, const double *du, const double *dl, const uint64_t *mask, const int *a,
                                         int k, const double *theta, const double *xbar, double *lam, double *y, double *thbar) {
-    constexpr int NL = CAP * (CAP - 1) / 2 + 1;
-    double L[NL], D[CAP], rD[CAP], c[CAP];
-    LMPC_SENS_UNROLL
-    for (int j = 0; j < CAP; j++) {
-        if (j < k) {
-            LMPC_SENS_UNROLL
-            for (int p = 0; p < j; p++) c[p] = L[j * (j - 1) / 2 + p] * D[p];
-            LMPC_SENS_UNROLL
-            for (int i = j; i < CAP; i++) {
-                if (i < k) {
-                    double v = S.G[sens_tri((size_t)a[i]) + a[j]];
-                    if (i == j && S.soft[a[j]] != 0.0) v = v + S.rho;
-                    LMPC_SENS_UNROLL
-                    for (int p = 0; p < j; p++) v = fma(-L[i * (i - 1) / 2 + p], c[p], v);
-                    if (i == j) {
-                        if (v < S.zero_tol) return SENS_SINGULAR;
-                        D[j] = v;
-                        rD[j] = 1.0 / v;
-                    } else {
-                        L[i * (i - 1) / 2 + j] = v * rD[j];
-                    }
-                }
-            }
-        }
-    }
+    SensFactor<CAP> F;
+    if (sens_factor<CAP>(S, a, k, F) != SENS_DONE) return SENS_SINGULAR;
+    double z[2][CAP];       // y, lambda
+    sens_rhs<CAP>(S, a, k, xbar, z[0]);
     LMPC_SENS_UNROLL
     for (int i = 0; i < CAP; i++) {
-        y[i] = 0.0;
-        lam[i] = 0.0;
+        z[1][i] = 0.0;
         if (i < k) {
             double acc = pack_grad_upper(mask, a[i]) ? du[a[i]] : dl[a[i]];
             for (int t = 0; t < S.nth; t++) acc = fma(S.Dth[(size_t)a[i] * S.nth + t], theta[t], acc);
-            lam[i] = acc;
+            z[1][i] = acc;
         }
     }
-    for (int q = 0; q < S.nout; q++) {
-        const double xb = xbar[q];
-        LMPC_SENS_UNROLL
-        for (int i = 0; i < CAP; i++) if (i < k) y[i] = fma(S.P[(size_t)a[i] * S.nout + q], xb, y[i]);
-    }
+    sens_subst<CAP, 2>(F, k, z);
     LMPC_SENS_UNROLL
-    for (int i = 1; i < CAP; i++) {
-        if (i < k) {
-            LMPC_SENS_UNROLL
-            for (int p = 0; p < i; p++) {
-                y[i] = fma(-L[i * (i - 1) / 2 + p], y[p], y[i]);
-                lam[i] = fma(-L[i * (i - 1) / 2 + p], lam[p], lam[i]);
-            }
-        }
-    }
-    LMPC_SENS_UNROLL
-    for (int i = 0; i < CAP; i++) if (i < k) { y[i] = y[i] * rD[i]; lam[i] = lam[i] * rD[i]; }
-    LMPC_SENS_UNROLL
-    for (int i = CAP - 2; i >= 0; i--) {
-        if (i < k) {
-            LMPC_SENS_UNROLL
-            for (int p = CAP - 1; p > i; p--)
-                if (p < k) {
-                    y[i] = fma(-L[p * (p - 1) / 2 + i], y[p], y[i]);
-                    lam[i] = fma(-L[p * (p - 1) / 2 + i], lam[p], lam[i]);
-                }
-        }
-    }
+    for (int i = 0; i < CAP; i++) if (i < k) { y[i] = z[0][i]; lam[i] = z[1][i]; }
     if (thbar)
-        for (int t = 0; t < S.nth; t++) {
-            double acc = 0.0;
-            for (int q = 0; q < S.nout; q++) acc = fma(S.Xth[(size_t)q * S.nth + t], xbar[q], acc);
-            LMPC_SENS_UNROLL
-            for (int i = 0; i < CAP; i++) if (i < k) acc = fma(S.Dth[(size_t)a[i] * S.nth + t], y[i], acc);
-            thbar[t] = acc;
-        }
+        for (int t = 0; t < S.nth; t++) thbar[t] = sens_tail<CAP>(S, a, k, z[0], t, sens_xth_dot(S, xbar, t));
     return SENS_DONE;
 }
 
@@ -167,12 +113,7 @@ template <int CAP>
 __global__ __launch_bounds__(kPackGradBlock) void pack_grad_lane_kernel(PackGradArgs A) {
     extern __shared__ double pack_grad_lds[];
     const SensDims d = A.d;
-    if (A.staged) {
-        const int nd = (int)sens_pack_doubles(d);
-        for (int i = threadIdx.x; i < nd; i += blockDim.x) pack_grad_lds[i] = A.C[i];
-        __syncthreads();
-    }
-    const SensView S = sens_view(A.staged ? pack_grad_lds : A.C, d, A.rho, A.zero_tol);
+    const SensView S = sens_view(sens_stage_pack(A.C, d, A.staged, pack_grad_lds), d, A.rho, A.zero_tol);
     const double *du = A.K + (size_t)(d.m + d.nout) * A.n, *dl = du + d.m;
     const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     int a[CAP];
@@ -184,11 +125,10 @@ __global__ __launch_bounds__(kPackGradBlock) void pack_grad_lane_kernel(PackGrad
         const int k = sens_active_rows<CAP>(mask, d.words, d.m, a);
         double lam[CAP], y[CAP];
         double *tb = A.thbar ? A.thbar + (size_t)p * d.nth : nullptr;
-        int st = SENS_FAILED_POINT;
-        if (A.flag[p] < 1) st = SENS_FAILED_POINT;
-        else if (k > kSensMaxSet) st = SENS_TOO_MANY;
-        else if (k > A.cap) queued = true;
-        else st = pack_grad_point<CAP>(S, du, dl, mask, a, k, A.theta + (size_t)p * d.nth, A.xbar + (size_t)p * d.nout, lam, y, tb);
+        int st = sens_classify(A.flag[p], k, A.cap);
+        queued = st == SENS_QUEUED;
+        if (st == SENS_DONE)
+            st = pack_grad_point<CAP>(S, du, dl, mask, a, k, A.theta + (size_t)p * d.nth, A.xbar + (size_t)p * d.nout, lam, y, tb);
         if (!queued) {
             if (st == SENS_DONE) {
                 double *r = A.rec + (size_t)p * 2 * A.recK;
@@ -201,23 +141,12 @@ __global__ __launch_bounds__(kPackGradBlock) void pack_grad_lane_kernel(PackGrad
             if (A.status) A.status[p] = st;
         }
     }
-    const unsigned long long q = __ballot(queued);
-    if (q) {
-        const int leader = __ffsll(q) - 1;
-        const unsigned below = __builtin_amdgcn_mbcnt_hi((unsigned)(q >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)q, 0u));
-        int slot = 0;
-        if ((int)__lane_id() == leader) slot = atomicAdd(A.count, (int)__popcll(q));
-        slot = __shfl(slot, leader);
-        if (queued) A.list[slot + (int)below] = (int32_t)p;
-    }
+    sens_append(queued, p, A.list, A.count);
 }
 
-// One listed point per wavefront, as sens_wave_kernel (same factor, same order per value), with the two right-hand
-// sides substituted side by side.
+// One listed point per wavefront, as sens_wave_kernel, with the two right-hand sides substituted side by side.
 __global__ __launch_bounds__(64) void pack_grad_wave_kernel(PackGradArgs A) {
-    __shared__ double Lm[kSensMaxSet * kSensLd];
-    __shared__ double Ds[kSensMaxSet], ys[kSensMaxSet];
-    __shared__ int idx[kSensMaxSet];
+    __shared__ SensWaveLds W;
     const SensDims d = A.d;
     const SensView S = sens_view(A.C, d, A.rho, A.zero_tol);
     const double *du = A.K + (size_t)(d.m + d.nout) * A.n, *dl = du + d.m;
@@ -226,84 +155,31 @@ __global__ __launch_bounds__(64) void pack_grad_wave_kernel(PackGradArgs A) {
     for (int e = blockIdx.x; e < cnt; e += gridDim.x) {
         const long long p = A.list[e];
         const uint64_t *mask = A.active + (size_t)p * d.words;
-        int mine = 0, k = 0;
-        for (int rw = 0; 64 * rw < d.m; rw++) {
-            uint64_t u = sens_rows(mask, d.words, d.m, rw);
-            while (u) {
-                if (k == lane) mine = 64 * rw + sens_ctz(u);
-                k++; u &= u - 1;
-            }
-        }
+        int mine;
+        const int k = sens_wave_rows(mask, d, lane, &mine);
         double *tb = A.thbar ? A.thbar + (size_t)p * d.nth : nullptr;
-        int st = SENS_DONE;
-        if (k > kSensMaxSet) st = SENS_TOO_MANY;     // (never listed; kept so that no lane index can leave the 64 rows)
-        const bool in = lane < k && st == SENS_DONE;
-        __syncthreads();
-        idx[lane] = mine;
-        __syncthreads();
-        if (in)
-            for (int j = 0; j <= lane; j++) {
-                double v = S.G[sens_tri((size_t)mine) + idx[j]];
-                if (j == lane && S.soft[mine] != 0.0) v = v + S.rho;
-                Lm[lane * kSensLd + j] = v;
-            }
-        __syncthreads();
-        for (int j = 0; st == SENS_DONE && j < k; j++) {
-            double v = 0.0;
-            if (in && lane >= j) {
-                v = Lm[lane * kSensLd + j];
-                for (int q = 0; q < j; q++) {
-                    const double c = Lm[j * kSensLd + q] * Ds[q];
-                    v = fma(-Lm[lane * kSensLd + q], c, v);
-                }
-            }
-            const double dj = __shfl(v, j);
-            if (dj < S.zero_tol) { st = SENS_SINGULAR; break; }
-            const double r = 1.0 / dj;
-            if (lane == j) Ds[j] = dj;
-            if (in && lane > j) Lm[lane * kSensLd + j] = v * r;
-            __syncthreads();
-        }
+        double rD = 0.0;
+        // (a set beyond the 64 rows is never listed; refused so that no lane index can leave them)
+        const int st = k > kSensMaxSet ? SENS_TOO_MANY : sens_wave_factor(W, S, lane, mine, k, &rD) ? SENS_DONE : SENS_SINGULAR;
+        if (lane == 0) { A.st[p] = st; if (A.status) A.status[p] = st; }
         if (st != SENS_DONE) {
             if (tb) for (int t = lane; t < d.nth; t += 64) tb[t] = 0.0;
-            if (lane == 0) { A.st[p] = st; if (A.status) A.status[p] = st; }
             continue;
         }
-        const double rD = in ? 1.0 / Ds[lane] : 0.0;
         const double *xb = A.xbar + (size_t)p * d.nout, *th = A.theta + (size_t)p * d.nth;
-        double z = 0.0, l = 0.0;
-        if (in) {
-            for (int q = 0; q < d.nout; q++) z = fma(S.P[(size_t)mine * d.nout + q], xb[q], z);
-            l = pack_grad_upper(mask, mine) ? du[mine] : dl[mine];
-            for (int t = 0; t < d.nth; t++) l = fma(S.Dth[(size_t)mine * d.nth + t], th[t], l);
+        double z[2] = {0.0, 0.0};       // y, lambda
+        if (lane < k) {
+            z[0] = sens_p_dot(S, mine, xb);
+            z[1] = pack_grad_upper(mask, mine) ? du[mine] : dl[mine];
+            for (int t = 0; t < d.nth; t++) z[1] = fma(S.Dth[(size_t)mine * d.nth + t], th[t], z[1]);
         }
-        for (int q = 0; q + 1 < k; q++) {
-            const double zq = __shfl(z, q), lq = __shfl(l, q);
-            if (in && lane > q) { z = fma(-Lm[lane * kSensLd + q], zq, z); l = fma(-Lm[lane * kSensLd + q], lq, l); }
-        }
-        z = z * rD;
-        l = l * rD;
-        for (int q = k - 1; q >= 1; q--) {
-            const double yq = __shfl(z, q), lq = __shfl(l, q);
-            if (lane < q) { z = fma(-Lm[q * kSensLd + lane], yq, z); l = fma(-Lm[q * kSensLd + lane], lq, l); }
-        }
-        if (in) {
+        sens_wave_subst<2>(W, lane, k, rD, z);
+        if (lane < k) {
             double *r = A.rec + (size_t)p * 2 * A.recK;
-            r[lane] = l;
-            r[A.recK + lane] = z;
+            r[lane] = z[1];
+            r[A.recK + lane] = z[0];
         }
-        if (tb) {
-            __syncthreads();
-            ys[lane] = z;
-            __syncthreads();
-            for (int t = lane; t < d.nth; t += 64) {
-                double acc = 0.0;
-                for (int q = 0; q < d.nout; q++) acc = fma(S.Xth[(size_t)q * d.nth + t], xb[q], acc);
-                for (int i = 0; i < k; i++) acc = fma(S.Dth[(size_t)idx[i] * d.nth + t], ys[i], acc);
-                tb[t] = acc;
-            }
-        }
-        if (lane == 0) { A.st[p] = SENS_DONE; if (A.status) A.status[p] = SENS_DONE; }
+        if (tb) sens_wave_tail<false>(W, S, lane, k, z[0], xb, 0, tb);
     }
 }
 

@@ -10,6 +10,7 @@
 #include "lmpc_internal.hpp"
 #include "lmpc_scenario_adjoint_kernel.hpp"
 #include "lmpc_scenario_host.hpp"
+#include "lmpc_sens_kernel.hpp"
 
 using namespace lmpc;
 
@@ -118,7 +119,7 @@ int sweep(lmpc_handle *h, int64_t N, int T, const lmpc_scenario_sim *s, const lm
 
 int refuse(lmpc_handle *h, int64_t N, int T, const lmpc_scenario_sim *s, const lmpc_scenario_tape *tape, const lmpc_scenario_grad *g,
            const char *who) {
-    LMPC_TRY(sens_refusal(h, who));
+    LMPC_TRY(sens_refuse(h, who));
     const HandleObserver ob(h);
     std::string msg = scenario_problem(h->P.nth, h->P.nout, ob.ptr, s);
     if (msg.empty()) msg = grad_problem(N, T, s, tape, g);
@@ -174,9 +175,10 @@ int lmpc_scenario_vjp_host(int n, int m, int ms, int nth, int nout, const double
                            const lmpc_settings *settings, int is_avi, const lmpc_observer *observer, int64_t N, int T,
                            const lmpc_scenario_sim *s, const lmpc_scenario_tape *tape, const lmpc_scenario_grad *g) {
     auto bad = [](int code, const std::string &msg) { g_setup_err = "lmpc_scenario_vjp_host: " + msg; return code; };
-    // the pack's own refusals, by the call every step makes (an empty batch runs the checks alone)
-    LMPC_TRY(lmpc_solve_vjp_host(n, m, ms, nth, nout, M, du, dl, Dth, Rout, x0, Xth, sense, settings, is_avi, 0, nullptr, nullptr,
-                                 nullptr, nullptr, nullptr));
+    (void)du; (void)dl; (void)x0;
+    // the pack's own refusals, those of lmpc_solve_vjp_host
+    lmpc_settings st;
+    LMPC_TRY(sens_check_pack("lmpc_solve_*_host", n, m, ms, nth, nout, M, Dth, Rout, Xth, sense, true, settings, is_avi, 0, &st));
     std::string msg = scenario_problem(nth, nout, observer, s);
     if (msg.empty()) msg = grad_problem(N, T, s, tape, g);
     if (msg.empty() && s->use_observer && (!observer->plant_dynamics || !observer->measurement_function || !observer->k_transpose))
@@ -185,7 +187,12 @@ int lmpc_scenario_vjp_host(int n, int m, int ms, int nth, int nout, const double
     if (N == 0) return LMPC_OK;
     const int nx = s->nx, nu = s->nu, nup = s->nuprev;
     const bool obs = s->use_observer != 0;
-    const size_t words = (size_t)((2 * m + 63) / 64);
+    SensDims d;
+    d.m = m; d.nth = nth; d.nout = nout; d.words = (2 * m + 63) / 64;
+    const size_t words = (size_t)d.words;
+    std::vector<double> C;                               // the derived pack, once for the sweep
+    sens_build_pack(n, d, M, nullptr, Dth, Rout, Xth, sense, C);
+    const SensView S = sens_view(C.data(), d, st.rho_soft, st.zero_tol);
     std::vector<double> state((size_t)N * ((size_t)2 * nx + nup + nu + nth));
     std::vector<int32_t> status((size_t)N);
     ScnAdj A;
@@ -204,8 +211,7 @@ int lmpc_scenario_vjp_host(int n, int m, int ms, int nth, int nout, const double
         adj_advance(A, N, T, k, g);
         adj_launch_host(A);
         if (k < 0) break;
-        LMPC_TRY(lmpc_solve_vjp_host(n, m, ms, nth, nout, M, du, dl, Dth, Rout, x0, Xth, sense, settings, is_avi, N,
-                                     tape->active + (size_t)k * N * words, tape->flag + (size_t)k * N, A.ubar, thbar, status.data()));
+        sens_host_points(S, d, false, N, tape->active + (size_t)k * N * words, tape->flag + (size_t)k * N, A.ubar, thbar, status.data());
     }
     return LMPC_OK;
 }
