@@ -43,6 +43,39 @@ int need_device(lmpc_handle *h, int *count) {
     return LMPC_OK;
 }
 
+// ListSnapshot (lmpc_internal.hpp): room for a list of seg_cap words per segment, the copy, the read-back
+int snapshot_capture_check(lmpc_handle *h, hipStream_t st) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) return LMPC_OK;
+    (void)hipGetLastError();
+    return fail(h, LMPC_ERR_UNSUPPORTED, "lmpc: \"list_snapshot\" 1 does not work inside a stream capture");
+}
+hipError_t ListSnapshot::prepare(long long seg_cap) {
+    const size_t words = (size_t)kCountSetWords + (size_t)kShards * (size_t)seg_cap;
+    if (words > buf.size()) segCap = 0;                 // (what it held goes with the block)
+    return buf.reserve(words);
+}
+hipError_t ListSnapshot::take(const int32_t *count, const int32_t *list, long long seg_cap, hipStream_t st) {
+    hipError_t e = hipMemcpyAsync(buf, count, sizeof(int32_t) * kCountSetWords, hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(count_set(buf.get(), 1), list, sizeof(int32_t) * kShards * (size_t)seg_cap, hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) segCap = seg_cap;
+    return e;
+}
+long long ListSnapshot::read(lmpc_handle *h, const char *who, int32_t *counts, int32_t *list, long long list_words) const {
+    if (!buf || segCap <= 0) return 0;
+    const long long need = (long long)kShards * segCap;
+    if (list && list_words < need) return fail(h, LMPC_ERR_BADARG, std::string(who) + ": list_words is smaller than 64 x seg_cap");
+    LMPC_ENTER_DEVICE(h);
+    hipError_t e = hipDeviceSynchronize();
+    int32_t cnt[kCountSetWords];
+    if (e == hipSuccess) e = hipMemcpy(cnt, buf, sizeof(cnt), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && list) e = hipMemcpy(list, count_set(buf.get(), 1), sizeof(int32_t) * (size_t)need, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(h, LMPC_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    for (int s = 0; s < kShards; s++) counts[s] = cnt[s * kCountStride];
+    return segCap;
+}
+
 }  // namespace lmpc
 
 namespace {
@@ -288,7 +321,7 @@ int launch_lane(lmpc_handle *h, const PackLayout &L, int B, size_t lds, int64_t 
         h->S.iter_limit > LMPC_FAST_KMAX + 1 && h->S.cycle_tol >= LMPC_FAST_KMAX + 1)
         tierArg = 2;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(B), lds, st, L, h->dC, theta, x, flag, iters, active,
-                       warm, list, count, count_next, segCap, kShards, (long long)nprob, tierArg);
+                       warm, list, count, count_next, segCap, (long long)nprob, tierArg);
     HIP_TRY(h, hipGetLastError());
     return LMPC_OK;
 }
@@ -384,25 +417,23 @@ int ensure_lists(lmpc_handle *h, int64_t nprob, hipStream_t st) {
     if (nprob <= h->listCap) return LMPC_OK;
     const size_t segCap = (size_t)lane_seg_cap(nprob);
     HIP_TRY(h, reserve_group(h->listCap, nprob, sized(h->dList, segCap * kShards),
-                             sized(h->dCount, (size_t)3 * kShards * kCountStride),   // two alternating sets + the parked list's
+                             sized(h->dCount, (size_t)3 * kCountSetWords),           // two alternating sets + the parked list's
                              sized(h->dList2, 0), sized(h->dList3, 0)));             // (launch_sim_run allocates these two)
-    HIP_TRY(h, hipMemsetAsync(h->dCount, 0, sizeof(int32_t) * 3 * kShards * kCountStride, st));
+    HIP_TRY(h, hipMemsetAsync(h->dCount, 0, sizeof(int32_t) * 3 * kCountSetWords, st));
     h->countSet = 0;
     return LMPC_OK;
 }
 
 // the work-list counter set of this call and the one the call's iterating kernel clears for the next call
 void next_count_set(lmpc_handle *h, int32_t **now, int32_t **next) {
-    *now = h->dCount + (size_t)h->countSet * kShards * kCountStride;
-    *next = h->dCount + (size_t)(h->countSet ^ 1) * kShards * kCountStride;
+    *now = count_set(h->dCount.get(), h->countSet);
+    *next = count_set(h->dCount.get(), h->countSet ^ 1);
     h->countSet ^= 1;
 }
 
 // ... and the list a front pass over a batch of nprob problems filled, as the wavefront path takes it
-WaveList work_list(const int32_t *list, const int32_t *count, int32_t *count_next, int64_t nprob) {
-    WaveList wl;
-    wl.list = list; wl.count = count; wl.count_next = count_next; wl.seg_cap = lane_seg_cap(nprob);
-    return wl;
+WorkList work_list(const int32_t *list, const int32_t *count, int32_t *count_next, int64_t nprob) {
+    return WorkList{list, count, count_next, lane_seg_cap(nprob)};
 }
 
 // what a front pass enqueued, for lmpc_front_pass_info (include/lmpc_hip.h lists the words)
@@ -411,34 +442,17 @@ void front_record(lmpc_handle *h, const FrontLaunch &fl, int64_t nprob, int walk
     h->frontRec.push({0, fl.kind, fl.n, sat(fl.grid), sat((long long)fl.lds), sat((long long)nprob), sat(lane_seg_cap(nprob)), walker});
 }
 
-int ensure_snapshot(lmpc_handle *h, int64_t nprob);
-// option "list_snapshot": the buffer for a batch of nprob problems (one counter set, then kShards segments), made ready
-// before the call enqueues anything (nothing with the option off)
+// option "list_snapshot" (nothing with it off): the buffer for a batch of nprob problems, ready before anything is enqueued
 int snapshot_prepare(lmpc_handle *h, int64_t nprob, hipStream_t st) {
     if (!h->listSnapshot) return LMPC_OK;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
-        (void)hipGetLastError();
-        return fail(h, LMPC_ERR_UNSUPPORTED, "lmpc: \"list_snapshot\" 1 does not work inside a stream capture");
-    }
-    return ensure_snapshot(h, nprob);
-}
-int ensure_snapshot(lmpc_handle *h, int64_t nprob) {
-    const size_t words = (size_t)kShards * kCountStride + (size_t)kShards * (size_t)lane_seg_cap(nprob);
-    if (words <= h->dSnap.size()) return LMPC_OK;
-    h->snapSegCap = 0;
-    HIP_TRY(h, h->dSnap.reserve(words));
+    LMPC_TRY(snapshot_capture_check(h, st));
+    HIP_TRY(h, h->snap.prepare(lane_seg_cap(nprob)));
     return LMPC_OK;
 }
-
 // ... and the copy itself, enqueued between a front pass and the kernel that walks its list
 int list_snapshot(lmpc_handle *h, const int32_t *count, int64_t nprob, hipStream_t st) {
     if (!h->listSnapshot) return LMPC_OK;
-    const size_t segCap = (size_t)lane_seg_cap(nprob);
-    HIP_TRY(h, hipMemcpyAsync(h->dSnap, count, sizeof(int32_t) * kShards * kCountStride, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(h, hipMemcpyAsync(h->dSnap + (size_t)kShards * kCountStride, h->dList, sizeof(int32_t) * kShards * segCap,
-                              hipMemcpyDeviceToDevice, st));
-    h->snapSegCap = (long long)segCap;
+    HIP_TRY(h, h->snap.take(count, h->dList, lane_seg_cap(nprob), st));
     return LMPC_OK;
 }
 
@@ -626,7 +640,7 @@ int launch_sim_run(lmpc_handle *h, const LoopMode &mode, int64_t nprob, const do
     const long long segCap = lane_seg_cap(nprob);
     HIP_TRY(h, h->dList2.reserve((size_t)lane_seg_cap(h->listCap) * kShards));
     HIP_TRY(h, h->dList3.reserve((size_t)lane_seg_cap(h->listCap) * kShards));
-    int32_t *parkCnt = h->dCount + 2 * (size_t)kShards * kCountStride;
+    int32_t *parkCnt = count_set(h->dCount.get(), 2);
     // first round: every scenario; later rounds: the scenarios of the round before's list, compacted
     const int32_t *lin = ar.listIn, *cin = ar.cntIn;
     int32_t *lout = (lin == h->dList) ? h->dList2 : h->dList;   // (the parked list as input: the work list is empty)
@@ -641,7 +655,7 @@ int launch_sim_run(lmpc_handle *h, const LoopMode &mode, int64_t nprob, const do
     const bool small_ = h->simSmall && Sf.nx <= 4 && Sf.nu == 1 && h->P.m >= 1 && h->P.m <= 8 && h->P.nth <= 8;
 #define LMPC_SRUN_(NM, NT, SM) hipLaunchKernelGGL((sim_run_kernel<NM, NT, SM>), dim3(grid), dim3(256), ldsr, st, L, h->dC, \
         const_cast<double *>(theta), Sf.kstep, ar.T, active, warm != nullptr ? 1 : 0, Sf.utraj, Sf.xtraj_base, \
-        Sf.flag_min, lout, cnt_now, segCap, kShards, (long long)nprob, lin, cin, ar.cap, h->dList3, parkCnt, \
+        Sf.flag_min, lout, cnt_now, segCap, (long long)nprob, lin, cin, ar.cap, h->dList3, parkCnt, \
         ar.x, ar.r, ar.up)
 #define LMPC_SRUN(NM, NT) do { if constexpr (NT <= 8) { if (small_) LMPC_SRUN_(NM, NT, true); else LMPC_SRUN_(NM, NT, false); } \
                             else LMPC_SRUN_(NM, NT, false); } while (0)
@@ -658,7 +672,7 @@ int launch_sim_run(lmpc_handle *h, const LoopMode &mode, int64_t nprob, const do
 #undef LMPC_SRUN_
     HIP_TRY(h, hipGetLastError());
     ar.x = ar.r = ar.up = nullptr;                      // only the first pass forms theta
-    if (ar.resetPark) HIP_TRY(h, hipMemsetAsync(parkCnt, 0, sizeof(int32_t) * kShards * kCountStride, st));
+    if (ar.resetPark) HIP_TRY(h, hipMemsetAsync(parkCnt, 0, sizeof(int32_t) * kCountSetWords, st));
     return LMPC_OK;
 }
 
@@ -1163,18 +1177,7 @@ int lmpc_front_pass_info(const lmpc_handle *h, int32_t *out, int max) {
 
 long long lmpc_work_list_read(lmpc_handle *h, int32_t *counts, int32_t *list, long long list_words) {
     if (!h || !counts) return LMPC_ERR_BADARG;
-    if (!h->dSnap || h->snapSegCap <= 0) return 0;
-    const long long need = (long long)kShards * h->snapSegCap;
-    if (list && list_words < need) return fail(h, LMPC_ERR_BADARG, "lmpc_work_list_read: list_words is smaller than 64 x seg_cap");
-    LMPC_ENTER_DEVICE(h);
-    hipError_t e = hipDeviceSynchronize();
-    int32_t cnt[kShards * kCountStride];
-    if (e == hipSuccess) e = hipMemcpy(cnt, h->dSnap, sizeof(cnt), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && list)
-        e = hipMemcpy(list, h->dSnap + (size_t)kShards * kCountStride, sizeof(int32_t) * (size_t)need, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return fail(h, LMPC_ERR_HIP, std::string("lmpc_work_list_read: ") + hipGetErrorString(e));
-    for (int s = 0; s < kShards; s++) counts[s] = cnt[s * kCountStride];
-    return h->snapSegCap;
+    return h->snap.read(h, "lmpc_work_list_read", counts, list, list_words);
 }
 
 int lmpc_avi_launch_info(const lmpc_handle *h, int32_t *out, int max) {
@@ -1184,8 +1187,7 @@ int lmpc_avi_launch_info(const lmpc_handle *h, int32_t *out, int max) {
 
 long long lmpc_avi_list_read(lmpc_handle *h, int which, int32_t *counts, int32_t *list, long long list_words) {
     if (!h || !counts || which < 0 || which > 1) return LMPC_ERR_BADARG;
-    LMPC_ENTER_DEVICE(h);
-    return avi_list_read(h, which, counts, list, list_words);
+    return h->aviSnap[which].read(h, "lmpc_avi_list_read", counts, list, list_words);
 }
 
 const char *lmpc_kernel_name(const lmpc_handle *h) {
@@ -1330,10 +1332,11 @@ int lmpc_set_option(lmpc_handle *h, const char *name, int value) {
     if (std::strcmp(name, "list_snapshot") == 0) {
         // (tests: what a front pass left on the work list, lmpc_work_list_read; the buffer for the lists the handle
         // holds now, a larger batch grows it)
-        h->listSnapshot = value != 0; h->snapSegCap = 0; h->aviSnapSeg[0] = h->aviSnapSeg[1] = 0;
+        h->listSnapshot = value != 0; h->snap.segCap = h->aviSnap[0].segCap = h->aviSnap[1].segCap = 0;
         if (!h->listSnapshot || h->listCap <= 0) return LMPC_OK;
         LMPC_ENTER_DEVICE(h);
-        return ensure_snapshot(h, h->listCap);
+        HIP_TRY(h, h->snap.prepare(lane_seg_cap(h->listCap)));
+        return LMPC_OK;
     }
     if (std::strcmp(name, "avi_tiers") == 0) { h->aviTiers = value != 0; return LMPC_OK; }
     if (std::strcmp(name, "sens_cap") == 0) {

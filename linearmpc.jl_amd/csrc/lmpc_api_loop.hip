@@ -175,8 +175,7 @@ int lmpc_simulate_device(lmpc_handle *h, int64_t N, int T, int nx, int nr, int n
         }
         if (h->useWave) mode.waveSim = WaveSim{h->simFG, h->simK, U_traj, X_traj, flag_min, nx, nu, nr, nuprev, (long long)N, -1, runAhead ? T : 0};
         constexpr int kBurst = 2;   // steps a scenario of a (short) work list may run ahead before it is parked
-        const size_t setLen = (size_t)kShards * kCountStride;
-        std::vector<int32_t> hc(3 * setLen);
+        std::vector<int32_t> hc(3 * kCountSetWords);
         uint64_t *masks = warm ? h->simAct : nullptr;
         int rc = LMPC_OK;
         ar.cap = T + 1;
@@ -191,10 +190,10 @@ int lmpc_simulate_device(lmpc_handle *h, int64_t N, int T, int nx, int nr, int n
             if (rc != LMPC_OK) break;
             if (hipMemcpyAsync(hc.data(), h->dCount, sizeof(int32_t) * hc.size(), hipMemcpyDeviceToHost, st) != hipSuccess ||
                 hipStreamSynchronize(st) != hipSuccess) { rc = fail(h, LMPC_ERR_HIP, "lmpc_simulate: reading the work-list counters"); break; }
-            const size_t off = (size_t)(ar.cntNow - h->dCount);
+            const int32_t *hq = hc.data() + (ar.cntNow - h->dCount), *hp = count_set(hc.data(), 2);     // queued now, parked
             long long queued = 0, longest = 0, parked = 0, plongest = 0;
             for (int sh = 0; sh < kShards; sh++) {
-                const long long q = hc[off + (size_t)sh * kCountStride], pk = ar.resetPark ? 0 : hc[2 * setLen + (size_t)sh * kCountStride];
+                const long long q = hq[sh * kCountStride], pk = ar.resetPark ? 0 : hp[sh * kCountStride];
                 queued += q; parked += pk;
                 longest = q > longest ? q : longest;
                 plongest = pk > plongest ? pk : plongest;
@@ -218,8 +217,8 @@ int lmpc_simulate_device(lmpc_handle *h, int64_t N, int T, int nx, int nr, int n
                 }
             } else if (parked > 0) {
                 // no iterating kernel ran, so nobody cleared the counter set the next pass writes
-                if (hipMemsetAsync(h->dCount, 0, sizeof(int32_t) * 2 * setLen, st) != hipSuccess) { rc = fail(h, LMPC_ERR_HIP, "lmpc_simulate: clearing the work-list counters"); break; }
-                ar.listIn = h->dList3; ar.cntIn = h->dCount + 2 * setLen; ar.maxIn = plongest;
+                if (hipMemsetAsync(h->dCount, 0, sizeof(int32_t) * 2 * kCountSetWords, st) != hipSuccess) { rc = fail(h, LMPC_ERR_HIP, "lmpc_simulate: clearing the work-list counters"); break; }
+                ar.listIn = h->dList3; ar.cntIn = count_set(h->dCount.get(), 2); ar.maxIn = plongest;
                 ar.cap = T + 1;
                 ar.resetPark = true;
             } else {
@@ -233,7 +232,7 @@ int lmpc_simulate_device(lmpc_handle *h, int64_t N, int T, int nx, int nr, int n
             rc = fail(h, LMPC_ERR_HIP, "lmpc_simulate: the scenario-asynchronous loop hit its pass limit with scenarios "
                                        "still queued (lmpc_set_option(\"sim_async\", 0) runs the step-synchronous loop)");
         // the last streaming pass queued nothing, so no iterating kernel cleared the other counter set
-        if (h->dCount) { hipMemsetAsync(h->dCount, 0, sizeof(int32_t) * 3 * kShards * kCountStride, st); h->countSet = 0; }
+        if (h->dCount) { hipMemsetAsync(h->dCount, 0, sizeof(int32_t) * 3 * kCountSetWords, st); h->countSet = 0; }
         return rc != LMPC_OK ? rc : unpack(h->simTheta);
     }
     if (!h->useWave && h->simFused && nu <= kMaxSimU) {

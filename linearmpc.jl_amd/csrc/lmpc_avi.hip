@@ -138,8 +138,8 @@ static int avi_ensure_lists(lmpc_handle *h, int64_t nprob, hipStream_t st) {
     if (h->dAviCnt) (void)hipStreamSynchronize(st);
     const size_t seg = (size_t)avi_seg_cap(nprob);
     HIP_TRY(h, reserve_group(h->aviListCap, nprob, sized(h->dAviList[0], seg * kShards), sized(h->dAviList[1], seg * kShards),
-                             sized(h->dAviCnt, (size_t)2 * kShards * kCountStride)));
-    HIP_TRY(h, hipMemsetAsync(h->dAviCnt, 0, sizeof(int32_t) * 2 * kShards * kCountStride, st));
+                             sized(h->dAviCnt, (size_t)2 * kCountSetWords)));
+    HIP_TRY(h, hipMemsetAsync(h->dAviCnt, 0, sizeof(int32_t) * 2 * kCountSetWords, st));
     return LMPC_OK;
 }
 
@@ -148,38 +148,6 @@ static void avi_record(lmpc_handle *h, int stage, int n, int k, int list, int ld
                        int occ, long long nprob, long long seg_cap) {
     const auto sat = [](long long v) { return (int32_t)(v < 0x7fffffffll ? v : 0x7fffffffll); };
     h->aviRec.push({0, stage, n, k, list, ldsc, prox, sat(grid), sat((long long)lds), occ, sat(nprob), sat(seg_cap)});
-}
-
-// option "list_snapshot": room for both lists of the chain as they are allocated now, made ready before the call
-// enqueues anything ...
-static int avi_snapshot_prepare(lmpc_handle *h) {
-    const size_t words = (size_t)kShards * kCountStride + (size_t)kShards * (size_t)avi_seg_cap(h->aviListCap);
-    HIP_TRY(h, h->dAviSnap.reserve(2 * words));
-    return LMPC_OK;
-}
-// ... and the copy of one list, enqueued right after the launch that filled it
-static int avi_snapshot(lmpc_handle *h, int which, const int32_t *count, const int32_t *list, long long seg_cap, hipStream_t st) {
-    int32_t *dst = h->dAviSnap + (size_t)which * (h->dAviSnap.size() / 2);
-    HIP_TRY(h, hipMemcpyAsync(dst, count, sizeof(int32_t) * kShards * kCountStride, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(h, hipMemcpyAsync(dst + (size_t)kShards * kCountStride, list, sizeof(int32_t) * kShards * (size_t)seg_cap,
-                              hipMemcpyDeviceToDevice, st));
-    h->aviSnapSeg[which] = seg_cap;
-    return LMPC_OK;
-}
-
-long long avi_list_read(lmpc_handle *h, int which, int32_t *counts, int32_t *list, long long list_words) {
-    if (!h->dAviSnap || h->aviSnapSeg[which] <= 0) return 0;
-    const long long seg = h->aviSnapSeg[which], need = (long long)kShards * seg;
-    if (list && list_words < need) return fail(h, LMPC_ERR_BADARG, "lmpc_avi_list_read: list_words is smaller than 64 x seg_cap");
-    const int32_t *src = h->dAviSnap + (size_t)which * (h->dAviSnap.size() / 2);
-    hipError_t e = hipDeviceSynchronize();
-    int32_t cnt[kShards * kCountStride];
-    if (e == hipSuccess) e = hipMemcpy(cnt, src, sizeof(cnt), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && list)
-        e = hipMemcpy(list, src + (size_t)kShards * kCountStride, sizeof(int32_t) * (size_t)need, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return fail(h, LMPC_ERR_HIP, std::string("lmpc_avi_list_read: ") + hipGetErrorString(e));
-    for (int s = 0; s < kShards; s++) counts[s] = cnt[s * kCountStride];
-    return seg;
 }
 
 // the generic kernel's grid for `tiles` tiles of 64 problems -- one wavefront per workgroup, resident wavefronts bounded
@@ -223,19 +191,17 @@ int launch_avi(lmpc_handle *h, int64_t nprob, const double *theta, double *x, in
     if (!x || !flag) return fail(h, LMPC_ERR_BADARG, "lmpc: the variational-inequality kernel needs x and exitflag arrays");
     const long long tiles = (nprob + 63) / 64;
     if (h->listSnapshot) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
-            (void)hipGetLastError();
-            return fail(h, LMPC_ERR_UNSUPPORTED, "lmpc: \"list_snapshot\" 1 does not work inside a stream capture");
-        }
-        h->aviSnapSeg[0] = h->aviSnapSeg[1] = 0;       // (a call without the chain leaves no list)
+        LMPC_TRY(snapshot_capture_check(h, st));
+        h->aviSnap[0].segCap = h->aviSnap[1].segCap = 0;       // (a call without the chain leaves no list)
     }
     if (!avi_use_tiers(h, nprob, warm))
         return avi_generic(h, nprob, tiles, theta, x, flag, iters, active, warm, nullptr, nullptr, 0, nullptr, st);
     // chain: tiers over the whole batch -> all n tiers on its list -> the generic kernel on that one's list
     const int rc0 = avi_ensure_lists(h, nprob, st);
     if (rc0 != LMPC_OK) return rc0;
-    if (h->listSnapshot) { const int rcs = avi_snapshot_prepare(h); if (rcs != LMPC_OK) return rcs; }
+    const long long seg = avi_seg_cap(h->aviListCap);
+    // option "list_snapshot": room for both lists, ready before anything is enqueued; each is copied behind its producer
+    if (h->listSnapshot) for (ListSnapshot &s : h->aviSnap) HIP_TRY(h, s.prepare(seg));
     // tiers of the first pass: three finish 93 % of the reference's game problem at 3 wavefronts per SIMD (n <= 6)
     const int kfirst = h->aviTiersFirst >= 0 ? h->aviTiersFirst : (h->aviTiersN <= 6 ? 3 : 2);
     for (int s = 0; s < 2; s++)
@@ -244,8 +210,7 @@ int launch_avi(lmpc_handle *h, int64_t nprob, const double *theta, double *x, in
                                              nullptr, nullptr, nullptr, nullptr, 0, 0, &h->aviTiersOcc[s]);
             if (rco != LMPC_OK) return rco;
         }
-    const long long seg = avi_seg_cap(h->aviListCap);
-    int32_t *cnt0 = h->dAviCnt, *cnt1 = h->dAviCnt + (size_t)kShards * kCountStride;
+    int32_t *cnt0 = h->dAviCnt, *cnt1 = count_set(h->dAviCnt.get(), 1);
     // workgroups of four wavefronts, a multiple of 16 (wavefronts a multiple of kShards), one resident round at most
     auto grid_for = [&](int occ) {
         long long g = (long long)h->numCU * occ;
@@ -261,12 +226,12 @@ int launch_avi(lmpc_handle *h, int64_t nprob, const double *theta, double *x, in
                               nullptr, h->dAviList[0], cnt0, cnt1, seg, (long long)nprob, nullptr, &sh);
     if (rc != LMPC_OK) return rc;
     avi_record(h, sh.stage, sh.n, sh.k, sh.list, 0, 0, g0, sh.lds, h->aviTiersOcc[0], nprob, seg);
-    if (h->listSnapshot) { rc = avi_snapshot(h, 0, cnt0, h->dAviList[0], seg, st); if (rc != LMPC_OK) return rc; }
+    if (h->listSnapshot) HIP_TRY(h, h->aviSnap[0].take(cnt0, h->dAviList[0], seg, st));
     rc = launch_avi_tiers(h, false, 0, g1, st, theta, x, flag, iters, active, h->dAviList[0], cnt0,
                           h->dAviList[1], cnt1, nullptr, seg, (long long)nprob, nullptr, &sh);
     if (rc != LMPC_OK) return rc;
     avi_record(h, sh.stage, sh.n, sh.k, sh.list, 0, 0, g1, sh.lds, h->aviTiersOcc[1], nprob, seg);
-    if (h->listSnapshot) { rc = avi_snapshot(h, 1, cnt1, h->dAviList[1], seg, st); if (rc != LMPC_OK) return rc; }
+    if (h->listSnapshot) HIP_TRY(h, h->aviSnap[1].take(cnt1, h->dAviList[1], seg, st));
     return avi_generic(h, nprob, std::min<long long>(tiles, (long long)h->numCU * 4), theta, x, flag, iters, active, nullptr,
                        h->dAviList[1], cnt1, seg, cnt0, st);
 }

@@ -30,6 +30,7 @@
 
 #include "lmpc_pack.hpp"
 #include "lmpc_wave_layout.hpp"
+#include "lmpc_worklist.hpp"
 
 namespace lmpc {
 
@@ -56,17 +57,15 @@ __global__ __launch_bounds__(64) void avi_kernel(
     const int n = P.n, m = P.m, nth = P.nth, cap = P.cap;
     const int lane = threadIdx.x;
     // work-list mode (behind avi_tiers_kernel, lmpc_avi_tiers_kernel.hpp): the problems to solve are the entries of
-    // kShards segments of `list` (segment s: count[s * kCountStride] entries from list[s * seg_cap]); workgroup b walks
-    // segment b % kShards (the grid is a multiple of kShards).  The counters of the chain's FIRST list are cleared here
+    // `list` (lmpc_worklist.hpp); workgroup b walks segment b % kShards (the grid is a multiple of kShards).  The
+    // counters of the chain's FIRST list are cleared here
     // for the next call (the kernel that read them has finished: stream order).
-    if (count_clear && blockIdx.x == 0 && lane < kShards) count_clear[lane * kCountStride] = 0;
+    wl_clear_counts(count_clear, lane);
     long long first = (long long)blockIdx.x * 64, stride = (long long)gridDim.x * 64, cnt = nprob;
     if (list) {
-        const int shard = (int)(blockIdx.x % kShards);
-        first = (long long)(blockIdx.x / kShards) * 64;
-        stride = (long long)(gridDim.x / kShards) * 64;
-        cnt = (long long)count[shard * kCountStride];
-        list += (long long)shard * seg_cap;
+        const WlWalk wk = wl_walk_block(64);
+        first = wk.first; stride = wk.stride; cnt = wk.count(count);
+        list = wk.segment(list, seg_cap);
         if (first >= cnt) return;                 // (nothing listed for this wavefront: the usual case behind the lane kernel)
     }
     if constexpr (LDSC) {

@@ -43,6 +43,7 @@
 #include "lmpc_pack.hpp"
 #include "lmpc_tiers.hpp"
 #include "lmpc_wave_layout.hpp"
+#include "lmpc_worklist.hpp"
 
 namespace lmpc {
 
@@ -130,32 +131,6 @@ __device__ __forceinline__ void avi_small_output(const AviLayout &P, const doubl
     }
 }
 
-// the lanes flagged `queue` append their problem index to segment `shard` of a work list -- in two halves, so that the
-// round trip of the counter's atomic is not waited for: avi_push_reserve at the end of a tile, avi_push_write at the end
-// of the NEXT one (and after the last)
-struct AviPush { unsigned long long mask = 0ull; int base = 0; int pid = 0; };
-__device__ __forceinline__ void avi_push_reserve(AviPush &q, bool queue, long long pid, int lane, int shard,
-                                                 int32_t *__restrict__ count_out) {
-    q.mask = __ballot(queue);
-    q.pid = (int)pid;
-    q.base = 0;
-    if (q.mask != 0ull && lane == 0) q.base = atomicAdd(&count_out[shard * kCountStride], __popcll(q.mask));
-}
-__device__ __forceinline__ void avi_push_write(AviPush &q, int lane, int shard, long long seg_cap, int32_t *__restrict__ list_out) {
-    if (q.mask != 0ull) {
-        const int qbase = __shfl(q.base, 0);
-        if ((q.mask >> lane) & 1ull)
-            list_out[(long long)shard * seg_cap + qbase + __popcll(q.mask & ((1ull << lane) - 1ull))] = q.pid;
-    }
-    q.mask = 0ull;
-}
-__device__ __forceinline__ void avi_small_push(bool queue, long long pid, int lane, int shard, long long seg_cap,
-                                               int32_t *__restrict__ list_out, int32_t *__restrict__ count_out) {
-    AviPush q;
-    avi_push_reserve(q, queue, pid, lane, shard, count_out);
-    avi_push_write(q, lane, shard, seg_cap, list_out);
-}
-
 // one scanned row: most violated inactive row at the target (ties: the first), first satisfied row the step breaks
 #define LMPC_AVI_SCAN_ROW(jj, ACTIVE_LANES)                                                                    \
     {                                                                                                          \
@@ -195,7 +170,7 @@ __global__ __launch_bounds__(256) void avi_tiers_kernel(
     const int nth = P.nth, nout = P.nout;
     const int tid = threadIdx.x, lane = tid & 63;
     // the counters of the list AFTER the next one are cleared here (the kernel that read them has finished: stream order)
-    if (count_clear && blockIdx.x == 0 && tid < kShards) count_clear[tid * kCountStride] = 0;
+    wl_clear_counts(count_clear, tid);
     avi_small_stage<N>(P, C, lds, tid, 256);
     __syncthreads();
     const double ptol = P.primal_tol, dtol = P.dual_tol, ztol = P.zero_tol;
@@ -204,8 +179,9 @@ __global__ __launch_bounds__(256) void avi_tiers_kernel(
     const int shard = (int)(gw % kShards);
     long long first, stride, cnt;
     if constexpr (LIST) {
-        first = (gw / kShards) * 64; stride = (nw / kShards) * 64; cnt = (long long)count_in[shard * kCountStride];
-        list_in += (long long)shard * seg_cap;
+        const WlWalk wk = wl_walk_wave(gw, nw);
+        first = wk.first; stride = wk.stride; cnt = wk.count(count_in);
+        list_in = wk.segment(list_in, seg_cap);
     } else {
         first = gw * 64; stride = nw * 64; cnt = nprob;
     }
@@ -215,7 +191,7 @@ __global__ __launch_bounds__(256) void avi_tiers_kernel(
     // there in VGPRs; as scalar loads inside the scan each row waited for its own)
     double sd[N];
     lmpc_lds_run<N>(lds + Ly::oSd, 0, sd);
-    AviPush pend;
+    WlPush pend;
     for (long long base = first; base < cnt; base += stride) {
         const long long idx = base + lane;
         const bool mine = idx < cnt;
@@ -367,10 +343,10 @@ __global__ __launch_bounds__(256) void avi_tiers_kernel(
 
         if (finished)
             avi_small_output<N>(P, C + zofs, shx, nout, pid, ufin, iter_fin, act_fin, low_fin, X, exitflag, iters, active);
-        avi_push_write(pend, lane, shard, seg_cap, list_out);          // (the tile before's)
-        avi_push_reserve(pend, mine && !finished, pid, lane, shard, count_out);
+        wl_push_write(pend, lane, shard, seg_cap, list_out);          // (the tile before's)
+        wl_push_reserve(pend, mine && !finished, pid, lane, shard, count_out);
     }
-    avi_push_write(pend, lane, shard, seg_cap, list_out);
+    wl_push_write(pend, lane, shard, seg_cap, list_out);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -662,7 +638,7 @@ __global__ __launch_bounds__(256, (N <= 6 ? 2 : 1)) void avi_lane_kernel(
     extern __shared__ __align__(16) double lds[];
     const int nth = P.nth, nout = P.nout;
     const int tid = threadIdx.x, lane = tid & 63;
-    if (count_clear && blockIdx.x == 0 && tid < kShards) count_clear[tid * kCountStride] = 0;
+    wl_clear_counts(count_clear, tid);
     avi_small_stage<N>(P, C, lds, tid, 256);
     __syncthreads();
     const double ptol = P.primal_tol, dtol = P.dual_tol, ztol = P.zero_tol;
@@ -670,8 +646,9 @@ __global__ __launch_bounds__(256, (N <= 6 ? 2 : 1)) void avi_lane_kernel(
     const int shard = (int)(gw % kShards);
     long long first, stride, cnt;
     if constexpr (LIST) {
-        first = (gw / kShards) * 64; stride = (nw / kShards) * 64; cnt = (long long)count_in[shard * kCountStride];
-        list_in += (long long)shard * seg_cap;
+        const WlWalk wk = wl_walk_wave(gw, nw);
+        first = wk.first; stride = wk.stride; cnt = wk.count(count_in);
+        list_in = wk.segment(list_in, seg_cap);
     } else {
         first = gw * 64; stride = nw * 64; cnt = nprob;
     }
@@ -709,7 +686,7 @@ __global__ __launch_bounds__(256, (N <= 6 ? 2 : 1)) void avi_lane_kernel(
             for (int c = 0; c < N; c++) uf[c] = s.ufin(c);
             avi_small_output<N>(P, C, s.park + 5 * N * 64, nout, pid, uf, s.iter_fin, s.act_fin, s.low_fin, X, exitflag, iters, active);
         }
-        avi_small_push(mine && !s.finished, pid, lane, shard, seg_cap, list_out, count_out);
+        wl_push(mine && !s.finished, pid, lane, shard, seg_cap, list_out, count_out);
     }
 }
 

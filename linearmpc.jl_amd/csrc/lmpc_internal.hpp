@@ -17,6 +17,7 @@
 #include "lmpc_buffer.hpp"
 #include "lmpc_pack.hpp"
 #include "lmpc_wave_layout.hpp"
+#include "lmpc_worklist.hpp"
 
 namespace lmpc {
 constexpr int kLaneSizes[] = {2, 3, 4, 5, 6, 8, 10, 12};
@@ -27,8 +28,6 @@ constexpr int kWaveMaxN = 127, kWaveMaxCap = 64, kWaveMaxM = 1024;
 constexpr int64_t kProbe = 16384;       // points a fresh wavefront-kernel handle solves in front of its first large batch (wave_probe)
 
 struct EventTriple { hipEvent_t a, mid, b; };
-// work-list mode of the wavefront kernel for one launch (list == nullptr: the whole batch)
-struct WaveList { const int32_t *list = nullptr, *count = nullptr; int32_t *count_next = nullptr; long long seg_cap = 0; };
 
 // The two allocation policies of lmpc::Buffer (lmpc_buffer.hpp) and the count of their live blocks (lmpc_debug_live_blocks)
 inline std::atomic<int64_t> g_live_blocks{0};
@@ -61,6 +60,15 @@ template <class T> using DevBuf = Buffer<T, DeviceAlloc>;
 template <class T> using MappedBuf = Buffer<T, HostAlloc<hipHostMallocMapped>>;
 template <class T> using PinnedBuf = Buffer<T, HostAlloc<hipHostMallocDefault>>;
 using DevBytes = DevBuf<unsigned char>;       // a block whose element type varies with the call: as<R>()
+// option "list_snapshot": one work list copied aside -- one set of counters, then the kShards segments (lmpc_api.hip)
+struct ListSnapshot {
+    DevBuf<int32_t> buf;
+    long long segCap = 0;       // seg_cap of the list it holds (0: none)
+    hipError_t prepare(long long seg_cap);                      // room for such a list, before anything is enqueued
+    hipError_t take(const int32_t *count, const int32_t *list, long long seg_cap, hipStream_t st);
+    // the counts and (list != nullptr) the segments back on the host; the list's seg_cap, 0 without one, or an error of `who`
+    long long read(lmpc_handle *h, const char *who, int32_t *counts, int32_t *list, long long list_words) const;
+};
 }  // namespace lmpc
 
 // What lmpc_release_scratch gives back: every buffer that grows with the batch, with its capacity and phase fields.
@@ -77,8 +85,7 @@ struct lmpc_scratch {
     DevBuf<int32_t> dList2, dList3;        // second work list of the scenario-asynchronous closed loop (lists alternate per round; lazy)
     int64_t listCap = 0;        // batch size the list buffer was sized for
     int countSet = 0;           // which of the two counter sets the next call uses
-    DevBuf<int32_t> dSnap;      // option "list_snapshot": [kShards * kCountStride counter words | kShards * seg_cap list words]
-    long long snapSegCap = 0;   // ... seg_cap of the snapshot it holds (0: none)
+    lmpc::ListSnapshot snap;    // option "list_snapshot": the list of the last front pass
     // the wavefront path's first-pass overflow list, and the slow path for working sets beyond the 64 lanes
     // (lmpc_big_kernel.hpp): overflow list, per-thread scratch
     DevBuf<int32_t> dOvfList1;
@@ -93,15 +100,13 @@ struct lmpc_scratch {
     lmpc::DevBytes dKeepR;
     DevBuf<int32_t> dKeepI;
     int64_t keepCap = 0;
-    // variational handle: scratch slabs, the two work lists of the chain (kShards segments each) with their counters
-    // (two sets of kShards, kCountStride apart), the snapshot of both (two blocks of [kShards * kCountStride | kShards * seg_cap])
+    // variational handle: scratch slabs, the two work lists of the chain with their counters (two sets), the snapshot of both
     DevBuf<double> dAviR;
     DevBuf<int32_t> dAviI;
     int aviSlabs = 0;           // wavefront slabs of scratch allocated
     DevBuf<int32_t> dAviList[2], dAviCnt;
     int64_t aviListCap = 0;
-    DevBuf<int32_t> dAviSnap;
-    long long aviSnapSeg[2] = {0, 0};            // ... seg_cap of the snapshot each block holds (0: none)
+    lmpc::ListSnapshot aviSnap[2];
     // closed-loop simulation scratch (simTheta2, simK: allocated by their first user)
     DevBuf<double> simTheta, simTheta2, simU, simFG;
     DevBuf<int32_t> simK;               // per-scenario step counters
@@ -191,7 +196,7 @@ struct lmpc_handle : lmpc_scratch {
     lmpc::LaunchRing<LMPC_ROW_INFO_WORDS, 4> rowRec;
     // ... and of the front passes (lmpc_front_pass_info): the four most recent screening / tiers launches, counted apart
     lmpc::LaunchRing<LMPC_FRONT_INFO_WORDS, 4> frontRec;
-    // option "list_snapshot": every front pass's counter set and work list copied aside for lmpc_work_list_read (dSnap)
+    // option "list_snapshot": every front pass's counter set and work list copied aside for lmpc_work_list_read (snap)
     int listSnapshot = 0;
     DevBuf<int32_t> dRegTable;     // hash table of lmpc_distinct_active_sets_device (lmpc_regions.hip): 16 control words + slots
     int regCap = 0;
@@ -413,7 +418,7 @@ inline const PackLayout &pack_layout(const lmpc_handle *h, const LoopMode &mode,
 // LoopMode included, down launch_wave -> launch_wave_t -> launch_wave_inst -> launch_wave_cfg and launch_row* -> launch_row_shape.
 struct WaveArgs {
     int pass = 0;               // 0: the only pass; 1: first of two (smaller capacity); 2: second (walks the first one's overflow list)
-    WaveList list{};            // work list of a front pass (list == nullptr: the whole batch)
+    WorkList list{};            // work list of a front pass (list == nullptr: the whole batch)
     int cap = 0;                // working-set capacity of this launch (the kernel's ldc = cap | 1)
     int level = -1, nwv = 0;    // preferred LDS staging level (-1 = automatic) and wavefronts per workgroup (0 = automatic)
     WaveSim waveSim{};          // LoopMode::waveSim, keep, raWarm, prof
@@ -422,7 +427,7 @@ struct WaveArgs {
     bool in_loop() const { return waveSim.FG != nullptr || keep; }
 };
 // ... of a launch at the handle's own capacity and tuning ("wave_cap", "wave_level", "wave_nwv")
-inline WaveArgs wave_args(const lmpc_handle *h, const LoopMode &mode, const WaveList &list = WaveList{}) {
+inline WaveArgs wave_args(const lmpc_handle *h, const LoopMode &mode, const WorkList &list = WorkList{}) {
     WaveArgs a;
     a.list = list; a.cap = h->W.cap; a.level = h->waveLevel; a.nwv = h->waveNwv;
     a.waveSim = mode.waveSim; a.keep = mode.keep; a.raWarm = mode.raWarm; a.prof = mode.prof;
@@ -521,7 +526,7 @@ int finalize_avi(lmpc_handle *h);
 void avi_fill_settings(lmpc_handle *h);
 int launch_avi(lmpc_handle *h, int64_t nprob, const double *theta, double *x, int32_t *flag, int32_t *iters,
                uint64_t *active, const uint64_t *warm, hipStream_t st);
-long long avi_list_read(lmpc_handle *h, int which, int32_t *counts, int32_t *list, long long list_words);
+int snapshot_capture_check(lmpc_handle *h, hipStream_t st);      // "list_snapshot": refuses a call inside a stream capture
 // what launch_avi_tiers enqueued, for the handle's record (lmpc_avi_launch_info)
 struct AviLaunchShape { int stage = 0, n = 0, k = 0, list = 0; size_t lds = 0; };
 int launch_avi_tiers(lmpc_handle *h, bool first, int kfirst, unsigned grid, hipStream_t st, const double *theta, double *x,

@@ -23,6 +23,7 @@
 
 #include "lmpc_pack.hpp"
 #include "lmpc_wave_layout.hpp"
+#include "lmpc_worklist.hpp"
 #include "lmpc_tiers.hpp"
 
 #ifndef LMPC_LANE_WAVES
@@ -659,19 +660,17 @@ __global__ __launch_bounds__(256, (N <= 5 ? LMPC_LANE_WAVES : 1)) void lane_kern
     double *__restrict__ X, int32_t *__restrict__ exitflag, int32_t *__restrict__ iters,
     uint64_t *__restrict__ active, const uint64_t *__restrict__ warm,
     const int32_t *__restrict__ list, const int32_t *__restrict__ count, int32_t *__restrict__ count_next,
-    long long seg_cap, int nshards, long long nprob, int tier) {
+    long long seg_cap, long long nprob, int tier) {
     extern __shared__ __align__(16) double lds[];
 
     const int m = P.m, B = blockDim.x, tid = threadIdx.x;
-    // `list` (from screen_kernel) holds the problems that need iterations, in `nshards` segments of
-    // capacity seg_cap with one counter each; block b works on segment b % nshards.  Without a list
-    // the kernel walks the whole batch.  Blocks stride over the work so a fixed grid covers any count.
+    // `list` (from screen_kernel, lmpc_worklist.hpp) holds the problems that need iterations; block b works on segment
+    // b % kShards.  Without a list the kernel walks the whole batch.  Blocks stride, so a fixed grid covers any count.
     // the counter set the next call's screening pass will use is cleared here (saves a memset
     // node per call; this call's screening pass finished before this kernel started)
-    if (count_next && blockIdx.x == 0 && (int)threadIdx.x < nshards) count_next[threadIdx.x * kCountStride] = 0;
-    const int shard = list ? (int)(blockIdx.x % nshards) : 0;
-    const long long first = (list ? (long long)(blockIdx.x / nshards) : (long long)blockIdx.x) * B;
-    const long long stride = (list ? (long long)(gridDim.x / nshards) : (long long)gridDim.x) * B;
+    wl_clear_counts(count_next, tid);
+    const WlWalk wk = list ? wl_walk_block(B) : WlWalk{0, (long long)blockIdx.x * B, (long long)gridDim.x * B};
+    const long long first = wk.first, stride = wk.stride;
     // Small instantiations: everything the first problem needs that does not depend on anything else
     // is requested in ONE round trip -- the segment's count, this lane's first list entry
     // (speculatively: the segment is allocated up to seg_cap, an entry at or beyond the count is simply
@@ -679,13 +678,13 @@ __global__ __launch_bounds__(256, (N <= 5 ? LMPC_LANE_WAVES : 1)) void lane_kern
     // order of the LDS copy: one loop).  The register-bound instantiations (one wavefront per SIMD)
     // keep the plain order: one more live register costs them more than the two round trips.
     constexpr bool kEarly = MA <= 6;
-    if (list) list += (long long)shard * seg_cap;
+    if (list) list = wk.segment(list, seg_cap);
     int32_t pid0 = 0;
     if (kEarly && list) {
         const long long i0 = first + tid;
         pid0 = list[i0 < seg_cap ? i0 : seg_cap - 1];
     }
-    const long long cnt = list ? (long long)count[shard * kCountStride] : nprob;
+    const long long cnt = list ? wk.count(count) : nprob;
     if (!kEarly && first >= cnt) return;
     double *sM = lds;                    // m x N   rows by per-lane constraint index
     double *sG = sM + m * N;             // packed lower triangle of M M'

@@ -37,6 +37,7 @@
 #include "lmpc_pack.hpp"
 #include "lmpc_tiers.hpp"
 #include "lmpc_wave_layout.hpp"
+#include "lmpc_worklist.hpp"
 
 namespace lmpc {
 
@@ -372,14 +373,7 @@ __global__ __launch_bounds__(256) void qp_tiers_kernel(
                 if (P.words > 1) active[pid * P.words + 1] = w1;
             }
         }
-        const bool queue = mine && !finished;
-        const unsigned long long qmask = __ballot(queue);
-        if (qmask != 0ull) {
-            int qbase = 0;
-            if (lane == 0) qbase = atomicAdd(&count[shard * kCountStride], __popcll(qmask));
-            qbase = __shfl(qbase, 0);
-            if (queue) list[(long long)shard * seg_cap + qbase + __popcll(qmask & ((1ull << lane) - 1ull))] = (int32_t)pid;
-        }
+        wl_push(mine && !finished, pid, lane, shard, seg_cap, list, count);
     }
 }
 

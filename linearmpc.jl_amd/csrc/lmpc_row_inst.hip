@@ -119,16 +119,15 @@ int launch_row_shape(lmpc_handle *h, const WaveArgs &a, const RowLaunch &rl, con
         bnbI = reinterpret_cast<int32_t *>(h->dRowBnb.get() + sizeof(R) * nrowsB * bdepth * (size_t)row_snap_reals(S, CAPP));
     }
     // counters: the wavefront kernel's own (launch_wave_cfg: two alternating sets, each launch clears the next one's)
-    constexpr int kP1 = kShards * kCountStride;
     LMPC_TRY(wave_scratch_counters(h, st));
     const int os = h->waveOvfSet;
-    int32_t *const p1Count = h->dOvfCount + os * kP1, *const p1Next = h->dOvfCount + (os ^ 1) * kP1;
-    int32_t *const p2Next = h->dOvfCount + 2 * kP1 + 8 * (os ^ 1);
+    int32_t *const p1Count = count_set(h->dOvfCount.get(), os), *const p1Next = count_set(h->dOvfCount.get(), os ^ 1);
+    int32_t *const p2Next = count_set(h->dOvfCount.get(), 2) + 8 * (os ^ 1);
     int32_t *const queueNext = h->dQueue + 8 * (h->waveCtrSet ^ 1);
     int32_t *queue = nullptr;
     int qchunk = 1;
     const long long nrows = grid * rl.nwv * 4;
-    const WaveList &wl = a.list;
+    const WorkList &wl = a.list;
     if (wl.list != nullptr) {
         queue = h->dQueue + 8 * h->waveCtrSet;
     } else if (nprob > 2 * nrows && h->waveQueue) {

@@ -26,21 +26,22 @@ template <int NTHMAX, int NT, bool SMALL>
 __global__ __launch_bounds__(256) void sim_run_kernel(
     const PackLayout P, const double *__restrict__ C, double *theta, int32_t *kstep, const int T,
     uint64_t *active, const int use_warm, double *U_traj, double *X_traj, int32_t *flag_min,
-    int32_t *__restrict__ list, int32_t *__restrict__ count, const long long seg_cap, const int nshards,
+    int32_t *__restrict__ list, int32_t *__restrict__ count, const long long seg_cap,
     const long long nprob, const int32_t *__restrict__ list_in, const int32_t *count_in,
     const int step_cap, int32_t *__restrict__ park_list, int32_t *park_count, const double *__restrict__ x_in,
     const double *__restrict__ r_in, const double *__restrict__ up_in) {
     static_assert(NT <= 16, "exact parameter count");
     const int m = P.m, tid = threadIdx.x, lane = tid & 63;
-    const int shard = blockIdx.x & (nshards - 1);
+    const WlWalk wk = wl_walk_block(blockDim.x);
+    const int shard = wk.shard;
     // round 0 walks all scenarios; later rounds only those the iterating kernel just advanced -- the list of
     // the round before, shard by shard, so that wavefronts stay full however few scenarios are still running
     long long pid = (long long)blockIdx.x * blockDim.x + tid;
     bool valid = pid < nprob;
     if (list_in != nullptr) {
-        const long long idx = (long long)(blockIdx.x / nshards) * blockDim.x + tid;
-        valid = idx < (long long)count_in[shard * kCountStride];
-        pid = valid ? (long long)list_in[(long long)shard * seg_cap + idx] : 0;
+        const long long idx = wk.first + tid;
+        valid = idx < wk.count(count_in);
+        pid = valid ? (long long)wk.segment(list_in, seg_cap)[idx] : 0;
     }
     const long long pc = valid ? pid : nprob - 1;
     const double ntol = -P.primal_tol;
@@ -277,18 +278,8 @@ __global__ __launch_bounds__(256) void sim_run_kernel(
     // scenarios that used up their step allowance without meeting such a step are parked: a wavefront of a
     // short list would otherwise spend ~2 us per step on a handful of lanes.  The host runs the parked
     // scenarios on, compacted, once the work list has drained.
-    const bool queue = valid && k < T && hard;
-    const unsigned long long mask = __ballot(queue);
-    int basei = 0;
-    if (mask != 0ull && lane == 0) basei = atomicAdd(&count[shard * kCountStride], __popcll(mask));
-    basei = __shfl(basei, 0);
-    if (queue) list[(long long)shard * seg_cap + basei + __popcll(mask & ((1ull << lane) - 1ull))] = (int32_t)pid;
-    const bool park = valid && k < T && !hard;
-    const unsigned long long pmask = __ballot(park);
-    int pbase = 0;
-    if (pmask != 0ull && lane == 0) pbase = atomicAdd(&park_count[shard * kCountStride], __popcll(pmask));
-    pbase = __shfl(pbase, 0);
-    if (park) park_list[(long long)shard * seg_cap + pbase + __popcll(pmask & ((1ull << lane) - 1ull))] = (int32_t)pid;
+    wl_push(valid && k < T && hard, pid, lane, shard, seg_cap, list, count);
+    wl_push(valid && k < T && !hard, pid, lane, shard, seg_cap, park_list, park_count);
 }
 
 }  // namespace lmpc

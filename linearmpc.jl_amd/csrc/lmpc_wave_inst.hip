@@ -18,11 +18,10 @@ int wave_reserve(lmpc_handle *h, int64_t nprob, hipStream_t st) { return wave_re
 
 // The ticket counter and the two sets of overflow counters (launch_wave_cfg describes their layout and protocol)
 int wave_scratch_counters(lmpc_handle *h, hipStream_t st) {
-    constexpr int kP1 = kShards * kCountStride;
     if (h->dQueue && h->dOvfCount) return LMPC_OK;
-    HIP_TRY(h, h->dOvfCount.reserve(2 * kP1 + 64));
+    HIP_TRY(h, h->dOvfCount.reserve(2 * kCountSetWords + 64));
     HIP_TRY(h, h->dQueue.reserve(64 / sizeof(int32_t)));
-    HIP_TRY(h, hipMemsetAsync(h->dOvfCount, 0, sizeof(int32_t) * (2 * kP1 + 64), st));
+    HIP_TRY(h, hipMemsetAsync(h->dOvfCount, 0, sizeof(int32_t) * (2 * kCountSetWords + 64), st));
     HIP_TRY(h, hipMemsetAsync(h->dQueue, 0, 64, st));
     h->waveCtrSet = 0; h->waveOvfSet = 0;
     return LMPC_OK;

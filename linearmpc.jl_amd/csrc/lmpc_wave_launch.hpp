@@ -228,21 +228,17 @@ int launch_wave_cfg(lmpc_handle *h, const WaveArgs &a, const WaveConfig &cfg, co
     // needs a memset in front of it -- two 5 us fill kernels per launch, 4 % of a closed-loop step.  Tickets alternate per
     // LAUNCH; the overflow counters per CALL (h->waveOvfSet, toggled by launch_wave_inst), because the second of two
     // passes reads the first one's as the length of its work list.  Layout of dOvfCount (ints): two first-pass sets
-    // shaped like a work list's counters (kShards words kCountStride apart, only word 0 ever non-zero), then the two
-    // words of the last pass's overflow (the slow path's list).
-    constexpr int kP1 = kShards * kCountStride;
+    // shaped like a work list's counters (lmpc_worklist.hpp; only word 0 ever non-zero), then the two words of the last
+    // pass's overflow (the slow path's list).
     LMPC_TRY(wave_scratch_counters(h, st));
     const int pass = a.pass;
     const int os = h->waveOvfSet;
-    int32_t *const p1Count = h->dOvfCount + os * kP1, *const p1Next = h->dOvfCount + (os ^ 1) * kP1;
-    int32_t *const ovfCount = h->dOvfCount + 2 * kP1 + 8 * os, *const p2Next = h->dOvfCount + 2 * kP1 + 8 * (os ^ 1);
+    int32_t *const p1Count = count_set(h->dOvfCount.get(), os), *const p1Next = count_set(h->dOvfCount.get(), os ^ 1);
+    int32_t *const ovfCount = count_set(h->dOvfCount.get(), 2) + 8 * os, *const p2Next = count_set(h->dOvfCount.get(), 2) + 8 * (os ^ 1);
     int32_t *const queueNext = h->dQueue + 8 * (h->waveCtrSet ^ 1);
 
-    WaveList wl2{};
-    if (pass == 2) {                                     // the first pass's overflow list IS this pass's work list
-        wl2.list = h->dOvfList1; wl2.count = p1Count; wl2.count_next = nullptr; wl2.seg_cap = (long long)nprob;
-    }
-    const WaveList &wl = pass == 2 ? wl2 : a.list;
+    // (the first pass's overflow list IS the second pass's work list)
+    const WorkList wl = pass == 2 ? WorkList{h->dOvfList1, p1Count, nullptr, (long long)nprob} : a.list;
     // more than two problems per resident wavefront: hand them out through the shared counter
     int32_t *queue = nullptr;
     int qchunk = 1;

@@ -534,14 +534,19 @@ class BatchedQP:
         """What the most recent front pass left on the work list (lmpc_work_list_read; needs set_option("list_snapshot",
         1) before the call): (counts, list) with counts the LIST_SHARDS segment counters and list a LIST_SHARDS x
         seg_cap int32 array of which row s holds counts[s] entries -- or None if no snapshot has been taken."""
+        return self._list_read(lib().lmpc_work_list_read)
+
+    def _list_read(self, read, *which):
+        """(counts, list) of one list snapshot through its C reader: asked for the counts and seg_cap first, then, with
+        room for them, for the segments"""
         counts = np.zeros(self.LIST_SHARDS, np.int32)
-        seg = lib().lmpc_work_list_read(self._h, _ptr(counts), None, 0)
+        seg = read(self._h, *which, _ptr(counts), None, 0)
         if seg < 0:
             check(int(seg), self._h)
         if seg == 0:
             return None
         lst = np.zeros((self.LIST_SHARDS, int(seg)), np.int32)
-        seg2 = lib().lmpc_work_list_read(self._h, _ptr(counts), _ptr(lst), lst.size)
+        seg2 = read(self._h, *which, _ptr(counts), _ptr(lst), lst.size)
         if seg2 != seg:
             check(int(seg2) if seg2 < 0 else -1, self._h)
         return counts, lst
@@ -568,17 +573,7 @@ class BatchedQP:
         """What the chain's launch over the whole batch (which = 0) or its lane kernel (1) left on its work list in the
         most recent call (lmpc_avi_list_read; needs set_option("list_snapshot", 1) before the call): (counts, list) as
         work_list_read -- or None if that call made no list."""
-        counts = np.zeros(self.LIST_SHARDS, np.int32)
-        seg = lib().lmpc_avi_list_read(self._h, int(which), _ptr(counts), None, 0)
-        if seg < 0:
-            check(int(seg), self._h)
-        if seg == 0:
-            return None
-        lst = np.zeros((self.LIST_SHARDS, int(seg)), np.int32)
-        seg2 = lib().lmpc_avi_list_read(self._h, int(which), _ptr(counts), _ptr(lst), lst.size)
-        if seg2 != seg:
-            check(int(seg2) if seg2 < 0 else -1, self._h)
-        return counts, lst
+        return self._list_read(lib().lmpc_avi_list_read, int(which))
 
     def ldp(self):
         """The constant pack the kernels use (row-major) -- what tests hand to the oracle."""
