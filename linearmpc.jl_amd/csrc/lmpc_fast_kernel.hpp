@@ -35,6 +35,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "lmpc_lane_kernel.hpp"
 #include "lmpc_tiers.hpp"
 
@@ -52,6 +54,14 @@ constexpr int kFastMaxTiles = 96;          // tiles of 64 problems per workgroup
 #define LMPC_FAST_AHEAD 1
 #endif
 constexpr int kFastAhead = LMPC_FAST_AHEAD;      // tiles a streaming wavefront requests before it consumes the first
+// the staged kernels' register path (fast_body): its own tile loop (0: the loop of the other kernels), which asks for the
+// next tile's record before the screened tile is published (0: behind it)
+#ifndef LMPC_FAST_TURN
+#define LMPC_FAST_TURN 1
+#endif
+#ifndef LMPC_FAST_TURN_EARLY
+#define LMPC_FAST_TURN_EARLY 1
+#endif
 
 // One LDS-DMA piece: every active lane moves 16 bytes from its own global address straight into LDS at
 // lds_dst + 16 * lane (lds_dst wave-uniform, in M0) -- no vector register on the way, 1 KiB per wave-instruction.
@@ -71,6 +81,13 @@ __device__ __forceinline__ void fast_dma16(const void *gsrc, unsigned lds_dst) {
 #endif
 // bytes of one ring slot = one tile of 64 records
 __host__ __device__ constexpr size_t fast_tile_bytes(int NT) { return (size_t)64 * NT * sizeof(double); }
+
+// the values as they are HERE, to the compiler: what computes them stays in front, memory accesses stay where they are
+__device__ __forceinline__ void fast_pin(double &s) { asm volatile("" : "+v"(s) :: "memory"); }
+template <int N> __device__ __forceinline__ void fast_pin(double (&b)[N]) {
+#pragma unroll
+    for (int j = 0; j < N; j++) fast_pin(b[j]);
+}
 
 __device__ __forceinline__ int lds_load(const int *p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -313,7 +330,9 @@ __device__ __forceinline__ void fast_body(
     const int role = (wv + (int)(blockIdx.x & 3)) & 3;
     // ------------------------------------------------------------------ producer: stream this wavefront's tiles
     if (role < nstr) {
-        // A streaming wavefront asks for ONE tile, waits, screens it, asks for the next (kFastAhead = 1).  Measured on
+        // A streaming wavefront has ONE tile in flight and one register set for it (kFastAhead = 1): it asks for a tile,
+        // waits, screens it, publishes it and asks for the next -- the staged kernels' register path asks for the next
+        // BEFORE it publishes, into the registers the screen has just read for the last time (see that loop).  Measured on
         // the headline batch with no point needing iterations (tools/stream_floor.py; one call, cold HBM, event-timed):
         // this form 20.3 us; the next tile requested before the current one is screened (two register sets used
         // alternately; removed) 21.2 us; two / four / seven tiles requested back to back before the first is
@@ -327,9 +346,14 @@ __device__ __forceinline__ void fast_body(
         // trip through LDS costs more than it saves.  tools/stream_floor.hip has the shapes in isolation: one tile
         // per wavefront at full occupancy reads the same bytes in 15.7 us, event overhead of 6.3 us included.)
         double buf[kFastAhead][NT];
-        auto process = [&](long long tile, const double (&th)[NT], bool live) {
-            const long long pid = tile * 64 + lane;
-            const bool valid = live && pid < nprob;
+        // A tile in two halves: screen() is every use of the record -- the fma chains, the adds and the compares --,
+        // publish() everything that makes the result visible (flags, queue, stores).  Back to back they are one tile's
+        // work (process, below); the staged register path asks for its next record between the two.
+        // (held: the record was asked for an iteration ago -- the staged register path -- and the compiler sees no load
+        // to hide: the Dth rows are then read from LDS FIRST and the record's arrival pinned behind them, so that those
+        // reads travel under the record's latency as they do where the request stands in front of them in the same block)
+        auto screen = [&](auto held, double (&th)[NT], const bool valid, double (&bq)[N], double &shift) -> bool {
+            constexpr bool HELD = decltype(held)::value;
             // screening test of screen_kernel: any row of dl + b <= 0 <= du + b violated by more than primal_tol?
             // (the constants come from LDS, uniform addresses, for every tile anew: as scalar loads the compiler
             // kept all ~110 scalar registers' worth of them live, more than there are, parked the kernel's pointers
@@ -347,13 +371,25 @@ __device__ __forceinline__ void fast_body(
             typedef const v2d __attribute__((address_space(3))) *lds_c2p;
             const lds_c2p c2 = (lds_c2p)(size_t)scr_off;
             static_assert(NTHMAX % 2 == 0, "rows of pairs");
-            double bq[N];
+            // (all N rows up to NT = 8 -- at most 20 reads, 80 registers; beyond, where the record itself is 18 - 32
+            // registers, the first row only)
+            constexpr int RQ = (NT + 1) / 2, NA = !HELD ? 0 : (NT > 8 ? 1 : (20 / RQ < N ? 20 / RQ : N));
+            v2d ahead[NA ? NA : 1][RQ];
+            if constexpr (HELD) {
+#pragma unroll
+                for (int j = 0; j < NA; j++)
+#pragma unroll
+                    for (int q = 0; q < RQ; q++) ahead[j][q] = c2[j * (NTHMAX / 2) + q];
+                fast_pin(th);
+            }
 #pragma unroll
             for (int j = 0; j < N; j++) {
                 double row[NTHMAX];
 #pragma unroll
                 for (int q = 0; q < (NT + 1) / 2; q++) {
-                    const v2d v = c2[j * (NTHMAX / 2) + q];
+                    v2d v;
+                    if (j < NA) v = ahead[j][q];
+                    else v = c2[j * (NTHMAX / 2) + q];
                     row[2 * q] = v.x; row[2 * q + 1] = v.y;
                 }
                 double acc = 0.0;
@@ -378,6 +414,14 @@ __device__ __forceinline__ void fast_body(
 #pragma unroll
                 for (int t = 0; t < NT; t++) sh = __builtin_fma(row[t], th[t], sh);
             }
+            shift = sh;
+            return hard;
+        };
+        // (th: the record once more, for the unstaged stores of several outputs only -- the staged kernels never read it
+        // here, which is what lets the register path below overwrite it with the next tile's while this runs)
+        auto publish = [&](long long tile, const double (&bq)[N], const double sh, const bool hard, const bool valid,
+                           const double (&th)[NT]) {
+            const long long pid = tile * 64 + lane;
             const unsigned long long mask = __ballot(hard);
             // every problem gets a flag HERE -- BEFORE a queued problem is published in the ring, so that the release below
             // orders this store in front of the solving lane's final one (issued after the publish, the
@@ -404,7 +448,10 @@ __device__ __forceinline__ void fast_body(
             if (mask != 0ull) {
                 int base = 0;
                 if (lane == 0) base = __hip_atomic_fetch_add(&ctrl[0], __popcll(mask), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                base = __shfl(base, 0);
+                // (staged: the branch is wave-uniform, lane 0 is active and holds the value -- no trip through the LDS
+                // crossbar and its wait to broadcast it)
+                if constexpr (stage) base = __builtin_amdgcn_readfirstlane(base);
+                else base = __shfl(base, 0);
                 if (hard) {
                     const int pos = base + __popcll(mask & ((1ull << lane) - 1ull));
                     if (pos < kFastPay) {
@@ -413,8 +460,17 @@ __device__ __forceinline__ void fast_body(
                         for (int j = 0; j < N; j++) pay[j] = bq[j];
                         if (!stage) pay[N] = sh;
                     }
-                    // (release: the payload is in LDS before the index that announces it)
-                    __hip_atomic_store(&ring[pos], (int32_t)(pid - base0), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    // (release: the payload is in LDS before the index that announces it.  Staged, everything the index
+                    // announces -- payload, x shift, provisional flag -- is in LDS and nothing is in memory, and one
+                    // wavefront's LDS operations complete in the order they were issued (the add on ctrl[2] below relies
+                    // on the same): an LDS wait and a relaxed store order them.  A release store would wait on every
+                    // counter, the next tile's records in flight included -- see the staged register path below.)
+                    if constexpr (stage) {
+                        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                        __hip_atomic_store(&ring[pos], (int32_t)(pid - base0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    } else {
+                        __hip_atomic_store(&ring[pos], (int32_t)(pid - base0), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    }
                 }
             }
             if (!stage && valid && !hard) {
@@ -433,6 +489,12 @@ __device__ __forceinline__ void fast_body(
                 if (iters) iters[pid] = 1;
                 if (active) active[pid * P.words] = 0ull;
             }
+        };
+        auto process = [&](long long tile, double (&th)[NT], bool live) {
+            const bool valid = live && tile * 64 + lane < nprob;
+            double bq[N], sh;
+            const bool hard = screen(std::false_type{}, th, valid, bq, sh);
+            publish(tile, bq, sh, hard, valid, th);
         };
         if (!GATHER && dk >= 2) {
             // Records by LDS-DMA (round 3).  The wavefront owns a ring of dk tile slots in LDS; a tile (64 records,
@@ -547,6 +609,57 @@ __device__ __forceinline__ void fast_body(
                     tl = nx;
                 }
             }
+            }
+        } else if constexpr (STAGE && LMPC_FAST_TURN) {
+            // Staged kernels, records through registers (the in-flight shape: four streaming wavefronts, no rings).  Still
+            // ONE tile and one register set per wavefront, but the next tile is asked for as soon as screen() has read
+            // the record for the last time -- its registers are dead from there on -- and BEFORE this tile is published:
+            // the ballot, the reservation (an LDS atomic and its wait), the payload, the ring store and the loop's own
+            // bookkeeping then run under the next record's latency instead of in front of it.  What keeps publish()
+            // from waiting for that record: its ring store is relaxed behind an LDS wait (see there; a release would
+            // wait on vmcnt as well), and nothing else in it touches a vector-memory counter -- the staged kernels store
+            // to LDS only.  The record's address is a running 64-bit value per lane, clamped to the batch's last
+            // record exactly as load_record clamps (a partial last tile reads that record on its idle lanes and never
+            // beyond the batch); the kernel argument theta is not read again per tile.  A request is made only if the
+            // wavefront has a further tile.  Three batches in flight: 12.84 -> 12.53 us per step, a call issued alone
+            // (not this kernel) unchanged (profiles/fast_turnaround.md).  The early request is the gain: this loop with the
+            // request behind publish() (-DLMPC_FAST_TURN_EARLY=0) measured 12.79, the loop below with the relaxed publish
+            // and no broadcast through LDS (-DLMPC_FAST_TURN=0) 12.80.  Raised priority from the loop's head to the request
+            // (-DLMPC_FAST_TURN_PRIO=1) stayed inside the spread over five alternated runs and is not compiled in.
+            const long long first = t0 + role;
+            if (first < t1) {
+                const uintptr_t last = reinterpret_cast<uintptr_t>(theta + (nprob - 1) * NT);
+                const uintptr_t step = (uintptr_t)nstr * (64 * NT * sizeof(double));
+                uintptr_t at = reinterpret_cast<uintptr_t>(theta + (first * 64 + lane) * NT);
+                typedef const double __attribute__((address_space(1))) *glb_cdp;     // (an integer cast back: say it is memory)
+                auto request = [&]() {
+                    const glb_cdp src = (glb_cdp)(at < last ? at : last);
+#pragma unroll
+                    for (int t = 0; t < NT; t++) buf[0][t] = src[t];
+                };
+                request();
+                for (long long tile = first;; tile += nstr) {
+                    const bool more = tile + nstr < t1;
+#ifdef LMPC_FAST_TURN_PRIO
+                    __builtin_amdgcn_s_setprio(LMPC_FAST_TURN_PRIO);
+#endif
+                    double bq[N], sh;
+                    const bool valid = tile * 64 + lane < nprob;
+                    const bool hard = screen(std::true_type{}, buf[0], valid, bq, sh);
+                    // (every use of the record feeds bq or sh: behind this point its registers are free.  Opaque and a
+                    // memory barrier, or the compiler asks for the next record FIRST, into registers of its own, and
+                    // spills the screen's constants to make room -- 44 instead of 12 spilled registers, seen)
+                    fast_pin(bq);
+                    fast_pin(sh);
+                    at += step;
+                    if (LMPC_FAST_TURN_EARLY && more) request();
+#ifdef LMPC_FAST_TURN_PRIO
+                    __builtin_amdgcn_s_setprio(0);
+#endif
+                    publish(tile, bq, sh, hard, valid, buf[0]);
+                    if (!more) break;
+                    if (!LMPC_FAST_TURN_EARLY) request();
+                }
             }
         } else
         for (long long base = t0 + role; base < t1; base += (long long)kFastAhead * nstr) {
